@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """bench.py -- depth frames/sec through the per-frame KinectFusion path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up for W frames, times K frames and prints the headline line (`value`, `ms_per_step`, the configuration);
+--dump-outputs DIR then also writes what the last timed frame produced (dump_outputs).  Every other block described below -- `roofline`,
+`cpu_baseline`, `parity_witness`, the other configurations, `per_rank`, `lockstep`, `c5` -- is measured only with --full.
 
 A step = one depth frame through  u16-mm -> f32 -> gate -> bilateral -> vertices/normals -> 3-level ICP (10/5/4,
 device-resident Gauss-Newton) -> TSDF integrate -> raycast.  Frames are synthetic (Scene S, hybkinectfu_amd/scene.py) and
@@ -600,6 +604,87 @@ def slab_block(name, args, world, rank, device, dist, n_frames, warmup, n_unique
 STAGE_NAMES = ["upload", "preprocess", "track", "integrate", "raycast", "integrate_kernel", "mcubes", "raycast_kernel"]
 
 
+DUMP_SEED = 20241015
+DUMP_VOXELS = 1 << 20          # voxels of the TSDF volume sampled into tsdf_sample / weight_sample (the same indices every run)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(pipe, out_dir, wl, rank, dist, chunk_layers=64):
+    """--dump-outputs: what the timed path handed its caller after its last frame, as DIR/<name>.npy --
+    pose (4x4 f32, the tracker's device-resident pose), model_vertices / model_normals (the raycast maps the next frame tracks against,
+    rows x cols x 4 f32), tsdf_sample / weight_sample (f32 at DUMP_VOXELS voxel indices drawn from a fixed seed over the whole volume,
+    x fastest), sample_index (f64: those indices) and counters (f64: tracked, iterations, updated_last, updated_total, frames_fused,
+    frames_lost).  z-slab runs: every rank fills in the sampled voxels of the layers it owns and rank 0 writes."""
+    import torch
+    res = wl["res"]
+    tracked, pose, _, iters = pipe.track_result()
+    st = pipe.stats()
+    n_vox = res ** 3
+    idx = np.random.default_rng(DUMP_SEED).integers(0, n_vox, min(DUMP_VOXELS, n_vox), dtype=np.int64)
+    dev_idx = torch.from_numpy(idx).cuda()
+    tsdf_s = torch.zeros(len(idx), device="cuda", dtype=torch.float32)
+    weight_s = torch.zeros_like(tsdf_s)
+    z_own0, z_own1 = pipe.ctx.owned
+    layer = res * res
+    t = torch.empty(min(chunk_layers, z_own1 - z_own0) * layer, device="cuda", dtype=torch.float32)
+    w = torch.empty_like(t)
+    for za in range(z_own0, z_own1, chunk_layers):
+        zb = min(za + chunk_layers, z_own1)
+        torch.cuda.synchronize()                 # the previous chunk's gathers have read t / w before the context's stream overwrites them
+        pipe.ctx.download_volume_device(za, zb, t.data_ptr(), w.data_ptr())
+        pipe.ctx.sync()
+        sel = (dev_idx >= za * layer) & (dev_idx < zb * layer)
+        tsdf_s[sel] = t[dev_idx[sel] - za * layer]
+        weight_s[sel] = w[dev_idx[sel] - za * layer]
+    torch.cuda.synchronize()
+    if dist is not None:
+        # the owned ranges do not overlap: a sampled voxel's bits come from one rank, zeros from the others (an integer sum keeps them exact)
+        dist.all_reduce(tsdf_s.view(torch.int32), op=dist.ReduceOp.SUM)
+        dist.all_reduce(weight_s.view(torch.int32), op=dist.ReduceOp.SUM)
+    if rank != 0:
+        return
+    arrays = dict(pose=np.asarray(pose, np.float32).reshape(4, 4),
+                  model_vertices=pipe.ctx.download_map(K.MAP_MODEL_VERTICES).astype(np.float32),
+                  model_normals=pipe.ctx.download_map(K.MAP_MODEL_NORMALS).astype(np.float32),
+                  tsdf_sample=tsdf_s.cpu().numpy(), weight_sample=weight_s.cpu().numpy(), sample_index=idx.astype(np.float64),
+                  counters=np.array([float(tracked), iters, st["updated_last"], st["updated_total"], st["frames_fused"], st["frames_lost"]], np.float64))
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def headline(args, wl, world, fps, dt, n_before, deferral_on, lost, slab, pipe, dist):
+    """The result line of every run: the headline rate of the timed frames and the configuration they ran"""
+    res, size, cam = wl["res"], wl["size"], wl["cam"]
+    maxw = int(P["volume_max_weight"])
+    out = dict(metric="depth frames/sec into TSDF (integrate+ICP+raycast)", value=round(fps, 2), unit="frames/s", n_gpus=world,
+               steps=args.steps, warmup=args.warmup, ms_per_step=round(1000.0 * dt / args.steps, 4), higher_is_better=True,
+               scaling="weak" if world == 1 else "strong", vs_baseline=None, dtype="f32", data="synthetic",
+               value_resident=round(fps, 2),
+               deferral=dict(enabled=deferral_on, frames_fused_before_timed=n_before, timed_frames=args.steps, max_weight=maxw,
+                             note="deferred free-space weights (integrate.hip, DEFER): from the second fused frame on, a quarter brick whose 128 voxels hold tsdf 1 and are "
+                                  "all observed as free space again is counted, not read or written; bit-identical results (tests/test_gpu_saturation.py, "
+                                  "tools/sat_equivalence.py).  Default: on for volumes of 768^3 and finer (1024^3 +46 %, 2048^3 +86 % frames/s), off below (512^3 with "
+                                  "the stock 2 m gate: -1.5 %, the fusion pass is not memory-bound there); kf_set_defer / KF_INTEGRATE_SAT=0|2 override"),
+               config=dict(workload=wl["desc"], volume="%d^3 @ %g m" % (res, size), image="%dx%d" % (cam[0], cam[1]),
+                           tracker=("CameraPoseFinderSDF (max %d iterations, device-resident)" % int(P["sdf_max_iter_nums"])
+                                    if (wl.get("tracker") == "sdf" or (slab and args.tracker == "sdf")) else "ICP 10/5/4 (device-resident Gauss-Newton)"),
+                           frames_lost=int(lost), env=env_knobs(),
+                           world_size=(dist.get_world_size() if dist is not None else 1),
+                           backend=("none" if dist is None else ("rccl" if args.backend == "nccl" else "gloo (rehearsal: host-staged collectives, ranks may share a GPU)")),
+                           partition="none" if not slab else
+                           "z-slab x%d (boundaries: %s); %d halo layers per side RE-INTEGRATED by both neighbours (recomputed, not exchanged per frame; when the boundaries move -- "
+                           "--rebalance-every -- whole brick layers travel rank to rank: SlabMigrator); "
+                           "raycast merge = MIN all-reduce (crossing parameter + vertex parameter as one 64-bit word, 2.5 MB at VGA) + integer SUM all-reduce (normal from the vertex's owner as three words, 3.7 MB); ICP %s"
+                           % (world, "balanced from a one-frame 256^3 probe of the work per z-layer" if (world > 1 and args.slab_balance == "probe") else "equal thickness",
+                              pipe.halo, args.icp_mode),
+                           slab_ranges=([list(r) for r in pipe.ranges] if slab else None)))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -636,6 +721,13 @@ def main():
                          "(device = local_rank %% device_count), collectives staged through host memory")
     ap.add_argument("--collective-selftest", action="store_true",
                     help="CPU only: run the z-slab pipeline's collective sequence over gloo on synthetic candidates and print one JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the roofline leg, per-stage times, the other configurations, PCIe-inclusive and steady-state rates, "
+                         "the CPU baseline and the parity witness (N=1), per-rank statistics, the lock-step check and the C5 block (N > 1), the mesh extraction "
+                         "(--config c5).  Without it a run sets up, warms up, times --steps frames and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed frames, write what the last of them handed the caller (pose, raycast model maps, a seeded sample of the "
+                         "TSDF volume, fusion counters) to DIR/<name>.npy in float32 / float64 (bench_outputs/ is git-ignored for this)")
     args = ap.parse_args()
 
     # ---- launcher: a parent that has touched neither the GPU nor the library starts the N ranks ----
@@ -686,11 +778,12 @@ def main():
     slab = not (world == 1 and not args.force_slab)
     if not slab:
         from hybkinectfu_amd.pipeline import SingleGpuPipeline as Pipe
-        pipe = Pipe(kcam, res, size, wl, device=device, max_triangles=(16_000_000 if wl.get("extract_mesh") else 4_000_000 if not args.no_extras else 0))
+        pipe = Pipe(kcam, res, size, wl, device=device,
+                    max_triangles=(0 if not args.full else 16_000_000 if wl.get("extract_mesh") else 4_000_000 if not args.no_extras else 0))
     else:
         from hybkinectfu_amd.pipeline import SlabPipeline as Pipe
         pipe = Pipe(kcam, res, size, wl, rank=rank, world=world, device=device, icp_mode=args.icp_mode, tracker=args.tracker,
-                    max_triangles=(16_000_000 // world + 1_000_000 if wl.get("extract_mesh") else 0),
+                    max_triangles=(16_000_000 // world + 1_000_000 if (args.full and wl.get("extract_mesh")) else 0),
                     ranges=balanced_ranges(args, kcam, res, size, wl, world, device, dev_frames.data_ptr()), rebalance_every=args.rebalance_every)
 
     def run(first, count):
@@ -712,17 +805,18 @@ def main():
     run(base, args.warmup)
     barrier()
     s0 = pipe.stats()
-    # Time the fusion kernel (bit 5) and the whole integrate stage (bit 3) inside the timed region with HIP events on the context's
-    # own stream.  Every `period`-th frame is sampled so that a short run still yields >= 5 timed launches (a timed launch costs
-    # ~6 us of stream time -- its dispatch carries two event packets: every 2nd frame timed takes 1.4 % off `value` at C2, every 4th
-    # 0.7 %, every 8th nothing measurable; the kernel's duration varies by < 2 % from launch to launch).
-    timer_period = max(1, min(8, args.steps // 5))
-    # (every event pair costs ~3 us of stream time: at --steps 20 the kernel's pair alone is 0.9 % of the timed region, the stage's pair
-    # another 1.4 % -- so when the per-stage times are measured anyway on the 50 frames AFTER the timed region (N=1 extras), the
-    # integrate STAGE is taken from there and only the roofline kernel is timed inside the region)
-    extras_planned = world == 1 and not wl.get("extract_mesh") and not args.force_slab and not args.no_extras
-    pipe.stage_timers((timer_period << 8) | (1 << 5) | (0 if extras_planned else (1 << 3)))
-    barrier()
+    if args.full:
+        # Time the fusion kernel (bit 5) and the whole integrate stage (bit 3) inside the timed region with HIP events on the context's
+        # own stream.  Every `period`-th frame is sampled so that a short run still yields >= 5 timed launches (a timed launch costs
+        # ~6 us of stream time -- its dispatch carries two event packets: every 2nd frame timed takes 1.4 % off `value` at C2, every 4th
+        # 0.7 %, every 8th nothing measurable; the kernel's duration varies by < 2 % from launch to launch).  A run without --full times no stage.
+        timer_period = max(1, min(8, args.steps // 5))
+        # (every event pair costs ~3 us of stream time: at --steps 20 the kernel's pair alone is 0.9 % of the timed region, the stage's pair
+        # another 1.4 % -- so when the per-stage times are measured anyway on the 50 frames AFTER the timed region (N=1 extras), the
+        # integrate STAGE is taken from there and only the roofline kernel is timed inside the region)
+        extras_planned = world == 1 and not wl.get("extract_mesh") and not args.force_slab and not args.no_extras
+        pipe.stage_timers((timer_period << 8) | (1 << 5) | (0 if extras_planned else (1 << 3)))
+        barrier()
     t0 = time.perf_counter()
     run(base + args.warmup, args.steps)
     barrier()
@@ -731,7 +825,7 @@ def main():
         t = torch.tensor([dt], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    ms, cnt = pipe.read_stage_ms()
+    ms, cnt = pipe.read_stage_ms() if args.full else (None, None)
     s1 = pipe.stats()
     lost = s1["frames_lost"] - s0["frames_lost"]
     n_upd = (s1["updated_total"] - s0["updated_total"])
@@ -742,6 +836,18 @@ def main():
     else:
         n_upd_all = n_upd
     fps = args.steps / dt
+    sat_env = os.environ.get("KF_INTEGRATE_SAT", "1")      # (kf_defer_enabled, integrate.hip: by default volumes of 768^3 and finer defer)
+    deferral_on = (sat_env == "2" or (sat_env == "1" and res >= 768)) and os.environ.get("KF_INTEGRATE_PAIRS", "1") != "0" and not wl.get("color")
+    out = headline(args, wl, world, fps, dt, base + args.warmup, deferral_on, lost, slab, pipe, dist)
+    if args.dump_outputs:
+        dump_outputs(pipe, args.dump_outputs, wl, rank, dist)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        pipe.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     # ---- roofline of the dominant HBM kernel: the fusion pass k_integrate_pairs ----
     # The timed region runs the kernel with deferred free-space weights (DEFER): it provably does not move the reference's bytes, so the
@@ -753,8 +859,6 @@ def main():
     defer_ms = float(ms[5]) / max(defer_launches, 1)
     stage_ms = float(ms[3]) / max(int(cnt[3]), 1)
     n_upd_region = n_upd
-    sat_env = os.environ.get("KF_INTEGRATE_SAT", "1")      # (kf_defer_enabled, integrate.hip: by default volumes of 768^3 and finer defer)
-    deferral_on = (sat_env == "2" or (sat_env == "1" and res >= 768)) and os.environ.get("KF_INTEGRATE_PAIRS", "1") != "0" and not wl.get("color")
     plain_frames = 24 if res <= 1024 else 12
     pipe.ctx.set_defer(0)
     run(base + args.warmup + args.steps, 2)                 # the first plain launch is preceded by the flush of every pending count
@@ -827,31 +931,7 @@ def main():
             total = int(tt.item())
         mesh = dict(triangles=total, ms=round(1000.0 * dtm, 3), note="kf_marching_cubes on every rank's slab after the timed frames (wall time incl. the count read-back)")
 
-    n_before = base + args.warmup
-    maxw = int(P["volume_max_weight"])
-    out = dict(metric="depth frames/sec into TSDF (integrate+ICP+raycast)", value=round(fps, 2), unit="frames/s", n_gpus=world,
-               steps=args.steps, warmup=args.warmup, ms_per_step=round(1000.0 * dt / args.steps, 4), higher_is_better=True,
-               scaling="weak" if world == 1 else "strong", vs_baseline=None, dtype="f32", data="synthetic",
-               value_resident=round(fps, 2),
-               deferral=dict(enabled=deferral_on, frames_fused_before_timed=n_before, timed_frames=args.steps, max_weight=maxw,
-                             note="deferred free-space weights (integrate.hip, DEFER): from the second fused frame on, a quarter brick whose 128 voxels hold tsdf 1 and are "
-                                  "all observed as free space again is counted, not read or written; bit-identical results (tests/test_gpu_saturation.py, "
-                                  "tools/sat_equivalence.py).  Default: on for volumes of 768^3 and finer (1024^3 +46 %, 2048^3 +86 % frames/s), off below (512^3 with "
-                                  "the stock 2 m gate: -1.5 %, the fusion pass is not memory-bound there); kf_set_defer / KF_INTEGRATE_SAT=0|2 override"),
-               config=dict(workload=wl["desc"], volume="%d^3 @ %g m" % (res, size), image="%dx%d" % (cam[0], cam[1]),
-                           tracker=("CameraPoseFinderSDF (max %d iterations, device-resident)" % int(P["sdf_max_iter_nums"])
-                                    if (wl.get("tracker") == "sdf" or (slab and args.tracker == "sdf")) else "ICP 10/5/4 (device-resident Gauss-Newton)"),
-                           frames_lost=int(lost), env=env_knobs(),
-                           world_size=(dist.get_world_size() if dist is not None else 1),
-                           backend=("none" if dist is None else ("rccl" if args.backend == "nccl" else "gloo (rehearsal: host-staged collectives, ranks may share a GPU)")),
-                           partition="none" if not slab else
-                           "z-slab x%d (boundaries: %s); %d halo layers per side RE-INTEGRATED by both neighbours (recomputed, not exchanged per frame; when the boundaries move -- "
-                           "--rebalance-every -- whole brick layers travel rank to rank: SlabMigrator); "
-                           "raycast merge = MIN all-reduce (crossing parameter + vertex parameter as one 64-bit word, 2.5 MB at VGA) + integer SUM all-reduce (normal from the vertex's owner as three words, 3.7 MB); ICP %s"
-                           % (world, "balanced from a one-frame 256^3 probe of the work per z-layer" if (world > 1 and args.slab_balance == "probe") else "equal thickness",
-                              pipe.halo, args.icp_mode),
-                           slab_ranges=([list(r) for r in pipe.ranges] if slab else None)),
-               roofline=roofline)
+    out["roofline"] = roofline
     if mesh is not None:
         out["mesh_extraction"] = mesh
     if slab and dist is not None:

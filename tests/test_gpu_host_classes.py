@@ -41,7 +41,7 @@ def oracle_sequence(res, size, cam, trunc, n, sdf=False):
 
 
 @pytest.mark.parametrize("host_loop", [False, True])
-def test_hybkinectfu_icp_sequence(host_loop):
+def test_hybkinectfu_icp_sequence(host_loop, tmp_path):
     res, size, cam = 128, 3.0, S.vga_camera()
     trunc = 5 * size / res
     n = 5
@@ -68,7 +68,7 @@ def test_hybkinectfu_icp_sequence(host_loop):
     ntri = app.generate_mesh()
     otris = O.marching_cubes(ovol, False, 300 * size / res, 600000)
     assert abs(ntri - len(otris)) <= 0.05 * len(otris)          # the volumes differ only through the mm-level pose differences
-    path = "/tmp/hybkf_test_mesh.obj"
+    path = str(tmp_path / "hybkf_test_mesh.obj")
     ok, nv, nf = app.save_mesh(path)
     assert ok and os.path.getsize(path) > 1000 and nf <= ntri and nv < 3 * ntri // 2
     gm = H.app_mesh()["faces"]                                  # no degenerate, no duplicate face survives (meshData.cpp:281, :42-82)

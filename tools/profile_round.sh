@@ -11,7 +11,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-extras --no-scaling-reference"
+COMMON="--full --no-cpu-baseline --no-extras --no-scaling-reference"
 run() {   # name, bench args for the trace pass, bench args for the PMC passes   (environment: as exported by the caller)
   local NAME=$1 TRACE_ARGS=$2 PMC_ARGS=$3
   rocprofv3 --kernel-trace --stats -d $OUT/trace_$NAME --output-format csv -- python3 $ROOT/bench.py $TRACE_ARGS $COMMON > $OUT/bench_trace_$NAME.log 2>&1 || return 1
