@@ -1019,6 +1019,12 @@ int kf_tail_cull_discard(kf_ctx* c) {
   return 0;
 }
 
+extern "C" int kf_get_fusion_form(kf_ctx* c, kf_fusion_form* out) {
+  if (!c || !out) return KF_ERR_ARG;
+  *out = c->fusion_form;
+  return 0;
+}
+
 extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weight_color, const kf_mat44* transform,
                                    const kf_integrate_params* ip, const kf_camera_params* dcam, const kf_camera_params* rcam) {
   if (!c || !ip || !dcam) return KF_ERR_ARG;
@@ -1059,11 +1065,12 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
   // The cull may have run already, as the tail of this frame's tracking launch (kf_icp_track, persistent loop): consumed when it saw what this call
   // would have shown it -- the device-resident pose, the same parameters, depth map, tile tables, slab and counter set; otherwise undone.
   bool culled = false;
+  kf_fusion_form form; memset(&form, 0, sizeof(form));                       // (kf_get_fusion_form) what this call launches, noted where it is launched
   if (c->tail_cull.armed) {
     const auto& t = c->tail_cull;
     culled = !transform && !defer && tiles_ready && t.parity == a.parity && t.sdf_trunc == a.sdf_trunc && t.max_dist == a.max_dist &&
              memcmp(&t.dcam, dcam, sizeof(*dcam)) == 0 && t.trunc_serial == c->trunc_serial && t.bz0 == c->vol.bz0 && t.bz1 == c->vol.bz1;
-    if (culled) { c->tail_cull.armed = 0; c->tail_cull.consumed++; }
+    if (culled) { c->tail_cull.armed = 0; c->tail_cull.consumed++; form.cull = KF_CULL_TAIL; }
     else { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
   }
   c->cull_hint.valid = transform ? 0 : 1;                // what the next tracking launch may cull for
@@ -1077,6 +1084,7 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
     if (sift_env == -2) { const char* e = getenv("KF_CULL_SIFT"); sift_env = e ? atoi(e) : -1; }
     const bool sift = sift_env >= 0 ? sift_env != 0 : n_macro >= 100000u;
     const int n_wg = (int)((n_macro + SIFT_CELLS - 1) / SIFT_CELLS);
+    form.cull = sift ? KF_CULL_SIFT : KF_CULL_MACRO; form.cull_defer = a.defer_cull ? 1 : 0;
     if (sift && a.defer_cull) hipLaunchKernelGGL(k_integrate_cull_sift<true>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg);
     else if (sift) hipLaunchKernelGGL(k_integrate_cull_sift<false>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg);
     else if (a.defer_cull) hipLaunchKernelGGL(k_integrate_cull<true>, dim3(cgrid), dim3(CULL_WAVES * 64), 0, c->stream, a);
@@ -1109,19 +1117,23 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
   hipEvent_t ke0 = nullptr, ke1 = nullptr;
   const bool timed = kf_evt_attach(c, KF_STAGE_INTEGRATE_KERNEL, &ke0, &ke1);
   const bool count = c->wgt0_tracking && c->wgt0_valid;   // the COUNT instantiations, while a host keeps asking kf_get_volume_stats for the observed-voxel count
-  bool counted = false;
 #define FUSE_LAUNCH(K) do { if (timed) hipExtLaunchKernelGGL(K, dim3(grid), dim3(256), 0, c->stream, ke0, ke1, 0, a); \
                             else hipLaunchKernelGGL(K, dim3(grid), dim3(256), 0, c->stream, a); } while (0)
+  // each instantiation is named once, and the form it is noted as comes from the same template arguments
+#define FUSE_NOTE(KIND, BR_, D_, C_, L_, N_) do { form.kernel = (KIND); form.bricks = (BR_); form.defer = (D_); form.color = (C_); form.layers = (L_); form.count = (N_); } while (0)
+#define FUSE_PAIRS(BR_, D_, C_, L_, N_) do { FUSE_NOTE(KF_FUSE_PAIRS, BR_, D_, C_, L_, N_); FUSE_LAUNCH((k_integrate_pairs<BR_, D_, C_, L_, N_>)); } while (0)
+#define FUSE_PIPE(D_, N_) do { FUSE_NOTE(KF_FUSE_PIPE, 1, D_, false, false, N_); FUSE_LAUNCH((k_integrate_pairs_pipe<D_, N_>)); } while (0)
+#define FUSE_BRICKS(C_, BR_) do { FUSE_NOTE(KF_FUSE_BRICKS, BR_, false, C_, false, false); FUSE_LAUNCH((k_integrate_bricks<C_, BR_>)); } while (0)
   static int color_pairs = -1;                            // 1 (default): colour through the packed-pair kernel; 0: the scalar kernel (A/B)
   if (color_pairs < 0) { const char* e = getenv("KF_INTEGRATE_COLOR_PAIRS"); color_pairs = e ? atoi(e) : 1; }
   if (has_color && color_pairs) {
     static int cbr = -1;                                   // bricks in flight per workgroup of the colour variant (KF_INTEGRATE_BR overrides)
     if (cbr < 0) { const char* e = getenv("KF_INTEGRATE_BR"); cbr = e ? atoi(e) : 2; if (cbr != 1 && cbr != 2 && cbr != 4) cbr = 2; }
-    if (cbr == 1) FUSE_LAUNCH((k_integrate_pairs<1, false, true>));
-    else if (cbr == 2) FUSE_LAUNCH((k_integrate_pairs<2, false, true>));
-    else FUSE_LAUNCH((k_integrate_pairs<4, false, true>));
+    if (cbr == 1) FUSE_PAIRS(1, false, true, false, false);
+    else if (cbr == 2) FUSE_PAIRS(2, false, true, false, false);
+    else FUSE_PAIRS(4, false, true, false, false);
   }
-  else if (has_color) FUSE_LAUNCH((k_integrate_bricks<true, 1>));
+  else if (has_color) FUSE_BRICKS(true, 1);
   else {
     // bricks in flight per workgroup (see the grid above): 1, or 4 for large volumes.  KF_INTEGRATE_BR overrides.
     static int br_env = -1;
@@ -1140,31 +1152,37 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
     else
 #endif
     if (pairs && a.layer_work) {                           // a sampled frame (kf_count_layer_work): the one-brick form that also counts per brick layer
-      if (defer) FUSE_LAUNCH((k_integrate_pairs<1, true, false, true>));
-      else FUSE_LAUNCH((k_integrate_pairs<1, false, false, true>));
+      if (defer) FUSE_PAIRS(1, true, false, true, false);
+      else FUSE_PAIRS(1, false, false, true, false);
     } else if (pairs && br == 1 && (pipe_env < 0 ? defer : pipe_env != 0)) {     // the one-brick form as a two-stage pipeline: by default where workgroups walk many bricks (KF_INTEGRATE_PIPE=0 / 1 forces)
-      if (defer && count) { FUSE_LAUNCH((k_integrate_pairs_pipe<true, true>)); counted = true; }
-      else if (defer) FUSE_LAUNCH((k_integrate_pairs_pipe<true>));
-      else if (count) { FUSE_LAUNCH((k_integrate_pairs_pipe<false, true>)); counted = true; }
-      else FUSE_LAUNCH((k_integrate_pairs_pipe<false>));
+      if (defer && count) FUSE_PIPE(true, true);
+      else if (defer) FUSE_PIPE(true, false);
+      else if (count) FUSE_PIPE(false, true);
+      else FUSE_PIPE(false, false);
     } else if (pairs) {
       if (defer) {
-        if (br == 1 && count) { FUSE_LAUNCH((k_integrate_pairs<1, true, false, false, true>)); counted = true; }
-        else if (br == 1) FUSE_LAUNCH((k_integrate_pairs<1, true>));
-        else if (br == 2) FUSE_LAUNCH((k_integrate_pairs<2, true>));
-        else FUSE_LAUNCH((k_integrate_pairs<4, true>));
-      } else if (br == 1 && count) { FUSE_LAUNCH((k_integrate_pairs<1, false, false, false, true>)); counted = true; }
-      else if (br == 1) FUSE_LAUNCH((k_integrate_pairs<1, false>));
-      else if (br == 2) FUSE_LAUNCH((k_integrate_pairs<2, false>));
-      else if (count) { FUSE_LAUNCH((k_integrate_pairs<4, false, false, false, true>)); counted = true; }
-      else FUSE_LAUNCH((k_integrate_pairs<4, false>));
-    } else if (br == 1) FUSE_LAUNCH((k_integrate_bricks<false, 1>));
-    else if (br == 2) FUSE_LAUNCH((k_integrate_bricks<false, 2>));
-    else FUSE_LAUNCH((k_integrate_bricks<false, 4>));
+        if (br == 1 && count) FUSE_PAIRS(1, true, false, false, true);
+        else if (br == 1) FUSE_PAIRS(1, true, false, false, false);
+        else if (br == 2) FUSE_PAIRS(2, true, false, false, false);
+        else FUSE_PAIRS(4, true, false, false, false);
+      } else if (br == 1 && count) FUSE_PAIRS(1, false, false, false, true);
+      else if (br == 1) FUSE_PAIRS(1, false, false, false, false);
+      else if (br == 2) FUSE_PAIRS(2, false, false, false, false);
+      else if (count) FUSE_PAIRS(4, false, false, false, true);
+      else FUSE_PAIRS(4, false, false, false, false);
+    } else if (br == 1) FUSE_BRICKS(false, 1);
+    else if (br == 2) FUSE_BRICKS(false, 2);
+    else FUSE_BRICKS(false, 4);
   }
+#undef FUSE_BRICKS
+#undef FUSE_PIPE
+#undef FUSE_PAIRS
+#undef FUSE_NOTE
 #undef FUSE_LAUNCH
+  form.grid = grid; form.calls = c->fusion_form.calls + 1;
+  c->fusion_form = form;
   // the running count of observed voxels (kf_get_volume_stats): a fusion launch that did not count leaves it behind the volume
-  if (!counted) c->wgt0_valid = 0;
+  if (!form.count) c->wgt0_valid = 0;
   if (c->wgt0_frames_unasked < (1 << 30)) ++c->wgt0_frames_unasked;
   if (c->wgt0_tracking && c->wgt0_frames_unasked > 64) c->wgt0_tracking = 0;        // nobody has asked for 64 frames: the plain kernels again
   if (timed) kf_evt_attached_done(c, KF_STAGE_INTEGRATE_KERNEL);

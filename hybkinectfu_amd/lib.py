@@ -67,6 +67,15 @@ class VolumeStats(C.Structure):
                 ("updated_total", C.c_uint64), ("frames_fused", C.c_uint64), ("frames_lost", C.c_uint64)]
 
 
+class FusionForm(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("bricks", C.c_int32), ("defer", C.c_int32), ("color", C.c_int32), ("layers", C.c_int32),
+                ("count", C.c_int32), ("cull", C.c_int32), ("cull_defer", C.c_int32), ("grid", C.c_uint32), ("calls", C.c_uint32)]
+
+
+FUSE_NONE, FUSE_PAIRS, FUSE_PIPE, FUSE_BRICKS = 0, 1, 2, 3           # kf_fusion_form::kernel
+CULL_NONE, CULL_TAIL, CULL_MACRO, CULL_SIFT = 0, 1, 2, 3             # kf_fusion_form::cull
+
+
 VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("color", "<f4", (3,))])
 TRI_DTYPE = np.dtype([("v", VERTEX_DTYPE, (3,))])
 
@@ -89,6 +98,7 @@ SYMBOLS = [
     "kf_sdf_partition_begin", "kf_sdf_partition_step", "kf_sdf_partition_finish", "kf_set_defer", "kf_inject_track_stall",
     "kf_download_volume_device", "kf_upload_volume_device", "kf_resize_slab", "kf_count_layer_work", "kf_read_layer_work",
     "kf_upload_depth_mm_next", "kf_take_next_depth", "kf_cull_tail_counts", "kf_count_observed_voxels", "kf_get_fusion_counters",
+    "kf_get_fusion_form",
 ]
 
 
@@ -338,6 +348,12 @@ class Context:
         tp = C.byref(Mat44.of(pose)) if pose is not None else None
         _chk(self.lib.kf_integrate_volume(self.h, int(has_color), int(angle_weight), tp, C.byref(ip), C.byref(self.cam),
                                           C.byref(self.rgb_cam)), "kf_integrate_volume")
+
+    def fusion_form(self):
+        """what the last integrate launched (kf_get_fusion_form): a dict of the kf_fusion_form fields"""
+        f = FusionForm()
+        _chk(self.lib.kf_get_fusion_form(self.h, C.byref(f)), "kf_get_fusion_form")
+        return {name: int(getattr(f, name)) for name, _ in FusionForm._fields_}
 
     def set_defer(self, mode):
         """deferred free-space weights: 1 on, 0 off (the plain fusion kernel on every frame), -1 follow the environment"""

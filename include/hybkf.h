@@ -171,6 +171,23 @@ int kf_wait_track_result(kf_ctx* ctx, kf_track_result* out);
 int kf_inject_track_stall(kf_ctx* ctx, int launches);
 /* diagnostics: culls that ran as the tail of a tracking launch and were consumed by kf_integrate_volume / were undone (see kf_integrate_volume) */
 int kf_cull_tail_counts(kf_ctx* ctx, uint32_t* consumed, uint32_t* undone);
+/* diagnostics: which instantiation of the fusion pass and which cull the last kf_integrate_volume launched (host-side bookkeeping at the dispatch,
+ * no device work).  The environment switches (KF_INTEGRATE_*, KF_CULL_*, KF_OBSERVED_COUNT), the volume's size and the context's state pick the form;
+ * every form gives the same bits, and the tests check each against the CPU oracle with this read-back telling them which one ran. */
+enum { KF_FUSE_NONE = 0, KF_FUSE_PAIRS = 1 /* k_integrate_pairs<bricks, defer, color, layers, count> */, KF_FUSE_PIPE = 2 /* k_integrate_pairs_pipe<defer, count> */,
+       KF_FUSE_BRICKS = 3 /* k_integrate_bricks<color, bricks> */ };
+enum { KF_CULL_NONE = 0, KF_CULL_TAIL = 1 /* run by the tracking launch's tail, consumed */, KF_CULL_MACRO = 2 /* k_integrate_cull<defer> */,
+       KF_CULL_SIFT = 3 /* k_integrate_cull_sift<defer> */ };
+typedef struct kf_fusion_form {
+  int32_t  kernel;          /* KF_FUSE_* (KF_FUSE_NONE before the first call, and for the timing experiments of the KF_EXPERIMENTS build) */
+  int32_t  bricks;          /* bricks in flight per workgroup (BR) */
+  int32_t  defer, color, layers, count;   /* 0 / 1: the instantiation's template switches */
+  int32_t  cull;            /* KF_CULL_* */
+  int32_t  cull_defer;      /* 0 / 1: the cull's template switch (0 for the tail) */
+  uint32_t grid;            /* workgroups of the fusion launch */
+  uint32_t calls;           /* kf_integrate_volume calls that launched a fusion pass since kf_create */
+} kf_fusion_form;
+int kf_get_fusion_form(kf_ctx* ctx, kf_fusion_form* out);
 
 /* cudaIntegrateVolume  src/cuda/integrateVolume.cu:78-96.  transform == NULL: use the device-resident pose and
  * integrate only if the last kf_*_track call tracked (src/HybKinectfu.cpp:123-140).

@@ -228,6 +228,10 @@ def test_c4_integrate_1024_cubed_and_two_slabs():
     assert halo == 8
     whole = K.Context(kcam, res, size, P["volume_max_weight"], levels=3, max_triangles=4_000_000)
     slabs = [K.Context(kcam, res, size, P["volume_max_weight"], levels=3, max_triangles=4_000_000, slab=r, halo=halo) for r in PL.slab_ranges(res, 2)]
+    # the same frames through the plain read-modify-write kernel (deferral off: four bricks in flight, k_integrate_pairs<4, false>) -- the kernel
+    # bench.py --full's plain_kernel_roofline measures at this size
+    plain = K.Context(kcam, res, size, P["volume_max_weight"], levels=3)
+    plain.set_defer(0)
     ovol = O.OVolume(res, size, P["volume_max_weight"])
     import torch
     dev = torch.device("cuda", 0)
@@ -239,18 +243,24 @@ def test_c4_integrate_1024_cubed_and_two_slabs():
         mm = S.render_depth_mm(pose, cam, size)
         tr, fl, v, n = oracle_preprocess(mm, ocam, tmax)
         n_o = O.integrate(ovol, tr, n, None, False, False, pose, P["integrate_sdf_trunc"], dist, ocam, ocam)
-        for c in [whole] + slabs:
+        for c in [whole, plain] + slabs:
             c.upload_depth_mm(mm)
             c.preprocess(P["depth_trunc_min"], tmax, P["filter_sigma_pixel"], P["filter_sigma_depth"])
             c.integrate(pose, P["integrate_sdf_trunc"], dist)
+        f = plain.fusion_form()
+        assert (f["kernel"], f["bricks"], f["defer"], f["color"], f["layers"], f["count"]) == (K.FUSE_PAIRS, 4, 0, 0, 0, 0), f
         st = whole.stats()
         assert st["updated_last"] == n_o and n_o > 30_000_000
         assert st["weight_gt0"] == O.count_weight_gt0(ovol)
         assert sum(c.stats()["weight_gt0"] for c in slabs) == st["weight_gt0"]
+        sp = plain.stats()
+        assert sp["updated_last"] == n_o and sp["weight_gt0"] == st["weight_gt0"]
     # planes: a z range in front of the camera and one across the slab boundary at z = 512
     for z0, z1 in ((96, 160), (480, 544)):
-        t, w = whole.download_volume(z0, z1)
-        assert np.array_equal(bits(t), bits(ovol.tsdf[z0:z1])) and np.array_equal(bits(w), bits(ovol.weight[z0:z1]))
+        for c in (whole, plain):
+            t, w = c.download_volume(z0, z1)
+            assert np.array_equal(bits(t), bits(ovol.tsdf[z0:z1])) and np.array_equal(bits(w), bits(ovol.weight[z0:z1]))
+    plain.close()
     for c, (z0, z1) in zip(slabs, PL.slab_ranges(res, 2)):
         a, b = (z1 - 64, z1) if z0 == 0 else (z0, z0 + 64)
         t, w = c.download_volume(a, b)
