@@ -39,7 +39,8 @@ public:
   RayCasterParams _raycast_params;
   MarchingcubeParams _marchingcube_params;
   IOParams _io_params;
-  // not in the reference: which GPU / z-slab this process owns (one process per GPU)
+  // not in the reference: which GPU / z-slab this process owns (one process per GPU).  HybKinectfu passes slab_* to its one context but
+  // raycasts the whole volume and merges nothing; for slabs whose model maps are merged use HybKinectfuSlabs (hybkf_slabs.hpp)
   int device = 0; unsigned slab_z_begin = 0, slab_z_end = 0, slab_halo = 0;
 protected:
   AppParams() { setDefaults(256, 3.0f); }

@@ -1,0 +1,97 @@
+// hybkf_slabs.cpp -- HybKinectfuSlabs (hybkf_slabs.hpp) over the slab group's C ABI.
+#include "hybkf_slabs.hpp"
+#include <string.h>
+
+std::vector<unsigned> SlabLayout::evenCuts(unsigned resolution, unsigned members) {
+  std::vector<unsigned> cuts(1, 0);
+  const unsigned nb = resolution / 8, base = members ? nb / members : 0, extra = members ? nb % members : 0;
+  unsigned b = 0;
+  for (unsigned r = 0; r < members; ++r) { b += base + (r < extra ? 1 : 0); cuts.push_back(b * 8); }
+  return cuts;
+}
+
+HybKinectfuSlabs::~HybKinectfuSlabs() { if (_group) kf_group_destroy(_group); _group = nullptr; }
+
+bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectfu::init (src/HybKinectfu.cpp:28-61) with a group for the data manager
+  if (_inited) return false;
+  const AppParams* p = AppParams::instance();
+  kf_config cfg; memset(&cfg, 0, sizeof(cfg));
+  cfg.depth_camera = p->_depth_camera_params; cfg.rgb_camera = p->_rgb_camera_params;
+  cfg.volume.resolution = p->_volume_params.nResolution; cfg.volume.size_m = p->_volume_params.fVolumeMeterSize; cfg.volume.max_weight = p->_volume_params.fWeightMax;
+  cfg.pyramid_levels = p->_icp_params.nPyramidLevels; cfg.max_triangles = p->_marchingcube_params.uMaxTriangles;
+  cfg.has_color = 0; cfg.device = p->device;
+  kf_group_params gp; memset(&gp, 0, sizeof(gp));
+  gp.trunc_min = p->_depth_prepocess_params.fMinTrunc; gp.trunc_max = p->_depth_prepocess_params.fMaxTrunc;
+  gp.sigma_pixel = p->_depth_prepocess_params.fSigmaPixel; gp.sigma_depth = p->_depth_prepocess_params.fSigmaDepth;
+  const IcpParams& ip = p->_icp_params;
+  gp.icp = {ip.nPyramidLevels, ip.fNormSinThres, ip.fDistThres, ip.fDistShake, ip.fAngleShake};
+  gp.integrate = {p->_integrate_params.fSdfTruncation, p->_integrate_params.fMaxIntegrateDist};
+  gp.raycast.ray_increment = p->_raycast_params.fRayIncrement;
+  if (layout.cuts.size() < 2) return check(KF_GROUP_ERR_ARG);
+  const uint32_t members = (uint32_t)layout.cuts.size() - 1;
+  if (!layout.devices.empty() && layout.devices.size() != members) return check(KF_GROUP_ERR_ARG);
+  if (layout.backend == KF_GROUP_RCCL_RANK && layout.unique_id.size() != KF_GROUP_UNIQUE_ID_BYTES) return check(KF_GROUP_ERR_ARG);
+  std::vector<int32_t> devs(layout.devices.begin(), layout.devices.end());
+  if (!check(kf_group_create(&cfg, &gp, layout.backend, members, layout.cuts.data(), devs.empty() ? nullptr : devs.data(), layout.halo,
+                             layout.unique_id.empty() ? nullptr : layout.unique_id.data(), layout.rank, layout.world, &_group)))
+    return false;
+  Mat44 camera_pose0 = Mat44::getIdentity();                   // the same expression as HybKinectfu::init
+  camera_pose0.setTranslation((float)(p->_volume_params.fVolumeMeterSize / 2.0), (float)(p->_volume_params.fVolumeMeterSize / 2.0),
+                              -p->_depth_prepocess_params.fMinTrunc);
+  kf_mat44 k; memcpy(k.m, camera_pose0.entries, sizeof(k.m));
+  if (!check(kf_group_set_pose(_group, &k))) return false;
+  _pose = camera_pose0;
+  _inited = true;
+  return true;
+}
+
+bool HybKinectfuSlabs::enqueueFrame(const DepthFrameData& d, const ColorFrameData&) {
+  if (!_inited) return false;
+  if (!check(kf_group_frame(_group, d.mm, d.on_device ? 1 : 0, (uint32_t)d.cols, (uint32_t)d.rows, d.frameId()))) return false;
+  _pending = true;
+  return true;
+}
+
+bool HybKinectfuSlabs::processNewFrame(const DepthFrameData& d, const ColorFrameData& c) {   // :98-160
+  return enqueueFrame(d, c) && syncVerdict();
+}
+
+bool HybKinectfuSlabs::syncVerdict() {
+  kf_track_result r;
+  if (!check(kf_group_track_result(_group, &r, 1))) return false;
+  memcpy(_pose.entries, r.pose.m, sizeof(_pose.entries));
+  _last_tracked = r.tracked != 0; _pending = false;
+  return true;
+}
+
+bool HybKinectfuSlabs::lastTracked() {
+  if (_pending) syncVerdict();
+  return _last_tracked;
+}
+
+Mat44 HybKinectfuSlabs::getCameraPose() {
+  lastTracked();
+  return _pose;
+}
+
+void HybKinectfuSlabs::generateMesh() {                        // MeshGeneratorMarchingcube::generateMesh, src/MeshGeneratorMarchingcube.cpp:23-29
+  if (!_inited) return;
+  const AppParams* p = AppParams::instance();
+  check(kf_group_marching_cubes(_group, 300 * p->_volume_params.fVolumeMeterSize / p->_volume_params.nResolution));
+}
+
+unsigned HybKinectfuSlabs::triangleCount() {
+  uint32_t n = 0;
+  if (_inited) check(kf_group_triangle_count(_group, &n));
+  return n;
+}
+
+bool HybKinectfuSlabs::saveMesh(const std::string& filename) {   // :61-96 on the slab-major triangle sequence
+  const unsigned n = triangleCount();
+  if (n == 0) return false;
+  std::vector<kf_triangle> tris(n);
+  if (!check(kf_group_read_triangles(_group, tris.data(), 0, n))) return false;
+  _mesh.setTriangles(tris.data(), n, false);
+  _mesh.weldMesh();
+  return _mesh.mesh().saveToFile(filename);
+}

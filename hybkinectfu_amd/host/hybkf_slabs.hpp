@@ -1,0 +1,51 @@
+// hybkf_slabs.hpp -- HybKinectfuSlabs: the reference's HybKinectfu surface (src/HybKinectfu.h) over a slab group (include/hybkf_group.h),
+// for C++ callers that want more than one GPU -- or the z-slab protocol on one GPU.  It reads the same AppParams as HybKinectfu (camera,
+// volume, ICP, depth preprocess, integrate, raycast) plus a SlabLayout.  HybKinectfu itself stays the one-context class and ignores
+// AppParams::slab_*.  Built as libhybkf_slabs.so, above libhybkf_host.so, libhybkf_group.so and libhybkf.so.
+#pragma once
+#include <stdint.h>
+#include <string>
+#include <vector>
+#include "hybkf_host.hpp"
+#include "../../include/hybkf_group.h"
+
+struct SlabLayout {
+  int backend = KF_GROUP_LOCAL;                  // KF_GROUP_LOCAL / KF_GROUP_RCCL_ALL / KF_GROUP_RCCL_RANK
+  std::vector<unsigned> cuts;                    // members + 1 brick-aligned z cuts, 0 .. resolution (RCCL_RANK: {z0, z1}, this rank's own slab)
+  std::vector<int> devices;                      // one per member; empty: AppParams::device for all
+  unsigned halo = 0;                             // 0: the thinnest the raycast accepts (pipeline.slab_halo_layers)
+  std::vector<uint8_t> unique_id;                // RCCL_RANK: kf_group_unique_id of rank 0, handed to every rank
+  unsigned rank = 0, world = 1;                  // RCCL_RANK
+  // equal slabs over `members` members (sizes differing by at most one brick layer), pipeline.slab_ranges without a work probe
+  static std::vector<unsigned> evenCuts(unsigned resolution, unsigned members);
+};
+
+class HybKinectfuSlabs {
+public:
+  HybKinectfuSlabs() {}
+  ~HybKinectfuSlabs();
+  HybKinectfuSlabs(const HybKinectfuSlabs&) = delete;             // owns its group: one owner, one kf_group_destroy
+  HybKinectfuSlabs& operator=(const HybKinectfuSlabs&) = delete;
+  bool init(const SlabLayout& layout);
+  // one frame through every member and the merge; blocks for the tracking verdict, like HybKinectfu::processNewFrame
+  bool processNewFrame(const DepthFrameData& depth_frame, const ColorFrameData& rgb_frame);
+  // streaming: no host synchronisation; lastTracked() / getCameraPose() read the verdict
+  bool enqueueFrame(const DepthFrameData& depth_frame, const ColorFrameData& rgb_frame);
+  bool lastTracked();
+  Mat44 getCameraPose();
+  // marching cubes on every member; saveMesh welds the slab-major triangles (= the whole volume's order) and writes .ply / .obj / .off
+  void generateMesh();
+  bool saveMesh(const std::string& filename);
+  unsigned triangleCount();
+  const MeshData& mesh() const { return _mesh.mesh(); }
+  kf_group* group() const { return _group; }
+  int lastError() const { return _err; }
+private:
+  bool check(int status) { if (status) _err = status; return status == 0; }
+  bool syncVerdict();
+  kf_group* _group = nullptr;
+  MeshGeneratorMarchingcube _mesh;
+  Mat44 _pose = Mat44::getIdentity();
+  bool _inited = false, _last_tracked = true, _pending = false;
+  int _err = 0;
+};

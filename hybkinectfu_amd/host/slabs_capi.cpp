@@ -1,0 +1,68 @@
+// slabs_capi.cpp -- a flat C surface over HybKinectfuSlabs (hybkf_slabs.hpp) for ctypes callers, in the style of host_capi.cpp's hkf_app_*.
+#include "hybkf_slabs.hpp"
+#include <string.h>
+
+static HybKinectfuSlabs* g_slabs = nullptr;
+
+extern "C" {
+
+// AppParams::setDefaults + the camera / volume / truncation arguments hkf_app_init takes, then HybKinectfuSlabs::init over `members`
+// slabs cut at cuts[0..members] (NULL: even slabs); devices: one per member (NULL: `device` for all)
+int hkf_slabs_init(unsigned volume_res, float volume_size, unsigned depth_cols, unsigned depth_rows, float cx, float cy, float fx, float fy,
+                   unsigned max_triangles, float sdf_trunc, float integrate_dist, float trunc_max, int device,
+                   int backend, unsigned members, const unsigned* cuts, const int* devices, unsigned halo) {
+  AppParams* p = AppParams::instance();
+  p->setDefaults(volume_res, volume_size);
+  p->_depth_camera_params = {depth_cols, depth_rows, cx, cy, fx, fy};
+  p->_rgb_camera_params = p->_depth_camera_params;
+  p->_marchingcube_params.uMaxTriangles = max_triangles;
+  if (sdf_trunc > 0) { p->_integrate_params.fSdfTruncation = sdf_trunc; p->_raycast_params.fRayIncrement = 0.7f * sdf_trunc; }
+  if (integrate_dist > 0) p->_integrate_params.fMaxIntegrateDist = integrate_dist;
+  if (trunc_max > 0) p->_depth_prepocess_params.fMaxTrunc = trunc_max;
+  p->device = device;
+  delete g_slabs; g_slabs = nullptr;
+  SlabLayout layout;
+  layout.backend = backend;
+  if (members == 0 || members > KF_GROUP_MAX_MEMBERS) return KF_GROUP_ERR_ARG;
+  layout.cuts = cuts ? std::vector<unsigned>(cuts, cuts + members + 1) : SlabLayout::evenCuts(volume_res, members);
+  if (devices) layout.devices.assign(devices, devices + members);
+  layout.halo = halo;
+  g_slabs = new HybKinectfuSlabs();
+  if (!g_slabs->init(layout)) { const int e = g_slabs->lastError(); delete g_slabs; g_slabs = nullptr; return e ? e : KF_GROUP_ERR_STATE; }
+  return 0;
+}
+void hkf_slabs_shutdown() { delete g_slabs; g_slabs = nullptr; }
+void* hkf_slabs_group() { return g_slabs ? (void*)g_slabs->group() : nullptr; }
+
+// HybKinectfuSlabs::processNewFrame; 1 tracked, 0 lost, <0 error
+int hkf_slabs_process_frame(const uint16_t* mm, int on_device, unsigned frame_id) {
+  if (!g_slabs) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
+  ColorFrameData col;
+  if (!g_slabs->processNewFrame(d, col)) return -2;
+  return g_slabs->lastTracked() ? 1 : 0;
+}
+int hkf_slabs_enqueue_frame(const uint16_t* mm, int on_device, unsigned frame_id) {
+  if (!g_slabs) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
+  ColorFrameData col;
+  return g_slabs->enqueueFrame(d, col) ? 0 : -2;
+}
+int hkf_slabs_get_pose(float out16[16]) {
+  if (!g_slabs) return -1;
+  Mat44 m = g_slabs->getCameraPose();
+  memcpy(out16, m.entries, 64);
+  return g_slabs->lastTracked() ? 1 : 0;
+}
+int hkf_slabs_generate_mesh() { if (!g_slabs) return -1; g_slabs->generateMesh(); return (int)g_slabs->triangleCount(); }
+int hkf_slabs_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
+  if (!g_slabs) return -1;
+  const bool ok = g_slabs->saveMesh(filename);
+  if (n_vertices) *n_vertices = (unsigned)(g_slabs->mesh().vertices.size() / 3);
+  if (n_faces) *n_faces = (unsigned)(g_slabs->mesh().faces.size() / 3);
+  return ok ? 1 : 0;
+}
+int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
+}

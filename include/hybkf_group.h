@@ -1,0 +1,114 @@
+/*
+ * hybkf_group.h -- C ABI of slab groups (libhybkf_group.so): one native owner of N z-slab contexts that runs the per-frame
+ * collective sequence of the slab merge itself, over RCCL or on one device.
+ *
+ * A group holds `members` kf_ctx, member i owning voxel layers [z_cuts[i], z_cuts[i+1]) plus a halo on each side (KF_GROUP_RCCL_RANK: the one
+ * member owns [z_cuts[0], z_cuts[1]), this rank's slab of the world's layout).  Per frame and
+ * member, kf_group_frame enqueues what pipeline.SlabPipeline runs with replicated ICP and speculative normals:
+ *   1. depth in          a host frame is copied once per device into a group-owned buffer; kf_set_depth_mm_device
+ *   2. kf_preprocess     (trunc_min, trunc_max, sigma_pixel, sigma_depth)
+ *   3. kf_icp_track      every member tracks the whole image (replicated: the same pose bits everywhere); from here on the
+ *                        device-resident pose (NULL transform), so a lost frame is handled on the device
+ *   4. kf_integrate_volume           own layers + halo
+ *   5. kf_raycast_volume_slab_cross_spec
+ *   6. MIN all-reduce of the 64-bit crossing words
+ *   7. kf_slab_ray_normals_spec
+ *   8. integer SUM all-reduce of the 3-word normal candidates
+ *   9. kf_set_model_maps_rays        -> every member holds the merged model maps (and levels 1, 2 of their pyramids)
+ * with near / far planes trunc_min / trunc_max.  No host synchronisation and no memset / memcpy of a per-frame buffer inside
+ * kf_group_frame: the kernels write every pixel of their outputs.
+ *
+ * Backends:
+ *   KF_GROUP_LOCAL      N members on ONE device, one group stream.  The two all-reduces are streaming kernels that reduce the N
+ *                       members' buffers into one group buffer which every member then reads.  For checking the protocol and for
+ *                       one-GPU use: it is NOT faster than one whole-volume context (every member marches every ray and runs its own ICP).
+ *   KF_GROUP_RCCL_ALL   one process, one member per device (distinct devices), one communicator per member (ncclCommInitAll);
+ *                       each member on its context's own stream, the N calls of a collective inside ncclGroupStart / End.
+ *   KF_GROUP_RCCL_RANK  one process per GPU (torchrun / MPI style): one member here, ncclCommInitRank from a unique id that the
+ *                       caller obtained on one rank with kf_group_unique_id and handed to every rank.
+ *
+ * Status codes are those of libhybkf.so (0 ok, hip errors, KF_GROUP_ERR_*); kf_group_error_string names them.  Every entry point
+ * restores the caller's current HIP device.  A member call that fails mid-frame puts the group into a failed state: every later
+ * call returns KF_GROUP_ERR_STATE (kf_group_destroy still frees it), and no collective is issued after the failure.
+ */
+#ifndef HYBKF_GROUP_H_
+#define HYBKF_GROUP_H_
+#include <stdint.h>
+#include <stddef.h>
+#include "hybkf.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct kf_group kf_group;
+
+enum { KF_GROUP_LOCAL = 0, KF_GROUP_RCCL_ALL = 1, KF_GROUP_RCCL_RANK = 2 };
+enum { KF_GROUP_MAX_MEMBERS = 16, KF_GROUP_UNIQUE_ID_BYTES = 128, KF_GROUP_MAX_TIMED_FRAMES = 4096 };
+/* the same values as libhybkf.so's own argument / state / allocation errors; KF_GROUP_ERR_RCCL: an RCCL call failed */
+enum { KF_GROUP_ERR_ARG = 1001, KF_GROUP_ERR_STATE = 1002, KF_GROUP_ERR_ALLOC = 1003, KF_GROUP_ERR_RCCL = 1004 };
+
+/* what pipeline.SlabPipeline reads from scene.STOCK and its workload dict */
+typedef struct kf_group_params {
+  float trunc_min, trunc_max;           /* depth gate of kf_preprocess, also the raycast's near / far planes */
+  float sigma_pixel, sigma_depth;       /* bilateral filter */
+  kf_icp_params icp;                    /* pyramid_levels is taken from the base config */
+  kf_integrate_params integrate;
+  kf_raycast_params raycast;
+} kf_group_params;
+
+const char* kf_group_error_string(int status);
+
+/* ncclGetUniqueId into out (KF_GROUP_UNIQUE_ID_BYTES bytes), for KF_GROUP_RCCL_RANK */
+int kf_group_unique_id(uint8_t out[128]);
+
+/* Checked before any HIP or RCCL call (KF_GROUP_ERR_ARG):
+ *   members in 1..16; LOCAL / RCCL_ALL: the whole layout, z_cuts[0] = 0, z_cuts[members] = resolution, rising strictly, multiples of 8;
+ *   RCCL_RANK: members = 1 and z_cuts = {z0, z1}, this rank's own slab: multiples of 8, z0 < z1 <= resolution, z0 = 0 exactly for rank 0
+ *   and z1 = resolution exactly for rank world - 1 (every rank passes its own pair; the pairs of ranks 0 .. world-1 must tile the volume);
+ *   halo (0: computed) not thinner than ceil(ray_increment / voxel) + 2 rounded up to 8 layers (pipeline.slab_halo_layers);
+ *   base->has_color == 0 (the slab raycast has no colour);
+ *   devices (NULL: base->device for every member): LOCAL all equal, RCCL_ALL all distinct, RCCL_RANK exactly one member;
+ *   unique_id / rank < world only for RCCL_RANK (ignored otherwise).
+ * base->slab_* are ignored: each member's slab comes from z_cuts. */
+int kf_group_create(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
+                    const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world, kf_group** out);
+/* the same checks alone, without creating anything (no HIP or RCCL call): 0 or KF_GROUP_ERR_ARG */
+int kf_group_validate(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
+                      const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world);
+int kf_group_destroy(kf_group* g);
+int kf_group_members(kf_group* g, uint32_t* members, uint32_t* halo);
+/* every member's device-resident pose (kf_set_pose).  kf_group_create already sets HybKinectfu::init's: identity rotation, camera at
+ * (size / 2, size / 2, -trunc_min) */
+int kf_group_set_pose(kf_group* g, const kf_mat44* pose);
+
+/* Enqueue one frame (asynchronous).  on_device = 0: mm is host memory, copied once per device; on_device = 1: mm is device memory
+ * that every member's device can read (for one device: a plain device buffer).  It must stay unchanged until the frame's
+ * preprocess has run on every member (kf_group_synchronize, or stream order on a caller stream that follows the group's). */
+int kf_group_frame(kf_group* g, const uint16_t* mm, int on_device, uint32_t cols, uint32_t rows, uint32_t frame_id);
+/* the same with one device frame per member (RCCL_ALL across devices: each member reads the copy on its own device) */
+int kf_group_frame_members(kf_group* g, const uint16_t* const* dev_mm, uint32_t cols, uint32_t rows, uint32_t frame_id);
+/* member 0's kf_read_track_result (blocking).  check_lockstep: also compare every member's pose bits, verdict, status and
+ * frames fused / lost with member 0's; a disagreement returns KF_GROUP_ERR_STATE (in-process members only: a RCCL_RANK
+ * group compares nothing across processes). */
+int kf_group_track_result(kf_group* g, kf_track_result* out, int check_lockstep);
+/* borrowed: for read-backs (maps, volume, stats).  The group owns the context and its stream; do not destroy it or change its stream. */
+int kf_group_member(kf_group* g, uint32_t i, kf_ctx** out);
+/* kf_marching_cubes on every member (each extracts its own layers) */
+int kf_group_marching_cubes(kf_group* g, float threshold);
+int kf_group_triangle_count(kf_group* g, uint32_t* count);                                     /* sum over the members, blocking */
+/* triangles [first, first + count) of the slab-major sequence: member 0's, then member 1's, ... = the whole volume's canonical order */
+int kf_group_read_triangles(kf_group* g, kf_triangle* dst, uint32_t first, uint32_t count);
+/* hipEvent pair around each frame's merge (steps 6-9), on member 0's stream; kf_group_read_merge_ms blocks, returns the total
+ * and the frame count since the last read, and resets them.  At most KF_GROUP_MAX_TIMED_FRAMES frames are timed between two reads
+ * (the event pool stops growing there; later frames run untimed and are not counted): read at least that often. */
+int kf_group_merge_timing(kf_group* g, int on);
+int kf_group_read_merge_ms(kf_group* g, float* total_ms, uint32_t* frames);
+int kf_group_synchronize(kf_group* g);
+/* the stream member i's work is enqueued on (LOCAL: the one group stream) */
+void* kf_group_stream(kf_group* g, uint32_t i);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* HYBKF_GROUP_H_ */
