@@ -231,6 +231,7 @@ struct kf_ctx {
   unsigned long long* layer_work; int layer_work_frames;   // per-brick-layer update counts of the next `layer_work_frames` integrate calls (kf_count_layer_work)
   int defer_override;            // kf_set_defer: -1 follow the environment (default), 0 never defer, 1 defer
   kf_fusion_form fusion_form;    // what the last kf_integrate_volume launched (kf_get_fusion_form)
+  kf_raycast_form raycast_form;  // what the last raycast launch took (kf_get_raycast_form)
   int pend_live;                 // a DEFER fusion pass has run since the volume was last reset / uploaded / flushed: deferred-weight words may be set
   unsigned vol_flags_serial, mc_zero_serial;   // bumped when brick flags may have been CLEARED (reset, upload) / the serial the class tables were last zeroed for
   void* host_pinned;                  // small pinned staging buffer (4 KiB); byte KF_PINNED_STALL_WORD: the ICP loop's stall word

@@ -49,7 +49,8 @@ struct RaycastArgs {
   int meso_words;                // words of the meso table (16^3-voxel cells) to keep in LDS behind the macro / super tables (0: it does not fit)
   int shared_grad;               // 1: a crossing's six gradient taps come from one 32-voxel neighbourhood (grad_shared.h; KF_RAYCAST_SHARED_GRAD=0: six separate lookups; 2: shared, with every other wave forced down the fallback -- tests)
   int bounds_meso;               // 1: where the volume has at most 8192 meso cells (up to 256^3), the tile bounds come from the meso table (KF_RAYCAST_BOUNDS_MESO=0: from the macro table)
-  int tile_bounds;               // 1: every workgroup first bounds its tile's rays by the non-empty macro cells its frustum meets (rc_tile_bounds; KF_RAYCAST_BOUNDS=0: off)
+  int tile_bounds;               // 1: every workgroup first bounds its tile's rays by the non-empty macro cells its frustum meets (rc_tile_bounds; KF_RAYCAST_BOUNDS=0: off,
+                                 // 2: tests -- always through the super-cell list, whatever the volume's size)
   int exp_mode;                  // timing experiments only (KF_RAYCAST_EXP): 1 = stop at the crossing without evaluating it
   KfCounters* work;              // measurement passes only (kf_stage_timers bit 16): count the reference march's samples and the hits
 };
@@ -287,7 +288,7 @@ __device__ __forceinline__ void rc_tile_bounds(const RaycastArgs& a, const unsig
   // a 256^3 volume has only 8^3 macro cells (RaycastArgs::bounds_meso; the table is in LDS)
   const int nq = v.nq;
   const bool by_meso = a.bounds_meso && a.meso_words != 0 && nq * nq * nq <= RAYCAST_THREADS * 16;
-  if (by_meso || nm * nm * nm <= RAYCAST_THREADS * 16) {
+  if (a.tile_bounds != 2 && (by_meso || nm * nm * nm <= RAYCAST_THREADS * 16)) {
     // few cells (macro: up to 512^3 = 4096): every thread tests its share of them directly -- one barrier instead of two, no list.  A thread takes whole BYTES of the
     // table (one LDS read per eight cells, then only the set bits), cells numbered x-fastest
     const unsigned* tbl = by_meso ? s_meso : s_macro;
@@ -577,7 +578,21 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
   if (meso_env < 0) { const char* e = getenv("KF_RAYCAST_MESO"); meso_env = e ? atoi(e) : 1; }
   a.meso_words = (meso_env && macro_bytes + meso_bytes <= RAYCAST_LDS_BYTES) ? c->vol.meso_words : 0;      // (2048^3: 256 KiB, no)
   macro_bytes += (size_t)a.meso_words * 4;                  // from here on: everything in front of the per-brick bits
-  a.neg_words = (macro_bytes + neg_bytes <= RAYCAST_LDS_BYTES) ? (int)(neg_bytes / 4) : 0;
+  static int neg_env = -1;                                  // KF_RAYCAST_NEG_LDS=0 (tests): brick flags from global memory at any size
+  if (neg_env < 0) { const char* e = getenv("KF_RAYCAST_NEG_LDS"); neg_env = e ? atoi(e) : 1; }
+  a.neg_words = (neg_env && macro_bytes + neg_bytes <= RAYCAST_LDS_BYTES) ? (int)(neg_bytes / 4) : 0;
+  // (kf_get_raycast_form) what this launch is, noted where its arguments are final; the kernel and the grid where it is launched
+  kf_raycast_form form; memset(&form, 0, sizeof(form));
+  form.output = out_ta ? (a.out_spec ? KF_RC_OUT_TA_SPEC : KF_RC_OUT_TA) : out_t ? KF_RC_OUT_T : KF_RC_OUT_MAPS;
+  form.tile_bounds = a.tile_bounds ? 1 : 0;
+  if (a.tile_bounds) {                                      // rc_tile_bounds' choice, from the same quantities
+    const int nq = c->vol.nq, nm = c->vol.nm;
+    const bool by_meso = a.bounds_meso && a.meso_words != 0 && nq * nq * nq <= RAYCAST_THREADS * 16;
+    form.bounds_path = (a.tile_bounds != 2 && by_meso) ? KF_RC_BOUNDS_MESO : (a.tile_bounds != 2 && nm * nm * nm <= RAYCAST_THREADS * 16) ? KF_RC_BOUNDS_MACRO : KF_RC_BOUNDS_LIST;
+  }
+  form.meso_lds = a.meso_words != 0; form.neg_lds = a.neg_words != 0;
+  form.shared_grad = a.shared_grad & 255; form.view_half = a.shared_grad >> 8; form.pyramid = model_pyr ? 1 : 0;
+  form.calls = c->raycast_form.calls + 1;
   kf_evt_begin(c, KF_STAGE_RAYCAST);
   {
     hipEvent_t ke0 = nullptr, ke1 = nullptr;               // the kernel's own timer rides on its dispatch (kf_evt_attach): the kernel as rocprofv3 sees it
@@ -609,6 +624,7 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
       const size_t rider_lds = behind ? (size_t)RIDER_LDS_BYTES : 2 * (BIL_TX + 8) * (BIL_TY + 8) * sizeof(float);
       const size_t lds2 = lds > rider_lds ? lds : rider_lds;
       const dim3 g2((unsigned)(n_rc + n_bil));
+      form.kernel = behind ? KF_RC_BEHIND : KF_RC_FILTER; form.fast = fast ? 1 : 0; form.grid = g2.x;
       if (fast) {
         if (timed) hipExtLaunchKernelGGL(k_raycast_prefetch<true>, g2, dim3(RAYCAST_THREADS), (unsigned)lds2, c->stream, ke0, ke1, 0, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
         else hipLaunchKernelGGL(k_raycast_prefetch<true>, g2, dim3(RAYCAST_THREADS), lds2, c->stream, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
@@ -627,14 +643,25 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
       c->prefetch_valid = 1; c->fp_done = 1;
       c->fp_tiles = build_tiles ? 1 : 0; c->fp_tiles_dist = c->fuse_max_dist; c->fp_tiles_min = (build_tiles && b.acc.n) ? 1 : 0;
       if (build_tiles) c->tiles_clear = 0;
-    } else if (timed) {
-      hipExtLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), (unsigned)lds, c->stream, ke0, ke1, 0, a);
-      kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
-    } else hipLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), lds, c->stream, a);
+    } else {
+      form.kernel = KF_RC_PLAIN; form.grid = grid.x * grid.y;
+      if (timed) {
+        hipExtLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), (unsigned)lds, c->stream, ke0, ke1, 0, a);
+        kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
+      } else hipLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), lds, c->stream, a);
+    }
   }
   kf_evt_end(c, KF_STAGE_RAYCAST);
   if (model_pyr) c->model_pyr_ok = 1;
+  c->raycast_form = form;
   return (int)hipGetLastError();
+}
+
+static_assert(sizeof(kf_raycast_form) == 48, "lib.py RaycastForm");
+extern "C" int kf_get_raycast_form(kf_ctx* c, kf_raycast_form* out) {
+  if (!c || !out) return KF_ERR_ARG;
+  *out = c->raycast_form;
+  return 0;
 }
 
 extern "C" int kf_raycast_volume(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp,

@@ -76,6 +76,17 @@ FUSE_NONE, FUSE_PAIRS, FUSE_PIPE, FUSE_BRICKS = 0, 1, 2, 3           # kf_fusion
 CULL_NONE, CULL_TAIL, CULL_MACRO, CULL_SIFT = 0, 1, 2, 3             # kf_fusion_form::cull
 
 
+class RaycastForm(C.Structure):
+    _fields_ = [("kernel", C.c_int32), ("fast", C.c_int32), ("output", C.c_int32), ("tile_bounds", C.c_int32), ("bounds_path", C.c_int32),
+                ("meso_lds", C.c_int32), ("neg_lds", C.c_int32), ("shared_grad", C.c_int32), ("view_half", C.c_int32), ("pyramid", C.c_int32),
+                ("grid", C.c_uint32), ("calls", C.c_uint32)]
+
+
+RC_NONE, RC_PLAIN, RC_FILTER, RC_BEHIND = 0, 1, 2, 3                  # kf_raycast_form::kernel
+RC_BOUNDS_NONE, RC_BOUNDS_MESO, RC_BOUNDS_MACRO, RC_BOUNDS_LIST = 0, 1, 2, 3    # kf_raycast_form::bounds_path
+RC_OUT_MAPS, RC_OUT_T, RC_OUT_TA, RC_OUT_TA_SPEC = 0, 1, 2, 3          # kf_raycast_form::output
+
+
 VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("color", "<f4", (3,))])
 TRI_DTYPE = np.dtype([("v", VERTEX_DTYPE, (3,))])
 
@@ -98,7 +109,7 @@ SYMBOLS = [
     "kf_sdf_partition_begin", "kf_sdf_partition_step", "kf_sdf_partition_finish", "kf_set_defer", "kf_inject_track_stall",
     "kf_download_volume_device", "kf_upload_volume_device", "kf_resize_slab", "kf_count_layer_work", "kf_read_layer_work",
     "kf_upload_depth_mm_next", "kf_take_next_depth", "kf_cull_tail_counts", "kf_count_observed_voxels", "kf_get_fusion_counters",
-    "kf_get_fusion_form",
+    "kf_get_fusion_form", "kf_get_raycast_form",
 ]
 
 
@@ -364,6 +375,12 @@ class Context:
         tp = C.byref(Mat44.of(pose)) if pose is not None else None
         _chk(self.lib.kf_raycast_volume(self.h, int(has_color), tp, C.byref(rp), C.byref(self.cam), C.c_float(near), C.c_float(far)),
              "kf_raycast_volume")
+
+    def raycast_form(self):
+        """what the last raycast launch took (kf_get_raycast_form): a dict of the kf_raycast_form fields"""
+        f = RaycastForm()
+        _chk(self.lib.kf_get_raycast_form(self.h, C.byref(f)), "kf_get_raycast_form")
+        return {name: int(getattr(f, name)) for name, _ in RaycastForm._fields_}
 
     def raycast_slab(self, pose, inc, near, far, dev_t, dev_v, dev_n):
         rp = RaycastParams(inc)

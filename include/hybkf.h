@@ -188,6 +188,31 @@ typedef struct kf_fusion_form {
   uint32_t calls;           /* kf_integrate_volume calls that launched a fusion pass since kf_create */
 } kf_fusion_form;
 int kf_get_fusion_form(kf_ctx* ctx, kf_fusion_form* out);
+/* diagnostics: which form the last raycast launch (kf_raycast_volume and its z-slab variants) took -- host-side bookkeeping at the dispatch, no device
+ * work.  The environment switches (KF_RAYCAST_*), the volume's size and a pending kf_prefetch_frame pick the form; every form gives the same bits.
+ * Test-only switches besides those of DESIGN.md: KF_RAYCAST_BOUNDS=2 takes the super / macro list path of the tile bounds at any volume size,
+ * KF_RAYCAST_NEG_LDS=0 keeps the per-brick bits out of LDS (the march reads brick flags from global memory, as from ~570^3 up). */
+enum { KF_RC_NONE = 0, KF_RC_PLAIN = 1 /* k_raycast */, KF_RC_FILTER = 2 /* k_raycast_prefetch<fast>, the next frame's filter riding */,
+       KF_RC_BEHIND = 3 /* k_raycast_prefetch<fast>, riders behind a filter that ran in the tracking launch */ };
+enum { KF_RC_BOUNDS_NONE = 0, KF_RC_BOUNDS_MESO = 1 /* direct scan of the meso table */, KF_RC_BOUNDS_MACRO = 2 /* direct scan of the macro table */,
+       KF_RC_BOUNDS_LIST = 3 /* super cells listed, then their macro cells */ };
+enum { KF_RC_OUT_MAPS = 0 /* the model maps */, KF_RC_OUT_T = 1 /* kf_raycast_volume_slab */, KF_RC_OUT_TA = 2 /* kf_raycast_volume_slab_cross */,
+       KF_RC_OUT_TA_SPEC = 3 /* kf_raycast_volume_slab_cross_spec */ };
+typedef struct kf_raycast_form {
+  int32_t  kernel;          /* KF_RC_* */
+  int32_t  fast;            /* k_raycast_prefetch's template switch (the riders' sentinel form of the bilateral filter); 0 for k_raycast */
+  int32_t  output;          /* KF_RC_OUT_* */
+  int32_t  tile_bounds;     /* 0 / 1: rc_tile_bounds runs */
+  int32_t  bounds_path;     /* KF_RC_BOUNDS_* (KF_RC_BOUNDS_NONE without tile bounds) */
+  int32_t  meso_lds;        /* 0 / 1: the meso table is in LDS */
+  int32_t  neg_lds;         /* 0 / 1: the per-brick bits are in LDS */
+  int32_t  shared_grad;     /* RaycastArgs::shared_grad: 0 / 1 / 2 */
+  int32_t  view_half;       /* the gathers' view in brick layers to either side (0: most) */
+  int32_t  pyramid;         /* 0 / 1: levels 1 and 2 of the model maps' pyramids were written by this launch */
+  uint32_t grid;            /* workgroups of the launch (the riders' included) */
+  uint32_t calls;           /* raycast launches since kf_create */
+} kf_raycast_form;
+int kf_get_raycast_form(kf_ctx* ctx, kf_raycast_form* out);
 
 /* cudaIntegrateVolume  src/cuda/integrateVolume.cu:78-96.  transform == NULL: use the device-resident pose and
  * integrate only if the last kf_*_track call tracked (src/HybKinectfu.cpp:123-140).

@@ -31,6 +31,7 @@ def test_struct_layouts_match_reference_sizes():
     # src/AppParams.h:36-43 CameraParams 24 B; src/cuda/Mat.h Mat44 64 B; MarchingcubeData.h Triangle 72 B
     assert C.sizeof(K.CameraParams) == 24 and C.sizeof(K.Mat44) == 64 and K.TRI_DTYPE.itemsize == 72
     assert C.sizeof(K.IntegrateParams) == 8 and C.sizeof(K.RaycastParams) == 4
+    assert C.sizeof(K.RaycastForm) == 48                         # (raycast.hip: static_assert on kf_raycast_form)
 
 
 def test_argument_errors_without_gpu():
