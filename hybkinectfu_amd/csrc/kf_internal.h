@@ -91,20 +91,15 @@ struct KfTrackState {
   int   tracked;         // result of the last findCameraPose
   int   iterations;
   int   converged;       // SDF tracker: |x| < 1e-3 reached
-  unsigned arrive;       // arrival counter of the persistent ICP loop's grid barrier (monotonic within a frame)
-  unsigned rescue_tag;   // persistent ICP loop: tag_base of the last launch that timed out waiting and was finished by ONE workgroup alone (track.hip)
+  unsigned rescue_tag;   // persistent tracking loops: tag_base of the last launch that timed out waiting and was finished by ONE workgroup alone (track.hip)
   int      rescued;      // the committed verdict of the last tracking call comes from that solo finish (kf_track_result::launch_form 3)
-  unsigned pad_[1];
+  unsigned pad_[2];
   float pose_inv[16];    // pose.getInverse(), written wherever pose is committed: integrate reads it (integrateVolume.cu:84)
-  // who ends a persistent tracking launch (track.hip: k_sdf_loop): tag_base | 1 the launch's own workgroups (workgroup 0 commits, each runs its share of the
+  // who ends a persistent tracking launch (track.hip: track_loop_end): tag_base | 1 the launch's own workgroups (workgroup 0 commits, each runs its share of the
   // tail), tag_base | 2 ONE workgroup that claimed the launch after a time-out (it commits and runs every share); any other upper bits: an older launch's
   // word, i.e. open.  Set by compare-and-swap, so exactly one of the two parties ends a launch.
   unsigned commit_word;
 };
-
-// software grid barrier of the persistent ICP loop: every word on its own 128-byte line
-struct KfPaddedCounter { unsigned v; unsigned pad_[31]; };
-struct KfGridBarrier { KfPaddedCounter group[8]; KfPaddedCounter top; KfPaddedCounter gen; };
 
 struct KfCounters {
   unsigned long long n_upd;       // (unused)
@@ -205,7 +200,6 @@ struct kf_ctx {
   int last_track_form;                // kf_track_result::launch_form of the last tracking call
   KfTrackState* track;                // device
   KfCounters* counters;               // device
-  KfGridBarrier* grid_barrier;        // device
   float* scratch_mats;                // device: 8 x 16 floats for host-supplied transforms
   KfVolume vol;
   size_t n_stored_vox, n_stored_bricks;

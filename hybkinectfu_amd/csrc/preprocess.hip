@@ -105,11 +105,10 @@ __global__ void __launch_bounds__(256) k_vertices_to_normals(const float4* __res
 struct PyrMaps { const float4* in[4]; float4* l1[4]; float4* l2[4]; };
 // begin_mode >= 0: block (0,0,0) also runs the start-of-tracking bookkeeping (k_track_begin) so a frame needs no extra launch
 __global__ void __launch_bounds__(256) k_pyramid(PyrMaps m, int cols0, int rows0, int levels, int kind_base,
-                                                 KfTrackState* st, KfGridBarrier* gb, int begin_mode) {
+                                                 KfTrackState* st, int begin_mode) {
   if (begin_mode >= 0 && blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0) {
-    if (threadIdx.x < 10 && gb) reinterpret_cast<KfPaddedCounter*>(gb)[threadIdx.x].v = 0u;      // 8 groups + top + gen
     if (threadIdx.x == 0) {
-      st->status = KF_TRACK_OK; st->iterations = 0; st->converged = 0; st->arrive = 0u;
+      st->status = KF_TRACK_OK; st->iterations = 0; st->converged = 0;
       if (begin_mode == 0) st->tracked = 1;
       else {
         st->tracked = 0;
@@ -152,7 +151,7 @@ int kf_launch_pyramids(kf_ctx* c, bool model, bool vertices, bool normals) {
   int c1 = c->cols >> 1, r1 = c->rows >> 1;
   dim3 grid(kf_div_up(kf_div_up(c1, 2), 32), kf_div_up(kf_div_up(r1, 2), 8), (vertices && normals) ? 2 : 1);
   hipLaunchKernelGGL(k_pyramid, grid, dim3(256), 0, c->stream, m, c->cols, c->rows, c->levels, (model ? 2 : 0) + (vertices ? 0 : 1),
-                     (KfTrackState*)nullptr, (KfGridBarrier*)nullptr, -1);
+                     (KfTrackState*)nullptr, -1);
   return (int)hipGetLastError();
 }
 // the pyramids (ICP.cpp:57-60) that do not describe their level 0 yet -- the raycast launch leaves the model maps' behind, its riders the
@@ -165,7 +164,7 @@ int kf_launch_pyramids_and_begin(kf_ctx* c, int begin_mode) {
   const int kinds = none ? 1 : (need_new && need_model ? 4 : 2), kind_base = (!none && !need_new) ? 2 : 0;
   dim3 grid(none ? 1 : kf_div_up(kf_div_up(c1, 2), 32), none ? 1 : kf_div_up(kf_div_up(r1, 2), 8), kinds);
   hipLaunchKernelGGL(k_pyramid, grid, dim3(256), 0, c->stream, m, none ? 0 : c->cols, none ? 0 : c->rows, c->levels, kind_base,
-                     c->track, c->grid_barrier, begin_mode);
+                     c->track, begin_mode);
   c->new_pyr_ok = 1; c->model_pyr_ok = 1;
   return (int)hipGetLastError();
 }

@@ -30,14 +30,18 @@
 #define TRK_THREADS 256
 #define TRK_PX 2                   // 8x8 tiles per wave of the SDF step (grid-stride beyond that): the lookups want many waves, not long lanes
 
+// the Gauss-Newton thresholds of one tracking call, in every form the kernels use (track_thresholds)
+struct TrackThresholds {
+  float dist_thres, sin_thres, dist_shake, angle_shake;
+  float cos_shake, dist_shake2;                  // cos(angle_shake), dist_shake^2: the shake test without acos / sqrt
+  float dist_thres2, sin_thres2;                 // the correspondence gates' squares (gate_square: a negative threshold rejects everything, as `norm > t` does)
+};
 struct TrackArgs {
   const float4* new_v; const float4* new_n; const float4* model_v; const float4* model_n;
   KfCam cam;
   KfMat cur_val, linv_val;                       // host-supplied transforms (per-call wrappers only)
   int use_state;                                 // 1: transforms come from the device-resident KfTrackState
-  float dist_thres, sin_thres, dist_shake, angle_shake;
-  float cos_shake, dist_shake2;                  // cos(angle_shake), dist_shake^2: the shake test without acos / sqrt (set next to the two above)
-  float dist_thres2, sin_thres2;                 // the correspondence gates' squares (gate_square: a negative threshold rejects everything, as `norm > t` does)
+  TrackThresholds th;
   float* partials;                               // 2 x KF_ICP_MAX_WG x 32 floats, indexed by step parity
   KfTrackState* track;
   int step;                                      // index of this Gauss-Newton step within the frame (buffer parity)
@@ -440,7 +444,7 @@ __device__ __forceinline__ int apply_step(const TrackArgs& a, const float* s_tot
       const float c2 = __int_as_float(__builtin_amdgcn_readlane(csi, 2)), s2 = __int_as_float(__builtin_amdgcn_readlane(sni, 2));
       if (threadIdx.x == 0) KF_SOLVE_STAMP(1);                               // increment broadcast + sin/cos + hand-back
       float T[16];
-      const bool still = transform_from_sincos(x, c0, s0, c1, s1, c2, s2, a.dist_shake2, a.cos_shake, T);
+      const bool still = transform_from_sincos(x, c0, s0, c1, s1, c2, s2, a.th.dist_shake2, a.th.cos_shake, T);
       if (threadIdx.x == 0) vs[16] = still ? 0.f : 1.f;
       if (still && threadIdx.x < 16) {
         // ICP.cpp:81 cur = T * cur; T's last row is (0, 0, 0, 1): that row of the product is cur's own last row, bit for bit
@@ -471,7 +475,7 @@ __device__ __forceinline__ int apply_step(const TrackArgs& a, const float* s_tot
     unpack27(s_tot, A, b);
     int code = STEP_APPLIED;
     llt_solve6(A, b, x);
-    if (!vector6_to_transform(x, a.dist_shake2, a.cos_shake, T)) code = STEP_LOST_SHAKE;
+    if (!vector6_to_transform(x, a.th.dist_shake2, a.th.cos_shake, T)) code = STEP_LOST_SHAKE;
     else {
       const float nx = sqrtf(x[0] * x[0] + x[1] * x[1] + x[2] * x[2] + x[3] * x[3] + x[4] * x[4] + x[5] * x[5]);
       if (nx < 0.001f) code = STEP_CONVERGED;                              // SDF.cpp:87-90: stop before applying x
@@ -552,7 +556,7 @@ __device__ __forceinline__ bool icp_finish(const TrackArgs& a, float4 vg, float4
   if (kf_is_zero4(nt)) return false;
   // `norm(p - q) > dist || norm(n_tgt x n_in) > sin` (CalPointToPlaneErrSolverParams.cu:52) on the squares: two square roots fewer per pixel
   const float3 dv = kf3(vt.x - vg.x, vt.y - vg.y, vt.z - vg.z), cr = kf_cross(kf3(nt.x, nt.y, nt.z), kf3(ng.x, ng.y, ng.z));
-  if (kf_dot(dv, dv) > a.dist_thres2 || kf_dot(cr, cr) > a.sin_thres2) return false;
+  if (kf_dot(dv, dv) > a.th.dist_thres2 || kf_dot(cr, cr) > a.th.sin_thres2) return false;
   const float3 p = kf3(vt.x, vt.y, vt.z), q = kf3(vg.x, vg.y, vg.z), n = kf3(nt.x, nt.y, nt.z);
   row[0] = q.y * n.z - q.z * n.y; row[1] = q.z * n.x - q.x * n.z; row[2] = q.x * n.y - q.y * n.x;
   row[3] = n.x; row[4] = n.y; row[5] = n.z;
@@ -677,36 +681,39 @@ __global__ void __launch_bounds__(ICP_THREADS) k_icp_step(TrackArgs a) {
 // A step then costs one store->load propagation (~1 us) instead of a dependent dispatch (~5 us measured here) plus a cold
 // start of the 30 KB straight-line step code, which is what bounded the one-launch-per-step form at ~22 us per step; the
 // two-level counter barrier this replaces cost three dependent atomic round trips (~4 us) per step.
-struct IcpLoopArgs {
+// What every persistent tracking launch (k_icp_loop, k_icp_loop_batched, k_sdf_loop) needs to exchange its partial sums and to end (track_loop_end)
+struct TrackLoopArgs {
+  unsigned long long* slots;                     // KF_ICP_LOOP_STEPS x KF_ICP_LOOP_MAX_WG x 32 tagged partial sums, one array per step
+  unsigned tag_base;                             // this launch's sequence number (host counter x 64); tag = tag_base + step
+  KfTrackState* track;
+  unsigned* stall_word;                          // pinned host word: set when the loop gives up waiting, polled by the next tracking call
+  int n_loop;                                    // the loop's workgroups = the publishers of a step
+  int play_dead;                                 // fault injection (kf_inject_track_stall): this workgroup exits at once, as if it had never become resident
+  int exp_mode;                                  // diagnostics only (KF_ICP_EXP): 1 = skip the solve (timing), 7 = shader-clock stamps per phase
+  // The fusion pass's brick cull as the TAIL of this launch (cull.h): it needs nothing but the committed pose, which every workgroup of the loop holds
+  // once the last step is applied -- so k_integrate_cull and one kernel boundary leave the stream (k_icp_loop and k_sdf_loop; the host arms it when the
+  // previous kf_integrate_volume left its parameters behind and the volume is small enough: kf_arm_tail_cull).
+  int cull_on;
+  IntegrateArgs cull;
+};
+struct IcpLoopArgs : TrackLoopArgs {
   const float4* new_v[KF_MAX_LEVELS]; const float4* new_n[KF_MAX_LEVELS];
   const float4* model_v[KF_MAX_LEVELS]; const float4* model_n[KF_MAX_LEVELS];
   KfCam cam[KF_MAX_LEVELS];
   int iters[KF_MAX_LEVELS]; int levels;
-  float dist_thres, sin_thres, dist_shake, angle_shake, cos_shake, dist_shake2, dist_thres2, sin_thres2;
-  unsigned long long* slots;                     // KF_ICP_LOOP_STEPS x KF_ICP_LOOP_MAX_WG x 32 tagged partial sums, one array per step
-  unsigned tag_base;                             // this launch's sequence number (host counter x 64); tag = tag_base + step
-  KfTrackState* track;
-  unsigned* stall_word;                          // pinned host word: set when the loop gives up waiting, polled by the next kf_icp_track
-  int exp_mode;                                  // diagnostics only (KF_ICP_EXP): 1 = skip the solve (timing), 7 = shader-clock stamps per phase
-  int play_dead;                                 // fault injection (kf_inject_track_stall): this workgroup exits at once, as if it had never become resident
+  TrackThresholds th;
   // Riders: workgroups [n_loop, gridDim.x) do not take part in the loop -- they carry the NEXT frame's u16 -> f32 + gate + bilateral filter
   // (kf_prefetch_frame, requested before kf_icp_track).  The loop keeps one workgroup on each of ~200 CUs busy for ~0.14 ms at two waves per
   // SIMD and leaves the other CUs idle; the riders are dispatched behind the loop's workgroups (they cannot displace them), wait for
   // nobody, and are long done when the loop ends.  gridDim.x == n_loop: none.
-  int n_loop;
   int n_virtual;                                 // workgroups the pixel dealing is defined for (= the workgroups level 0 needs at ICP_PX pixels per lane, what the per-step form
                                                  // launches): n_loop in k_icp_loop; larger in k_icp_loop_batched, whose n_loop resident workgroups each play several of them
   KfBilateralArgs bil; int bil_gx, bil_tiles, bil_fast;
-  // The fusion pass's brick cull as the TAIL of this launch (cull.h): it needs nothing but the committed pose, which every workgroup of the loop holds
-  // once the last step is applied -- so k_integrate_cull and one kernel boundary leave the stream (k_icp_loop only; the host arms it when the previous
-  // kf_integrate_volume left its parameters behind and the volume is small enough: kf_icp_track).
-  int cull_on;
-  IntegrateArgs cull;
 };
 
 // A workgroup gives up waiting for the others' partial sums after ICP_WAIT_LIMIT ticks of the 100 MHz wall clock (s_memrealtime) = 20 ms -- a
 // legitimate wait is tens of microseconds; the clock is read every 64th poll (~1-1.5 us each).  Giving up costs latency, not the frame: one
-// workgroup then finishes the frame's Gauss-Newton loop alone (icp_solo_finish below), with the same bits.
+// workgroup then finishes the frame's Gauss-Newton loop alone (track_loop_end below), with the same bits.
 #define ICP_WAIT_LIMIT 2000000ull
 #define ICP_FOLD_BATCH 13
 #ifndef KF_ICP_POLL_PIPE
@@ -797,88 +804,16 @@ __device__ __forceinline__ void fold_partials_tagged(const unsigned long long* s
 }
 
 
-// ---- a loop that timed out is finished by ONE workgroup ---------------------------------------------------------------------------------
-// The loop's workgroups wait for each other, so they must all be resident; when some are not (a foreign process holds CUs -- the cross-process
-// registry of ctx.hip only sees processes of this library) a fold times out.  The frame is NOT given up: the first workgroup to time out claims
-// the launch (rescue_tag), everybody else leaves (workgroups dispatched later see the claim and leave at once), and the claimant runs the whole
-// Gauss-Newton loop of this frame again by itself, playing every workgroup of the launch in turn: the same pixel dealing (icp_dealt_pixel_of),
-// the same pixel phase (icp_accumulate), the same workgroup reduction (icp_wg_reduce), its partial sums published into the same tagged slots and
-// folded by the same fold -- hence the SAME BITS as the loop or the per-step form would have produced (tests/test_gpu_track_forms.py injects the
-// fault).  It costs milliseconds (one CU walks all pixels 19 times), not the frame; the host backs off to per-step launches afterwards.
-// Not inlined: the hot kernel's register allocation stays what it was.
-__device__ __forceinline__ void icp_solo_finish(const IcpLoopArgs& L, float (*s_pose)[16], float* s_linv, float* s_wave, float* s_tot, int* s_abort) {
-  KfTrackState* st = L.track;
-  int cur_buf = 0;
-  float* s_cur = s_pose[0];
-  if (threadIdx.x < 16) s_cur[threadIdx.x] = st->pose[threadIdx.x];            // from the committed pose again (ICP.cpp:62): nothing of the attempt is kept
-  if (threadIdx.x == 0) *s_abort = 0;
-  __syncthreads();
-  if (threadIdx.x == 0) kf_mat44_inverse(s_cur, s_linv);
-  __syncthreads();
-  TrackArgs a;
-  a.dist_thres = L.dist_thres; a.sin_thres = L.sin_thres; a.dist_shake = L.dist_shake; a.angle_shake = L.angle_shake; a.cos_shake = L.cos_shake; a.dist_shake2 = L.dist_shake2;
-  a.dist_thres2 = L.dist_thres2; a.sin_thres2 = L.sin_thres2; a.sdf = 0;
-#ifdef KF_EXPERIMENTS
-  a.dbg = nullptr; a.exp_nodet = false;
-#endif
-  int step = 0, n_prev = 0, applied = 0, code = STEP_APPLIED;
-  for (int l = L.levels - 1; l >= 0 && code == STEP_APPLIED; --l) {
-    a.cam = L.cam[l];
-    const float4* __restrict__ new_v = L.new_v[l]; const float4* __restrict__ new_n = L.new_n[l];
-    const int npx = a.cam.cols * a.cam.rows;
-    int px_l, grid_l;
-    icp_level_geometry(npx, L.n_virtual, l, px_l, grid_l);
-    for (int it = 0; it < L.iters[l]; ++it, ++step) {
-      if (step > 0) {
-        fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, L.tag_base + (unsigned)(step - 1), s_tot, s_abort);
-        code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-        if (code != STEP_APPLIED) break;
-        cur_buf ^= 1; s_cur = s_pose[cur_buf];
-        ++applied;
-      }
-      const int n_pub = grid_l < L.n_loop ? grid_l : L.n_loop;                 // publishers: the launch's workgroups (k_icp_loop: one per workgroup of the dealing)
-      for (int g = 0; g < n_pub; ++g) {                                        // every workgroup of the launch, one after the other
-        float gsum = 0.f;
-        for (int w = g; w < grid_l; w += L.n_loop) {                           // ... each with the workgroups of the dealing it plays (k_icp_loop_batched), summed in its order
-          float4 iv[ICP_PX], in_[ICP_PX];
-#pragma unroll
-          for (int j = 0; j < ICP_PX; ++j) {
-            const int i = icp_dealt_pixel_of(j, grid_l, w);
-            iv[j] = make_float4(0.f, 0.f, 0.f, 0.f); in_[j] = iv[j];
-            if (j < px_l && i < npx) { iv[j] = new_v[i]; in_[j] = new_n[i]; }
-          }
-          float acc[27];
-#pragma unroll
-          for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-          icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
-          int k; float sw;
-          const bool holder = icp_wg_reduce(acc, s_wave, k, sw);
-          if (holder) gsum = (w == g) ? sw : gsum + sw;
-          __syncthreads();                                                     // s_wave is reused by the next turn
-          if (holder && w + L.n_loop >= grid_l)
-            __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + g * 32 + k,
-                               ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(gsum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-      }
-      n_prev = n_pub;
-    }
-  }
-  if (code == STEP_APPLIED) {                                                  // the last step's system, then commit _pose (ICP.cpp:84)
-    fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, L.tag_base + (unsigned)(step - 1), s_tot, s_abort);
-    code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-    if (code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; }
-    if (threadIdx.x < 27) st->reduced[threadIdx.x] = s_tot[threadIdx.x];
-  }
-  if (code != STEP_APPLIED) { if (threadIdx.x == 0) { st->status = code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 1; } return; }
-  if (threadIdx.x < 16) st->pose[threadIdx.x] = s_cur[threadIdx.x];
-  if (threadIdx.x == 0) { st->status = KF_TRACK_OK; st->tracked = 1; st->iterations = applied + 1; st->converged = 0; st->rescued = 1; }
-  __shared__ float s_tinv[16];
-  __shared__ unsigned s_cull[17];
-  if (threadIdx.x == 64) kf_mat44_inverse(s_cur, s_tinv);
-  __syncthreads();
-  if (threadIdx.x < 16) st->pose_inv[threadIdx.x] = s_tinv[threadIdx.x];
-  if (L.cull_on)                                                               // the launch's tail (cull.h), every workgroup's share in turn: nobody else is left
-    for (int w = 0; w < L.n_loop; ++w) cull_tail(L.cull, s_tinv, w, L.n_loop, s_cull);
+// ---- the end of a persistent tracking launch -------------------------------------------------------------------------------------------------
+// How a persistent loop left its Gauss-Newton steps: at fold `fold` (of `n_pub` publishers) with its update's `code` -- STEP_PENDING: that fold is still
+// to be done and applied -- or timed out waiting in that fold.  `applied`: the updates applied so far.
+enum { STEP_PENDING = -1 };
+struct LoopOutcome { int code, fold, n_pub, applied; bool timed_out; };
+enum { LOOP_DONE = 0, LOOP_SOLO = 1 };
+
+// the whole verdict of a tracking call (a persistent launch may have run without k_track_begin's reset).  One lane calls.
+__device__ __forceinline__ void track_verdict(KfTrackState* st, int status, int iterations, int converged, int rescued) {
+  st->status = status; st->tracked = status == KF_TRACK_OK ? 1 : 0; st->iterations = iterations; st->converged = converged; st->rescued = rescued;
 }
 // Who ends a persistent tracking launch?  One compare-and-swap on KfTrackState::commit_word decides for every workgroup: (tag_base | 1) the launch's own
 // workgroups, (tag_base | 2) ONE workgroup that finishes it alone after a time-out.  `want`: 1 or 2; `seen0`: the word as this workgroup read it when it
@@ -893,26 +828,74 @@ __device__ __forceinline__ unsigned track_commit_decide(KfTrackState* st, unsign
     expect = seen;                                                          // (an older word replaced by this launch's)
   }
 }
-// a fold of the loop timed out (uniform: every lane of the workgroup is here): claim the launch or leave
-// s_abort on exit of the decision: 2 this workgroup finishes the frame alone; 1 somebody else does (leave); 3 the launch's own workgroups are ending it -- only
-// possible when the time-out hit the LAST fold (a workgroup that passed it proves every partial sum of every step published, this one's included): retry that fold
-#define ICP_DECIDE_ABORT() do { \
-    if (threadIdx.x == 0) { \
-      bool mine_; \
-      const unsigned who_ = track_commit_decide(st, L.tag_base, 2u, commit_seen0, &mine_); \
-      if (who_ == 2u && mine_) { \
-        __hip_atomic_store(&st->rescue_tag, L.tag_base, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);      /* whoever still polls leaves */ \
-        __hip_atomic_store(L.stall_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM); \
-        s_abort = 2; \
-      } else s_abort = who_ == 2u ? 1 : 3; \
-    } \
-    __syncthreads(); \
-  } while (0)
-#ifdef KF_ICP_NO_SOLO          /* A/B variant only (tools/build_variant.sh): what the solo path costs the hot loop in registers / code placement */
-#define ICP_SOLO_CALL do { if (threadIdx.x == 0) { st->status = KF_TRACK_STALLED; st->tracked = 0; } } while (0)
-#else
-#define ICP_SOLO_CALL icp_solo_finish(L, s_pose, s_linv, s_wave, s_tot, &s_abort)
-#endif
+// The loop's workgroups wait for each other, so they must all be resident; when some are not (a foreign process holds CUs -- the cross-process
+// registry of ctx.hip only sees processes of this library) a fold times out.  The frame is NOT given up.  Every workgroup of a persistent launch
+// (k_icp_loop, k_icp_loop_batched, k_sdf_loop) ends here, with its loop's outcome:
+//  * the loop went through: track_commit_decide settles the party.  The launch's own workgroups: workgroup 0 commits (SDF.cpp:103, ICP.cpp:84; a
+//    lost frame keeps the old pose) and every workgroup runs its own share of the tail.  A workgroup that claimed the launch: this one leaves.
+//  * a fold timed out: the first workgroup to claim the launch raises rescue_tag (whoever still polls leaves) and the stall word, and gets LOOP_SOLO:
+//    the caller runs the frame's whole loop again by itself, playing every publisher of the launch in turn -- the same pixel dealing, pixel phase,
+//    reduction, tagged slots and fold, hence the SAME BITS as the loop (tests/test_gpu_track_forms.py injects the fault) -- and comes back with
+//    `solo`: it commits and runs every share of the tail.  It costs milliseconds, not the frame; the host backs off to per-step launches afterwards.
+//    Somebody else's claim: leave.  The launch's own workgroups ended it after all: the fold that timed out is then the launch's last executed one
+//    (a workgroup that passed it proves every partial sum of it published), so it is folded again and applied to the transform this workgroup holds
+//    -- the step the others took -- and the workgroup ends with them: the verdict if it is workgroup 0, its own share of the tail.
+// `apply`: the tracker's update from s_tot (STEP_*, behind a workgroup barrier), leaving the running transform in *s_cur; s_tinv: 16 floats of LDS the loop
+// no longer needs (the committed pose's inverse goes there).  Every lane calls.
+template <class Apply>
+__device__ __forceinline__ int track_loop_end(const TrackLoopArgs& L, unsigned commit_seen0, bool solo, LoopOutcome o, float* s_tot, int* s_abort,
+                                              float* const& s_cur, Apply& apply, float* s_tinv) {
+  KfTrackState* st = L.track;
+  __shared__ unsigned s_who;                                                   // 1 the launch's own workgroups end it, 2 a claimant, 3 this workgroup claimed it
+  __shared__ unsigned s_cull[17];
+  for (;;) {
+    if (o.code == STEP_PENDING) {
+      fold_partials_tagged(L.slots + (size_t)o.fold * KF_ICP_LOOP_MAX_WG * 32, o.n_pub, L.tag_base + (unsigned)o.fold, s_tot, s_abort, 0,
+                           solo ? nullptr : &st->rescue_tag, L.tag_base);
+      o.timed_out = *s_abort != 0;
+    }
+    // a lane of an idle wave settles it, while wave 0 solves a pending step; s_who is read behind the next workgroup barrier
+    if (!solo && threadIdx.x == 128) {
+      bool mine;
+      unsigned who = track_commit_decide(st, L.tag_base, o.timed_out ? 2u : 1u, commit_seen0, &mine);
+      if (o.timed_out && who == 2u && mine) {
+        __hip_atomic_store(&st->rescue_tag, L.tag_base, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(L.stall_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        who = 3u;
+      }
+      s_who = who;
+    }
+    if (!o.timed_out) break;
+    __syncthreads();
+    if (solo) {                                                                // (a solo fold waits for nobody: unreachable)
+      if (threadIdx.x == 0) track_verdict(st, KF_TRACK_STALLED, o.applied, 0, 1);
+      return LOOP_DONE;
+    }
+    if (s_who != 1u) return s_who == 3u ? LOOP_SOLO : LOOP_DONE;
+    __syncthreads();
+    if (threadIdx.x == 0) *s_abort = 0;                                        // every sum of the fold is published: it cannot wait again
+    o.code = STEP_PENDING; o.timed_out = false;
+  }
+  if (o.code == STEP_PENDING) { o.code = apply(); if (o.code == STEP_APPLIED) ++o.applied; }
+  else __syncthreads();
+  if (!solo && s_who == 2u) return LOOP_DONE;                                  // a workgroup claimed the launch: it commits and runs every share of the tail
+  const bool good = o.code == STEP_APPLIED || o.code == STEP_CONVERGED;        // (uniform over the launch: every workgroup arrives at the same verdict)
+  const bool writer = solo || blockIdx.x == 0, tail = L.cull_on && good;
+  if (writer) {
+    if (threadIdx.x < 27 && KF_EXP_MODE(L) != 7) st->reduced[threadIdx.x] = s_tot[threadIdx.x];
+    if (good && threadIdx.x < 16) st->pose[threadIdx.x] = s_cur[threadIdx.x];
+    if (threadIdx.x == 0) track_verdict(st, good ? KF_TRACK_OK : o.code, o.applied, o.code == STEP_CONVERGED ? 1 : 0, solo ? 1 : 0);
+  }
+  if (!good || (!writer && !tail)) return LOOP_DONE;
+  if (threadIdx.x == 64) kf_mat44_inverse(s_cur, s_tinv);                      // a lane of another wave: world -> camera (integrateVolume.cu:84), for the fusion pass and the tail
+  __syncthreads();
+  if (writer && threadIdx.x < 16) st->pose_inv[threadIdx.x] = s_tinv[threadIdx.x];
+  if (tail) {                                                                  // every workgroup holds the same pose bits, hence the same inverse
+    if (solo) { for (int w = 0; w < L.n_loop; ++w) cull_tail(L.cull, s_tinv, w, L.n_loop, s_cull); }
+    else cull_tail(L.cull, s_tinv, (int)blockIdx.x, L.n_loop, s_cull);
+  }
+  return LOOP_DONE;
+}
 
 // a rider workgroup of a tracking launch: two 64x4 tiles of the NEXT frame's gate + bilateral filter (IcpLoopArgs::bil)
 __device__ __forceinline__ void icp_rider(const IcpLoopArgs& L) {
@@ -924,292 +907,219 @@ __device__ __forceinline__ void icp_rider(const IcpLoopArgs& L) {
   else kf_bilateral_tile<4, false>(L.bil, tt % L.bil_gx, tt / L.bil_gx, (int)(threadIdx.x & 255), tile);
 }
 
-__global__ void __launch_bounds__(ICP_THREADS) k_icp_loop(IcpLoopArgs L) {
+// this lane's pixels of workgroup w of a level's dealing (zeros where w holds no pixels, beyond px_l and beyond the image)
+__device__ __forceinline__ void icp_load_pixels(const float4* __restrict__ new_v, const float4* __restrict__ new_n, int w, int grid_l, int px_l, int npx,
+                                                float4 iv[ICP_PX], float4 in_[ICP_PX]) {
+#pragma unroll
+  for (int j = 0; j < ICP_PX; ++j) {
+    const int i = icp_dealt_pixel_of(j, grid_l, w);
+    iv[j] = make_float4(0.f, 0.f, 0.f, 0.f); in_[j] = iv[j];
+    if (w < grid_l && j < px_l && i < npx) { iv[j] = new_v[i]; in_[j] = new_n[i]; }
+  }
+}
+// One publisher's share of a Gauss-Newton step of level l: publisher g plays the workgroups g, g + n_loop, ... of the dealing in turn -- each turn exactly a
+// workgroup's pixel phase and reduction in the per-step form's dealing -- adds their sums up HERE, in that order, and publishes them as ONE set of 27 tagged
+// words: a step's fold then walks n_loop x 27 words (205 at 1280x960), not grid_l x 27 (800).  The per-step form folds its partials in the same groups
+// (fold_partials, TrackArgs::fold_group): the same bits.  ivn / inn: the first turn's pixels, requested by the caller; every later turn's are requested one
+// turn ahead (a turn's own loads, ~1 us from L2 / the Infinity Cache, would otherwise be exposed three or four times per step).
+__device__ __forceinline__ void icp_publish(const IcpLoopArgs& L, const TrackArgs& a, int l, int step, int g, int grid_l, int px_l,
+                                            const float* s_cur, const float* s_linv, float* s_wave, float4 ivn[ICP_PX], float4 inn[ICP_PX]) {
+  const int npx = a.cam.cols * a.cam.rows;
+  float gsum = 0.f;
+  for (int w = g; w < grid_l; w += L.n_loop) {
+    float4 iv[ICP_PX], in_[ICP_PX];
+#pragma unroll
+    for (int j = 0; j < ICP_PX; ++j) { iv[j] = ivn[j]; in_[j] = inn[j]; }
+    if (w + L.n_loop < grid_l) icp_load_pixels(L.new_v[l], L.new_n[l], w + L.n_loop, grid_l, px_l, npx, ivn, inn);
+    float acc[27];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) acc[k] = 0.f;
+    icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
+    int k; float sw;
+    const bool holder = icp_wg_reduce(acc, s_wave, k, sw);
+    if (holder) gsum = (w == g) ? sw : gsum + sw;
+    __syncthreads();                                                           // s_wave is reused by the next turn
+    if (holder && w + L.n_loop >= grid_l)                                      // the last turn: publish
+      __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + g * 32 + k,
+                         ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(gsum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// The Gauss-Newton steps of a persistent ICP launch, coarse -> fine (ICP.cpp:65), up to the last step's fold -- or an earlier verdict, or a fold that timed out.
+// BATCHED (k_icp_loop_batched, the solo finish): every step plays this workgroup's publisher (icp_publish) -- or every publisher in turn, `solo`.  A lane's
+// pixels cannot stay in registers across steps (several turns share them): they are re-read every step, from L2 / the Infinity Cache (78 MB per step at
+// 1280x960 fit the 256 MiB cache).  Otherwise (k_icp_loop) every workgroup is one workgroup of the dealing, and its pixels stay in registers for all the
+// iterations of a level.  `apply` (track_loop_end) flips the running transform s_pose[cur_buf] between the two buffers.
+template <bool BATCHED, class Apply>
+__device__ __forceinline__ LoopOutcome icp_loop_steps(const IcpLoopArgs& L, TrackArgs& a, bool solo, Apply& apply, float (*s_pose)[16], int& cur_buf,
+                                                      float*& s_cur, const float* s_linv, float* s_wave, float* s_tot, int* s_abort) {
+  KfTrackState* st = L.track;
+  LoopOutcome o = {STEP_APPLIED, 0, 0, 0, false};
+  int step = 0;
+  // diagnostic build path (KF_ICP_EXP=7): workgroup 0 accumulates shader-clock ticks per segment into track->reduced
+  const bool stamp = !BATCHED && KF_EXP_MODE(L) == 7 && blockIdx.x == 0 && threadIdx.x == 0;
+  unsigned long long t_last = 0; float seg[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#define KF_STAMP(i) do { if (stamp) { unsigned long long t_now = __builtin_amdgcn_s_memtime(); seg[i] += (float)(t_now - t_last); t_last = t_now; } } while (0)
+  if (stamp) t_last = __builtin_amdgcn_s_memtime();
+  for (int l = L.levels - 1; l >= 0; --l) {
+    a.cam = L.cam[l];
+    const int npx = a.cam.cols * a.cam.rows;
+    int px_l, grid_l;
+    icp_level_geometry(npx, L.n_virtual, l, px_l, grid_l);
+    const int g0 = solo ? 0 : (int)blockIdx.x;                                 // this workgroup's (first) publisher
+    float4 iv[ICP_PX], in_[ICP_PX];
+    // this lane's own vertices / normals depend neither on the running transform nor on the iteration: they are loaded once per pyramid level and stay in
+    // registers for all of its iterations (the reference re-reads them 4 / 5 / 10 times).  (A conditional load on purpose: the branch-free form that helps
+    // the per-step gathers in icp_accumulate costs 21 us per frame here -- measured, profiles/r03_icp_step.txt -- and these loads happen once per level.)
+    if constexpr (!BATCHED) icp_load_pixels(L.new_v[l], L.new_n[l], g0, grid_l, px_l, npx, iv, in_);
+    for (int it = 0; it < L.iters[l]; ++it, ++step) {
+      KF_STAMP(0);
+      // batched: this step's first turn's pixels are requested before the previous step's sums are waited for (they depend on the level only)
+      if constexpr (BATCHED) icp_load_pixels(L.new_v[l], L.new_n[l], g0, grid_l, px_l, npx, iv, in_);
+      if (step > 0) {
+        o.fold = step - 1;
+#ifdef KF_EXPERIMENTS
+        if (!BATCHED && KF_EXP_MODE(L) == 14) {
+          // experiment (VERDICT r3 #3b, "leader fold"): workgroup 0 alone folds and solves; everybody else polls ONE line -- the new transform as 16
+          // tagged words (+ the verdict) -- instead of folding the 200 x 27 partial sums itself.  Same bits; timing: profiles/r04_icp_exchange.txt
+          unsigned long long* bc = L.slots + (size_t)28 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)(step - 1) * 32;
+          const unsigned tag = L.tag_base + (unsigned)(step - 1);
+          __shared__ int s_bc_code;
+          if (blockIdx.x == 0) {
+            fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, o.n_pub, tag, s_tot, s_abort);
+            o.code = apply();
+            if (threadIdx.x < 17) {
+              const unsigned bits = threadIdx.x < 16 ? __float_as_uint(s_cur[threadIdx.x]) : (unsigned)o.code;
+              __hip_atomic_store(bc + threadIdx.x, ((unsigned long long)tag << 32) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+          } else {
+            if (threadIdx.x < 17) {
+              unsigned long long u;
+              do { u = __hip_atomic_load(bc + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if ((unsigned)(u >> 32) != tag) __builtin_amdgcn_s_sleep(1); } while ((unsigned)(u >> 32) != tag);
+              if (threadIdx.x < 16) s_pose[cur_buf ^ 1][threadIdx.x] = __uint_as_float((unsigned)u); else s_bc_code = (int)(unsigned)u;
+            }
+            __syncthreads();
+            o.code = s_bc_code;
+            if (o.code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; }
+          }
+          __syncthreads();
+        } else
+#endif
+        {
+          fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, (KF_EXP_MODE(L) == 2 && o.n_pub > 16) ? 16 : o.n_pub, L.tag_base + (unsigned)(step - 1),
+                               s_tot, s_abort, KF_EXP_MODE(L), solo ? nullptr : &st->rescue_tag, L.tag_base);
+          if (*s_abort) { o.timed_out = true; return o; }
+          KF_STAMP(1);
+#ifdef KF_EXPERIMENTS
+          if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)     // per-wave: fold of the previous step done
+            L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + 16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
+          if (KF_EXP_MODE(L) == 8 && threadIdx.x == 0) L.slots[(size_t)24 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)(step - 1) * 1024 + blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime();
+#endif
+          if (KF_EXP_MODE(L) == 1) { o.code = STEP_APPLIED; __syncthreads(); }    // timing only: skip the 6x6 solve
+          else o.code = apply();
+        }
+        if (o.code != STEP_APPLIED) return o;                                  // same verdict in every workgroup
+        ++o.applied;
+      }
+      KF_STAMP(2);
+      if constexpr (BATCHED) {
+        const int g1 = solo ? (grid_l < L.n_loop ? grid_l : L.n_loop) : g0 + 1;
+        for (int g = g0; g < g1; ++g) {
+          if (g > g0) icp_load_pixels(L.new_v[l], L.new_n[l], g, grid_l, px_l, npx, iv, in_);
+          icp_publish(L, a, l, step, g, grid_l, px_l, s_cur, s_linv, s_wave, iv, in_);
+        }
+        o.n_pub = grid_l < L.n_loop ? grid_l : L.n_loop;
+      } else {
+        if ((int)blockIdx.x < grid_l) {
+          float acc[27];
+#pragma unroll
+          for (int k = 0; k < 27; ++k) acc[k] = 0.f;
+          icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
+          KF_STAMP(3);
+#ifdef KF_EXPERIMENTS
+          if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)     // per-wave: pixel phase done (workgroup 5)
+            L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
+#endif
+          // workgroup partial, stored write-through (sc1) for the other CUs
+          int k; float sw;
+          if (icp_wg_reduce(acc, s_wave, k, sw))
+            __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + blockIdx.x * 32 + k,
+                               ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(sw),
+                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        KF_STAMP(4);
+        KF_STAMP(5);
+#ifdef KF_EXPERIMENTS
+        if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)       // per-wave: partial published / wave idle again
+          L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + 8 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
+        if (KF_EXP_MODE(L) == 8 && threadIdx.x == 0) L.slots[(size_t)24 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 1024 + blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
+#endif
+        o.n_pub = grid_l;
+      }
+    }
+  }
+#undef KF_STAMP
+  if (stamp) { for (int i = 0; i < 6; ++i) st->reduced[20 + i] = seg[i]; }
+  o.code = STEP_PENDING; o.fold = step - 1;                                   // the last step's system: folded and applied by track_loop_end
+  return o;
+}
+
+// Both persistent ICP kernels: the loop, then track_loop_end -- and after a time-out that this workgroup claimed, the frame's whole loop again by itself,
+// from the committed pose (which nobody else can have changed since the kernel started: the claim excludes every other committer).
+template <bool BATCHED>
+__device__ __forceinline__ void icp_loop(const IcpLoopArgs& L) {
   if ((int)blockIdx.x >= L.n_loop) { icp_rider(L); return; }                   // a rider: two 64x4 filter tiles (bilateral_tile.h), then done
   __shared__ float s_pose[2][16], s_linv[16];                                  // the running transform lives in one of two buffers: a step writes the other one
   __shared__ float s_wave[27 * (ICP_THREADS / 16)], s_tot[(ICP_THREADS / 32) * 32];
   __shared__ int s_abort;
-  int s_code = STEP_APPLIED, cur_buf = 0;
+  int cur_buf = 0;
   float* s_cur = s_pose[0];
   KfTrackState* st = L.track;
-  // a workgroup that only becomes resident after the launch has been given up (icp_solo_finish above) has nothing to do; `play_dead`: fault
-  // injection (kf_inject_track_stall) -- the last workgroup behaves as if it never became resident
-  // (the pose and the claim word are requested together: one round trip)
-  const float pose_e = st->pose[threadIdx.x & 15];                             // ICP.cpp:62 cur_transform = _pose
-  const unsigned commit_seen0 = __hip_atomic_load(&st->commit_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // (requested with the pose and the claim word: one round trip)
-  if (__hip_atomic_load(&st->rescue_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == L.tag_base) return;
-  if (L.play_dead && (int)blockIdx.x == L.n_loop - 1) return;
-  if (threadIdx.x < 16) s_cur[threadIdx.x] = pose_e;
-  if (threadIdx.x == 0) s_abort = 0;
-  __syncthreads();
-  if (threadIdx.x == 0) kf_mat44_inverse(s_cur, s_linv);                        // ICP.cpp:63 last_transform_inv
-  __syncthreads();
-  TrackArgs a;
-  a.dist_thres = L.dist_thres; a.sin_thres = L.sin_thres; a.dist_shake = L.dist_shake; a.angle_shake = L.angle_shake; a.cos_shake = L.cos_shake; a.dist_shake2 = L.dist_shake2;
-  a.dist_thres2 = L.dist_thres2; a.sin_thres2 = L.sin_thres2; a.sdf = 0;
-#ifdef KF_EXPERIMENTS
-  a.dbg = (KF_EXP_MODE(L) == 11 && blockIdx.x == 0) ? L.slots + (size_t)26 * KF_ICP_LOOP_MAX_WG * 32 : nullptr;
-  a.exp_nodet = KF_EXP_MODE(L) == 12;
-#endif
-  int step = 0, n_prev = 0, applied = 0;
-  bool timed_out = false;                        // a fold gave up waiting: leave both loops, see ICP_ON_ABORT (one copy of the solo finish)
-  // diagnostic build path (KF_ICP_EXP=7): workgroup 0 accumulates shader-clock ticks per segment into track->reduced
-  const bool stamp = KF_EXP_MODE(L) == 7 && blockIdx.x == 0 && threadIdx.x == 0;
-  unsigned long long t_last = 0; float seg[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#define KF_STAMP(i) do { if (stamp) { unsigned long long t_now = __builtin_amdgcn_s_memtime(); seg[i] += (float)(t_now - t_last); t_last = t_now; } } while (0)
-  if (stamp) t_last = __builtin_amdgcn_s_memtime();
-  for (int l = L.levels - 1; l >= 0; --l) {                                      // coarse -> fine, ICP.cpp:65
-    a.cam = L.cam[l];
-    const float4* __restrict__ new_v = L.new_v[l]; const float4* __restrict__ new_n = L.new_n[l];
-    const float4* __restrict__ model_v = L.model_v[l]; const float4* __restrict__ model_n = L.model_n[l];
-    const int npx = a.cam.cols * a.cam.rows;
-    int px_l, grid_l;
-    icp_level_geometry(npx, L.n_virtual, l, px_l, grid_l);
-    const bool has_px = (int)blockIdx.x < grid_l;
-    // this lane's own vertices / normals depend neither on the running transform nor on the iteration: they are loaded once
-    // per pyramid level and stay in registers for all of its iterations (the reference re-reads them 4 / 5 / 10 times)
-    float4 iv[ICP_PX], in_[ICP_PX];
-#pragma unroll
-    for (int j = 0; j < ICP_PX; ++j) {
-      const int i = icp_dealt_pixel(j, grid_l);
-      // (a conditional load on purpose: the branch-free form that helps the per-step gathers in icp_accumulate costs 21 us per frame
-      // here -- measured, profiles/r03_icp_step.txt -- and these loads happen once per pyramid level, not once per step)
-      iv[j] = make_float4(0.f, 0.f, 0.f, 0.f); in_[j] = iv[j];
-      if (has_px && j < px_l && i < npx) { iv[j] = new_v[i]; in_[j] = new_n[i]; }
-    }
-    for (int it = 0; it < L.iters[l]; ++it, ++step) {
-      KF_STAMP(0);
-#ifdef KF_EXPERIMENTS
-      if (step > 0 && KF_EXP_MODE(L) == 14) {
-        // experiment (VERDICT r3 #3b, "leader fold"): workgroup 0 alone folds and solves; everybody else polls ONE line -- the new transform as 16
-        // tagged words (+ the verdict) -- instead of folding the 200 x 27 partial sums itself.  Same bits; timing: profiles/r04_icp_exchange.txt
-        unsigned long long* bc = L.slots + (size_t)28 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)(step - 1) * 32;
-        const unsigned tag = L.tag_base + (unsigned)(step - 1);
-        if (blockIdx.x == 0) {
-          fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, tag, s_tot, &s_abort);
-          s_code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-          if (threadIdx.x < 17) {
-            const unsigned bits = threadIdx.x < 16 ? __float_as_uint(s_pose[cur_buf ^ 1][threadIdx.x]) : (unsigned)s_code;
-            __hip_atomic_store(bc + threadIdx.x, ((unsigned long long)tag << 32) | bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        } else {
-          __shared__ int s_bc_code;
-          if (threadIdx.x < 17) {
-            unsigned long long u;
-            do { u = __hip_atomic_load(bc + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if ((unsigned)(u >> 32) != tag) __builtin_amdgcn_s_sleep(1); } while ((unsigned)(u >> 32) != tag);
-            if (threadIdx.x < 16) s_pose[cur_buf ^ 1][threadIdx.x] = __uint_as_float((unsigned)u); else s_bc_code = (int)(unsigned)u;
-          }
-          __syncthreads();
-          s_code = s_bc_code;
-        }
-        if (s_code != STEP_APPLIED) {
-          if (blockIdx.x == 0 && threadIdx.x == 0) { st->status = s_code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 0; }
-          return;
-        }
-        cur_buf ^= 1; s_cur = s_pose[cur_buf];
-        __syncthreads();
-        ++applied;
-      } else
-#endif
-      if (step > 0) {
-        fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, (KF_EXP_MODE(L) == 2 && n_prev > 16) ? 16 : n_prev, L.tag_base + (unsigned)(step - 1), s_tot, &s_abort, KF_EXP_MODE(L), &st->rescue_tag, L.tag_base);
-        if (s_abort) { timed_out = true; break; }
-        KF_STAMP(1);
-#ifdef KF_EXPERIMENTS
-        if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)     // per-wave: fold of the previous step done
-          L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + 16 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef KF_EXPERIMENTS
-        if (KF_EXP_MODE(L) == 8 && threadIdx.x == 0) L.slots[(size_t)24 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)(step - 1) * 1024 + blockIdx.x * 2 + 1] = __builtin_amdgcn_s_memrealtime();
-#endif
-        if (KF_EXP_MODE(L) == 1) { s_code = STEP_APPLIED; __syncthreads(); } else     // timing only: skip the 6x6 solve
-        { s_code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]); if (s_code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; } }
-        if (s_code != STEP_APPLIED) {                                            // same verdict in every workgroup
-          if (blockIdx.x == 0 && threadIdx.x == 0) { st->status = s_code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 0; }
-          return;
-        }
-        ++applied;
-      }
-      KF_STAMP(2);
-      float acc[27];
-#pragma unroll
-      for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-      if (has_px) {
-        icp_accumulate(a, s_cur, s_linv, iv, in_, model_v, model_n, acc);
-        KF_STAMP(3);
-#ifdef KF_EXPERIMENTS
-        if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)     // per-wave: pixel phase done (workgroup 5)
-          L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
-#endif
-        // workgroup partial, stored write-through (sc1) for the other CUs
-        int k; float sw;
-        if (icp_wg_reduce(acc, s_wave, k, sw))
-          __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + blockIdx.x * 32 + k,
-                             ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(sw),
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      KF_STAMP(4);
-      KF_STAMP(5);
-#ifdef KF_EXPERIMENTS
-      if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)       // per-wave: partial published / wave idle again
-        L.slots[(size_t)25 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 32 + 8 + (threadIdx.x >> 6)] = __builtin_amdgcn_s_memrealtime();
-#endif
-#ifdef KF_EXPERIMENTS
-      if (KF_EXP_MODE(L) == 8 && threadIdx.x == 0) L.slots[(size_t)24 * KF_ICP_LOOP_MAX_WG * 32 + (size_t)step * 1024 + blockIdx.x * 2] = __builtin_amdgcn_s_memrealtime();
-#endif
-      n_prev = grid_l;
-    }
-    if (timed_out) break;
-  }
-  if (stamp) { for (int i = 0; i < 6; ++i) st->reduced[20 + i] = seg[i]; }
-  // the last step's system, then commit _pose (ICP.cpp:84)
-  __shared__ unsigned s_who;
-  for (;;) {
-    if (!timed_out) fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, L.tag_base + (unsigned)(step - 1), s_tot, &s_abort, 0, &st->rescue_tag, L.tag_base);
-    if (!(timed_out || s_abort)) break;
-    ICP_DECIDE_ABORT();
-    if (s_abort == 2) { ICP_SOLO_CALL; return; }
-    if (s_abort != 3 || timed_out) return;                                     // somebody else finishes the launch alone
-    __syncthreads();
-    if (threadIdx.x == 0) s_abort = 0;                                         // the others are through: every sum is published, the last fold cannot wait again
-    __syncthreads();
-  }
-  // exactly one party ends the launch: a lane of an idle wave settles it while wave 0 solves; s_who is read behind apply_step's barrier
-  if (threadIdx.x == 128) { bool mine_; s_who = track_commit_decide(st, L.tag_base, 1u, commit_seen0, &mine_); }
-  s_code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-  if (s_who == 2u) return;                                                     // a workgroup claimed the launch after a time-out: it commits and runs every share of the tail
-  if (s_code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; }
-  const bool tail = L.cull_on && s_code == STEP_APPLIED;                       // (uniform over the launch: every workgroup arrives at the same verdict)
-  if (blockIdx.x != 0 && !tail) return;
-  __shared__ float s_tinv[16];
-  __shared__ unsigned s_cull[17];
-  if (blockIdx.x == 0) {
-    if (threadIdx.x < 27 && KF_EXP_MODE(L) != 7) st->reduced[threadIdx.x] = s_tot[threadIdx.x];
-    if (s_code != STEP_APPLIED) { if (threadIdx.x == 0) { st->status = s_code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 0; } return; }
-    if (threadIdx.x < 16) st->pose[threadIdx.x] = s_cur[threadIdx.x];
-    if (threadIdx.x == 0) { st->status = KF_TRACK_OK; st->tracked = 1; st->iterations = applied + 1; st->converged = 0; st->rescued = 0; }    // (the whole verdict: this launch may have run without k_track_begin's reset)
-  }
-  if (threadIdx.x == 64) kf_mat44_inverse(s_cur, s_tinv);                      // a lane of another wave: world -> camera (integrateVolume.cu:84), for the fusion pass and the tail
-  __syncthreads();
-  if (blockIdx.x == 0 && threadIdx.x < 16) st->pose_inv[threadIdx.x] = s_tinv[threadIdx.x];
-  if (tail) cull_tail(L.cull, s_tinv, (int)blockIdx.x, L.n_loop, s_cull);      // every workgroup holds the same pose bits, hence the same inverse
-}
-
-
-// ---- the same loop for images whose level 0 needs more workgroups than the chip holds at once (1280x960: 800) ------------------------------------------
-// The per-step form pays a kernel boundary per Gauss-Newton step and folds 800 x 27 partials from a cold start each time (24 us per step at 1280x960:
-// 0.46 ms of BASELINE config C5's frame).  Here n_loop resident workgroups play the n_virtual workgroups of the dealing in turn -- workgroup p plays p,
-// p + n_loop, ... -- each turn exactly a workgroup's pixel phase, reduction and publication in the per-step form's dealing, so the tagged slots hold the
-// same partial sums and the same fold arrives at the SAME BITS as k_icp_step (tests/test_gpu_track_forms.py).  A lane's pixels cannot stay in registers
-// across steps (several turns share them): they are re-read every step, from L2 / the Infinity Cache (78 MB per step at 1280x960 fit the 256 MiB cache).
-__global__ void __launch_bounds__(ICP_THREADS) k_icp_loop_batched(IcpLoopArgs L) {
-  if ((int)blockIdx.x >= L.n_loop) { icp_rider(L); return; }
-  __shared__ float s_pose[2][16], s_linv[16];
-  __shared__ float s_wave[27 * (ICP_THREADS / 16)], s_tot[(ICP_THREADS / 32) * 32];
-  __shared__ int s_abort;
-  int s_code = STEP_APPLIED, cur_buf = 0;
-  float* s_cur = s_pose[0];
-  KfTrackState* st = L.track;
+  // a workgroup that only becomes resident after the launch has been given up has nothing to do; `play_dead`: fault injection (kf_inject_track_stall) --
+  // the last workgroup behaves as if it never became resident.  (The pose and the two words are requested together: one round trip.)
   const float pose_e = st->pose[threadIdx.x & 15];                             // ICP.cpp:62 cur_transform = _pose
   const unsigned commit_seen0 = __hip_atomic_load(&st->commit_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (__hip_atomic_load(&st->rescue_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == L.tag_base) return;
   if (L.play_dead && (int)blockIdx.x == L.n_loop - 1) return;
-  if (threadIdx.x < 16) s_cur[threadIdx.x] = pose_e;
-  if (threadIdx.x == 0) s_abort = 0;
-  __syncthreads();
-  if (threadIdx.x == 0) kf_mat44_inverse(s_cur, s_linv);                        // ICP.cpp:63 last_transform_inv
-  __syncthreads();
   TrackArgs a;
-  a.dist_thres = L.dist_thres; a.sin_thres = L.sin_thres; a.dist_shake = L.dist_shake; a.angle_shake = L.angle_shake; a.cos_shake = L.cos_shake; a.dist_shake2 = L.dist_shake2;
-  a.dist_thres2 = L.dist_thres2; a.sin_thres2 = L.sin_thres2; a.sdf = 0;
+  a.th = L.th; a.sdf = 0;
+#ifdef KF_EXPERIMENTS
+  a.dbg = (!BATCHED && KF_EXP_MODE(L) == 11 && blockIdx.x == 0) ? L.slots + (size_t)26 * KF_ICP_LOOP_MAX_WG * 32 : nullptr;
+  a.exp_nodet = !BATCHED && KF_EXP_MODE(L) == 12;
+#endif
+  auto start = [&](bool solo) {                                               // the running transform and last_transform_inv (ICP.cpp:62-63)
+    cur_buf = 0; s_cur = s_pose[0];
+    if (threadIdx.x < 16) s_cur[threadIdx.x] = solo ? st->pose[threadIdx.x] : pose_e;
+    if (threadIdx.x == 0) s_abort = 0;
+    __syncthreads();
+    if (threadIdx.x == 0) kf_mat44_inverse(s_cur, s_linv);
+    __syncthreads();
+  };
+  auto apply = [&]() {
+    const int code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
+    if (code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; }
+    return code;
+  };
+  start(false);
+  LoopOutcome o = icp_loop_steps<BATCHED>(L, a, false, apply, s_pose, cur_buf, s_cur, s_linv, s_wave, s_tot, &s_abort);
+  if (track_loop_end(L, commit_seen0, false, o, s_tot, &s_abort, s_cur, apply, s_linv) != LOOP_SOLO) return;
+#ifdef KF_ICP_NO_SOLO          // A/B variant only (tools/build_variant.sh): what the solo path costs the hot loop in registers / code placement
+  if (threadIdx.x == 0) track_verdict(st, KF_TRACK_STALLED, 0, 0, 0);
+#else
 #ifdef KF_EXPERIMENTS
   a.dbg = nullptr; a.exp_nodet = false;
 #endif
-  int step = 0, n_prev = 0, applied = 0;
-  bool timed_out = false;
-  for (int l = L.levels - 1; l >= 0; --l) {                                      // coarse -> fine, ICP.cpp:65
-    a.cam = L.cam[l];
-    const float4* __restrict__ new_v = L.new_v[l]; const float4* __restrict__ new_n = L.new_n[l];
-    const int npx = a.cam.cols * a.cam.rows;
-    int px_l, grid_l;
-    icp_level_geometry(npx, L.n_virtual, l, px_l, grid_l);
-    for (int it = 0; it < L.iters[l]; ++it, ++step) {
-      // this step's FIRST turn's pixels are requested before the previous step's sums are waited for (they depend on the level only): in flight during the fold;
-      // every later turn's pixels are requested one turn ahead (below)
-      float4 ivn[ICP_PX], inn[ICP_PX];
-#pragma unroll
-      for (int j = 0; j < ICP_PX; ++j) {
-        const int i = icp_dealt_pixel_of(j, grid_l, (int)blockIdx.x);
-        ivn[j] = make_float4(0.f, 0.f, 0.f, 0.f); inn[j] = ivn[j];
-        if ((int)blockIdx.x < grid_l && j < px_l && i < npx) { ivn[j] = new_v[i]; inn[j] = new_n[i]; }
-      }
-      if (step > 0) {
-        fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, L.tag_base + (unsigned)(step - 1), s_tot, &s_abort, 0, &st->rescue_tag, L.tag_base);
-        if (s_abort) { timed_out = true; break; }
-        s_code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-        if (s_code != STEP_APPLIED) {                                            // same verdict in every workgroup
-          if (blockIdx.x == 0 && threadIdx.x == 0) { st->status = s_code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 0; }
-          return;
-        }
-        cur_buf ^= 1; s_cur = s_pose[cur_buf];
-        ++applied;
-      }
-      // this workgroup's turns: the workgroups blockIdx.x, blockIdx.x + n_loop, ... of the dealing; their partial sums are added up HERE, in that order, and
-      // published as ONE set of 27 words -- a step's fold then walks n_loop x 27 tagged words (205 at 1280x960), not grid_l x 27 (800): round 4's batched
-      // loop spent four polling passes per step on them.  The per-step form folds its 800 partials in the same groups (fold_partials, TrackArgs::fold_group).
-      float gsum = 0.f;
-      // the NEXT turn's pixels are requested before this turn's pixel phase: a turn's own loads (L2 / Infinity Cache, ~1 us) would otherwise be exposed three or
-      // four times per step -- the workgroups of a step reach the exchange that much earlier
-      for (int w = (int)blockIdx.x; w < grid_l; w += L.n_loop) {
-        float4 iv[ICP_PX], in_[ICP_PX];
-#pragma unroll
-        for (int j = 0; j < ICP_PX; ++j) { iv[j] = ivn[j]; in_[j] = inn[j]; }
-        if (w + L.n_loop < grid_l) {
-#pragma unroll
-          for (int j = 0; j < ICP_PX; ++j) {
-            const int i = icp_dealt_pixel_of(j, grid_l, w + L.n_loop);
-            ivn[j] = make_float4(0.f, 0.f, 0.f, 0.f); inn[j] = ivn[j];
-            if (j < px_l && i < npx) { ivn[j] = new_v[i]; inn[j] = new_n[i]; }
-          }
-        }
-        float acc[27];
-#pragma unroll
-        for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-        icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
-        int k; float sw;
-        const bool holder = icp_wg_reduce(acc, s_wave, k, sw);
-        if (holder) gsum = (w == (int)blockIdx.x) ? sw : gsum + sw;
-        __syncthreads();                                                         // s_wave is reused by the next turn
-        if (holder && w + L.n_loop >= grid_l)                                    // the last turn: publish
-          __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + blockIdx.x * 32 + k,
-                             ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(gsum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      n_prev = grid_l < L.n_loop ? grid_l : L.n_loop;
-    }
-    if (timed_out) break;
-  }
-  __shared__ unsigned s_who;
-  for (;;) {
-    if (!timed_out) fold_partials_tagged(L.slots + (size_t)(step - 1) * KF_ICP_LOOP_MAX_WG * 32, n_prev, L.tag_base + (unsigned)(step - 1), s_tot, &s_abort, 0, &st->rescue_tag, L.tag_base);
-    if (!(timed_out || s_abort)) break;
-    ICP_DECIDE_ABORT();
-    if (s_abort == 2) { ICP_SOLO_CALL; return; }
-    if (s_abort != 3 || timed_out) return;
-    __syncthreads();
-    if (threadIdx.x == 0) s_abort = 0;
-    __syncthreads();
-  }
-  if (threadIdx.x == 128) { bool mine_; s_who = track_commit_decide(st, L.tag_base, 1u, commit_seen0, &mine_); }      // (see k_icp_loop)
-  s_code = apply_step(a, s_tot, s_cur, nullptr, s_pose[cur_buf ^ 1]);
-  if (s_who == 2u) return;
-  if (s_code == STEP_APPLIED) { cur_buf ^= 1; s_cur = s_pose[cur_buf]; }
-  if (blockIdx.x != 0) return;
-  if (threadIdx.x < 27) st->reduced[threadIdx.x] = s_tot[threadIdx.x];
-  if (s_code != STEP_APPLIED) { if (threadIdx.x == 0) { st->status = s_code; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 0; } return; }
-  if (threadIdx.x < 16) st->pose[threadIdx.x] = s_cur[threadIdx.x];
-  if (threadIdx.x == 64) kf_mat44_inverse(s_cur, st->pose_inv);
-  if (threadIdx.x == 0) { st->status = KF_TRACK_OK; st->tracked = 1; st->iterations = applied + 1; st->converged = 0; st->rescued = 0; }
+  start(true);
+  o = icp_loop_steps<true>(L, a, true, apply, s_pose, cur_buf, s_cur, s_linv, s_wave, s_tot, &s_abort);
+  track_loop_end(L, commit_seen0, true, o, s_tot, &s_abort, s_cur, apply, s_linv);
+#endif
 }
+__global__ void __launch_bounds__(ICP_THREADS) k_icp_loop(IcpLoopArgs L) { icp_loop<false>(L); }
+// ---- the same loop for images whose level 0 needs more workgroups than the chip holds at once (1280x960: 800) ------------------------------------------
+// The per-step form pays a kernel boundary per Gauss-Newton step and folds 800 x 27 partials from a cold start each time (24 us per step at 1280x960:
+// 0.46 ms of BASELINE config C5's frame).  Here n_loop resident workgroups play the n_virtual workgroups of the dealing in turn (icp_publish), so the
+// tagged slots hold the same partial sums and the same fold arrives at the SAME BITS as k_icp_step (tests/test_gpu_track_forms.py).
+__global__ void __launch_bounds__(ICP_THREADS) k_icp_loop_batched(IcpLoopArgs L) { icp_loop<true>(L); }
 
 // ---- SDF tracker ------------------------------------------------------------------------------------------------------
 // the six perturbed transforms delta * cur for +w1, -w1, +w2, -w2, +w3, -w3 (CalSDFErrSolverParams.cu:118-133) into s_m[1..6]; s_m[0] = cur.  96 lanes.
@@ -1288,21 +1198,17 @@ static inline void launch_sdf_step(kf_ctx* c, int grid, const TrackArgs& a) {
 // sees the same mix of surface and background), the 27 sums per workgroup by DPP + LDS, published as tagged 64-bit words and folded by everybody in one fixed
 // order (fold_partials_tagged), the 6x6 system solved by a wave (llt_solve6_wave), the shake / convergence tests and the fp64 exponential map on that wave,
 // and the loop leaves as soon as the increment's norm drops below 1e-3 (SDF.cpp:87-90) -- no launches that find `converged` and return.
-// A fold that times out is finished by ONE workgroup playing every workgroup in turn (as icp_solo_finish, but the same code: `first` / `stride`), and
-// exactly one party ends the launch (KfTrackState::commit_word).
+// It ends as the ICP loop does (track_loop_end); a workgroup that finishes the launch alone runs the same loop again playing every workgroup of the
+// dealing in turn (`first` / `stride`).
 #ifndef SDF_THREADS
 #define SDF_THREADS ICP_THREADS
 #endif
-struct SdfLoopArgs {
+struct SdfLoopArgs : TrackLoopArgs {
   KfVolume vol; const float* depth; KfCam cam;
   int max_iter;
-  float dist_shake, angle_shake, cos_shake, dist_shake2;
-  unsigned long long* slots; unsigned tag_base; KfTrackState* track; unsigned* stall_word;
-  int n_loop;                                    // workgroups of the launch = publishers of a step
+  TrackThresholds th;
   int px_l;                                      // pixels per lane = 8x8 tiles per wave: ceil(tiles / (waves per workgroup * n_loop))
   int slab_pixels;
-  int play_dead;                                 // fault injection (kf_inject_track_stall)
-  int cull_on; IntegrateArgs cull;               // the fusion pass's brick cull as the launch's tail (cull.h), as in k_icp_loop
 };
 // direct_exponential_map (eigen_utils.cpp:84-127) + SDF.cpp:92-100 with the three even series in t = theta^2 instead of sqrt / sin / cos / five fp64 divisions
 // on the one-lane chain of every iteration: sinc = sum (-t)^k / (2k+1)!, mcosc = sum (-t)^k / (2k+2)!, msinc = sum (-t)^k / (2k+3)!, cos = 1 - t mcosc.
@@ -1412,9 +1318,7 @@ template <typename AD>
 __global__ void __launch_bounds__(SDF_THREADS) k_sdf_loop(SdfLoopArgs L) {
   __shared__ float s_m[7][16];
   __shared__ float s_wave[27 * (SDF_THREADS / 16)], s_tot[(SDF_THREADS / 32) * 32];
-  __shared__ int s_abort, s_code, s_role;
-  __shared__ float s_tinv[16];
-  __shared__ unsigned s_cull[17];
+  __shared__ int s_abort, s_code;
   KfTrackState* st = L.track;
   // (the claim word and the commit word are requested together with the pose: one round trip)
   const unsigned commit_seen0 = __hip_atomic_load(&st->commit_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1427,15 +1331,16 @@ __global__ void __launch_bounds__(SDF_THREADS) k_sdf_loop(SdfLoopArgs L) {
   const KfRecip rS = kf_recip(L.vol.size);
   const float rcell = 1.0f / L.vol.cell;
   const AD S(L.vol);
+  float* const s_cur = s_m[0];
+  auto apply = [&]() { return sdf_apply_step_wave(s_tot, s_cur, L.th.dist_shake2, L.th.cos_shake, &s_code); };     // SDF.cpp:79-100
   int first = (int)blockIdx.x, stride = L.n_loop;                         // the workgroups of the dealing this one plays: its own -- or all of them, once it finishes alone
   bool solo = false;
-  int code = STEP_APPLIED, applied = 0;
-  for (int attempt = 0; ; ++attempt) {
-    if (threadIdx.x < 16) s_m[0][threadIdx.x] = st->pose[threadIdx.x];    // SDF.cpp:56 cur_transform = _pose (again from the committed pose: nothing of an attempt is kept)
+  for (;;) {
+    // SDF.cpp:56 cur_transform = _pose -- for the solo finish, too: the claim excludes every other committer, so st->pose is still the pose at kernel entry
+    if (threadIdx.x < 16) s_cur[threadIdx.x] = st->pose[threadIdx.x];
     if (threadIdx.x == 0) s_abort = 0;
     __syncthreads();
-    code = STEP_APPLIED; applied = 0;
-    bool timed_out = false;
+    LoopOutcome o = {STEP_APPLIED, 0, grid_l, 0, false};
     for (int it = 0; it < L.max_iter; ++it) {                             // SDF.cpp:57
       sdf_perturbed_transforms(s_m, w_h);
       __syncthreads();
@@ -1465,65 +1370,22 @@ __global__ void __launch_bounds__(SDF_THREADS) k_sdf_loop(SdfLoopArgs L) {
         __syncthreads();                                                   // s_wave is reused by the next turn
       }
       fold_partials_tagged(L.slots + (size_t)it * KF_ICP_LOOP_MAX_WG * 32, grid_l, L.tag_base + (unsigned)it, s_tot, &s_abort, 0, solo ? nullptr : &st->rescue_tag, L.tag_base);
-      if (s_abort) { timed_out = true; break; }
-      code = sdf_apply_step_wave(s_tot, s_m[0], L.dist_shake2, L.cos_shake, &s_code);      // SDF.cpp:79-100
-      if (code != STEP_APPLIED) break;
-      ++applied;
+      o.fold = it;
+      if (s_abort) { o.timed_out = true; break; }
+      o.code = apply();
+      if (o.code != STEP_APPLIED) break;
+      ++o.applied;
     }
-    // Who ends the launch?  role 0: leave; 1: the ordinary end (one of the launch's workgroups); 2: finish the launch alone (run the loop again, playing every
-    // workgroup); 3: the others went through after all (every sum is published by now): run the loop again in step with them; 4: the solo finisher's end
-    if (threadIdx.x == 0) {
-      int role;
-      if (solo) role = timed_out ? 0 : 4;
-      else {
-        bool mine;
-        const unsigned who = track_commit_decide(st, L.tag_base, timed_out ? 2u : 1u, commit_seen0, &mine);
-        if (!timed_out) role = who == 1u ? 1 : 0;
-        else if (who == 2u && mine) {                                      // this workgroup's compare-and-swap took the word: it finishes the launch alone
-          __hip_atomic_store(&st->rescue_tag, L.tag_base, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);       // whoever still polls leaves
-          __hip_atomic_store(L.stall_word, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-          role = 2;
-        } else role = who == 1u ? 3 : 0;
-      }
-      s_role = role;
-    }
-    __syncthreads();
-    const int role = s_role;
-    if (role == 1 || role == 4) break;
-    if (role == 2) { solo = true; first = 0; stride = 1; continue; }
-    if (role == 3 && attempt < 3) continue;
-    if (solo && threadIdx.x == 0) { st->status = KF_TRACK_STALLED; st->tracked = 0; st->iterations = applied; st->converged = 0; st->rescued = 1; }   // (a solo fold waits for nobody: unreachable)
-    return;
-  }
-  // ---- the launch's end: SDF.cpp:103 _pose = cur_transform (a lost frame keeps the old pose: `return false` at :84), then the tail --------------------
-  const bool writer = solo || blockIdx.x == 0;
-  const bool good = code != STEP_LOST_SHAKE && code != STEP_LOST_DET;
-  if (writer) {
-    if (threadIdx.x < 27) st->reduced[threadIdx.x] = s_tot[threadIdx.x];
-    if (good && threadIdx.x < 16) st->pose[threadIdx.x] = s_m[0][threadIdx.x];
-    if (threadIdx.x == 0) {
-      st->status = good ? KF_TRACK_OK : code; st->tracked = good ? 1 : 0; st->iterations = applied;
-      st->converged = code == STEP_CONVERGED ? 1 : 0; st->rescued = solo ? 1 : 0;
-    }
-  }
-  if (!good) return;
-  const bool tail = L.cull_on != 0;
-  if (!writer && !tail) return;
-  if (threadIdx.x == 64) kf_mat44_inverse(s_m[0], s_tinv);                // world -> camera (integrateVolume.cu:84), for the fusion pass and the tail
-  __syncthreads();
-  if (writer && threadIdx.x < 16) st->pose_inv[threadIdx.x] = s_tinv[threadIdx.x];
-  if (tail) {
-    if (solo) { for (int w = 0; w < L.n_loop; ++w) cull_tail(L.cull, s_tinv, w, L.n_loop, s_cull); }
-    else cull_tail(L.cull, s_tinv, (int)blockIdx.x, L.n_loop, s_cull);
+    if (track_loop_end(L, commit_seen0, solo, o, s_tot, &s_abort, s_cur, apply, s_m[1]) != LOOP_SOLO) return;
+    solo = true; first = 0; stride = 1;
   }
 }
 
 // ---- loop control ---------------------------------------------------------------------------------------------------
 // mode 0: frame 0 (no tracking, "tracked"); mode 1: start of a Gauss-Newton loop
-__global__ void k_track_begin(KfTrackState* st, int mode, KfGridBarrier* gb) {
-  if (blockIdx.x == 0 && threadIdx.x < 10 && gb) reinterpret_cast<KfPaddedCounter*>(gb)[threadIdx.x].v = 0u;   // 8 groups + top + gen
+__global__ void k_track_begin(KfTrackState* st, int mode) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  st->status = KF_TRACK_OK; st->iterations = 0; st->converged = 0; st->arrive = 0u; st->rescued = 0;
+  st->status = KF_TRACK_OK; st->iterations = 0; st->converged = 0; st->rescued = 0;
   if (mode == 0) { st->tracked = 1; return; }
   st->tracked = 0;
   for (int i = 0; i < 16; ++i) st->cur[0][i] = st->pose[i];                 // ICP.cpp:62
@@ -1556,13 +1418,26 @@ static inline float shake_cos(float angle) { return angle >= 3.14159274f ? -2.f 
 // is rejected, every increment counts as shaking): -1 keeps that, since a squared norm is never below zero
 static inline float gate_square(float t) { return t < 0.f ? -1.f : t * t; }
 // the thresholds of one tracking call, in every form the kernels use
-static inline void set_thresholds(TrackArgs& a, float dist_thres, float sin_thres, float dist_shake, float angle_shake) {
-  a.dist_thres = dist_thres; a.sin_thres = sin_thres; a.dist_shake = dist_shake; a.angle_shake = angle_shake;
-  a.cos_shake = shake_cos(angle_shake); a.dist_shake2 = gate_square(dist_shake);
-  a.dist_thres2 = gate_square(dist_thres); a.sin_thres2 = gate_square(sin_thres);
+static inline TrackThresholds track_thresholds(float dist_thres, float sin_thres, float dist_shake, float angle_shake) {
+  TrackThresholds t;
+  t.dist_thres = dist_thres; t.sin_thres = sin_thres; t.dist_shake = dist_shake; t.angle_shake = angle_shake;
+  t.cos_shake = shake_cos(angle_shake); t.dist_shake2 = gate_square(dist_shake);
+  t.dist_thres2 = gate_square(dist_thres); t.sin_thres2 = gate_square(sin_thres);
+  return t;
 }
 static inline KfCam to_cam(const kf_camera_params* p) {
   KfCam c; c.cols = (int)p->cols; c.rows = (int)p->rows; c.cx = p->cx; c.cy = p->cy; c.fx = p->fx; c.fy = p->fy; return c;
+}
+// the camera of pyramid level l (ICP.cpp:36-48: every level halves the one above)
+static inline KfCam level_cam(const kf_camera_params* cam0, int l) {
+  kf_camera_params p = *cam0;
+  for (int k = 0; k < l; ++k) { p.cols /= 2; p.rows /= 2; p.cx /= 2; p.cy /= 2; p.fx /= 2; p.fy /= 2; }
+  return to_cam(&p);
+}
+static int icp_iters(int levels, int iters[KF_MAX_LEVELS]) {                // ICP.cpp:14-35
+  iters[0] = iters[1] = iters[2] = 0;
+  if (levels == 1) iters[0] = 3; else if (levels == 2) { iters[0] = 10; iters[1] = 5; } else if (levels == 3) { iters[0] = 10; iters[1] = 5; iters[2] = 4; } else return 0;
+  return iters[0] + iters[1] + iters[2];
 }
 static inline int track_grid(int npx) {           // SDF tracker: 256 lanes, grid-stride
   int g = kf_div_up(npx, TRK_THREADS * TRK_PX);
@@ -1593,7 +1468,7 @@ extern "C" int kf_cal_point_to_plane_solver_params(kf_ctx* c, uint32_t level, co
   a.new_v = c->new_v[level]; a.new_n = c->new_n[level]; a.model_v = c->model_v[level]; a.model_n = c->model_n[level];
   a.cam = to_cam(cam);
   for (int i = 0; i < 16; ++i) { a.cur_val.m[i] = cur->m[i]; a.linv_val.m[i] = last_inv->m[i]; }
-  set_thresholds(a, dist_thres, sin_thres, 0.f, 0.f);
+  a.th = track_thresholds(dist_thres, sin_thres, 0.f, 0.f);
   a.partials = c->icp_partials; a.track = c->track;
   const int grid = icp_grid(a.cam.cols * a.cam.rows);
   if (grid > KF_ICP_MAX_WG) return KF_ERR_ARG;
@@ -1628,7 +1503,7 @@ extern "C" int kf_read_solver_params(kf_ctx* c, float out27[27]) {
 #ifndef KF_ICP_COOPERATIVE_DEFAULT
 #define KF_ICP_COOPERATIVE_DEFAULT 0
 #endif
-// a persistent loop timed out and was finished by one workgroup alone (icp_solo_finish: the frame is kept, milliseconds late): back off to
+// a persistent loop timed out and was finished by one workgroup alone (track_loop_end: the frame is kept, milliseconds late): back off to
 // per-step launches for a while (64 frames, doubling up to 4096 on repeats; 1024 clean loop frames in a row forget the history).  One episode
 // is noted once: launches of the loop that were already enqueued when the word was seen raise it again while the back-off is running.
 static void kf_note_loop_stall(kf_ctx* c) {
@@ -1636,6 +1511,22 @@ static void kf_note_loop_stall(kf_ctx* c) {
   c->persistent_backoff_len = c->persistent_backoff_len ? (c->persistent_backoff_len >= 2048 ? 4096 : c->persistent_backoff_len * 2) : 64;
   c->persistent_backoff = c->persistent_backoff_len;
   c->loop_clean_frames = 0;
+}
+// May this tracking call run a persistent loop (k_icp_loop, k_icp_loop_batched, k_sdf_loop)?  `fits`: the caller's own conditions.  A loop of an EARLIER frame
+// that gave up waiting (its workgroups were not co-resident: a foreign process on the GPU) has set the pinned stall word by now -- no read-back of the verdict
+// needed: the next frames take one launch per step (same bits for ICP, see k_icp_step); after `persistent_backoff_len` of them the loop is tried again, and
+// every further stall doubles that wait.  The loop also needs this context alone on a device nobody else uses.  Admitted: this launch's tags and fault
+// injection go into L.
+static bool kf_loop_admit(kf_ctx* c, bool fits, TrackLoopArgs& L) {
+  unsigned* stall_word = (unsigned*)((char*)c->host_pinned + KF_PINNED_STALL_WORD);
+  if (__atomic_load_n(stall_word, __ATOMIC_RELAXED)) { __atomic_store_n(stall_word, 0u, __ATOMIC_RELAXED); kf_note_loop_stall(c); }
+  else if (c->persistent_backoff == 0 && c->persistent_backoff_len && ++c->loop_clean_frames >= 1024) { c->persistent_backoff_len = 0; c->loop_clean_frames = 0; }
+  if (!fits || c->loop_refused || kf_live_contexts(c->cfg.device) != 1 || kf_device_shared(c->cfg.device)) return false;
+  if (c->persistent_backoff > 0) { --c->persistent_backoff; return false; }
+  c->icp_loop_seq += 64u;                                    // tags of one launch never collide with an earlier launch's slots
+  L.slots = c->icp_loop_slots; L.tag_base = c->icp_loop_seq; L.track = c->track; L.stall_word = stall_word;
+  if (c->inject_stall > 0) { L.play_dead = 1; --c->inject_stall; }
+  return true;
 }
 
 // The fusion pass's cull as the tail of a persistent tracking launch (k_icp_loop, k_sdf_loop): the previous kf_integrate_volume(transform == NULL) left its
@@ -1660,30 +1551,17 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
   c->last_track_form = 0;
   { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }   // (a tail cull of the previous frame that no kf_integrate_volume consumed)
   if (frame_id == 0) {                                       // ICP.cpp:52-55
-    hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 0, c->grid_barrier);
+    hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 0);
     return (int)hipGetLastError();
   }
-  int iters[KF_MAX_LEVELS] = {0, 0, 0};                      // ICP.cpp:14-35
-  if (c->levels == 1) iters[0] = 3; else if (c->levels == 2) { iters[0] = 10; iters[1] = 5; } else { iters[0] = 10; iters[1] = 5; iters[2] = 4; }
+  int iters[KF_MAX_LEVELS];
+  const int n_steps = icp_iters(c->levels, iters);
   int st;
   kf_evt_begin(c, KF_STAGE_TRACK);
-  kf_camera_params cams[KF_MAX_LEVELS]; cams[0] = *cam0;
-  for (int l = 1; l < c->levels; ++l) {                      // ICP.cpp:36-48
-    cams[l].cols = cams[l - 1].cols / 2; cams[l].rows = cams[l - 1].rows / 2;
-    cams[l].cx = cams[l - 1].cx / 2; cams[l].cy = cams[l - 1].cy / 2; cams[l].fx = cams[l - 1].fx / 2; cams[l].fy = cams[l - 1].fy / 2;
-  }
   const int grid0 = icp_grid(c->cols * c->rows);
   static int persistent_env = -1, coop_env = -1;
   if (persistent_env < 0) { const char* e = getenv("KF_ICP_PERSISTENT"); persistent_env = e ? atoi(e) : 1; }
   if (coop_env < 0) { const char* e = getenv("KF_ICP_COOPERATIVE"); coop_env = e ? atoi(e) : KF_ICP_COOPERATIVE_DEFAULT; }
-  // A persistent loop of an EARLIER frame that gave up waiting (its workgroups were not co-resident: a foreign process on the GPU) has
-  // set the pinned stall word by now -- no read-back of the verdict needed.  The next frames use one launch per step (same bits, see
-  // k_icp_step); after `persistent_backoff_len` of them the loop is tried again, and every further stall doubles that wait.
-  unsigned* stall_word = (unsigned*)((char*)c->host_pinned + KF_PINNED_STALL_WORD);
-  if (__atomic_load_n(stall_word, __ATOMIC_RELAXED)) { __atomic_store_n(stall_word, 0u, __ATOMIC_RELAXED); kf_note_loop_stall(c); }
-  else if (c->persistent_backoff == 0 && c->persistent_backoff_len && ++c->loop_clean_frames >= 1024) { c->persistent_backoff_len = 0; c->loop_clean_frames = 0; }
-  bool use_loop = persistent_env && !c->loop_refused && grid0 <= KF_ICP_LOOP_MAX_WG && iters[0] + iters[1] + iters[2] <= KF_ICP_LOOP_STEPS &&
-                  kf_live_contexts(c->cfg.device) == 1 && !kf_device_shared(c->cfg.device);
   if (c->loop_occupancy == 0) {                              // (asked once, whatever form this call takes: the per-step form folds in the batched loop's groups)
     // every workgroup must be resident at once (they wait for each other's tagged partial sums): ask the runtime how many 512-lane
     // workgroups of THESE kernels a CU holds (registers, LDS) instead of assuming one
@@ -1696,45 +1574,30 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
   // VGA loop uses (the CU count less a share for the riders), each playing several workgroups of the dealing in turn.  KF_ICP_BATCHED=0: per step.
   static int batched_env = -1;
   if (batched_env < 0) { const char* e = getenv("KF_ICP_BATCHED"); batched_env = e ? atoi(e) : 1; }
-  int n_resident = grid0;                                    // workgroups of the loop launch
-  bool batched = false;
+  const bool beyond = c->loop_occupancy < 1 || (long long)grid0 > (long long)c->loop_occupancy * c->num_cus;
+  static int room_env = -1;                                  // KF_ICP_BATCHED_ROOM=n: resident workgroups of the batched loop (A/B; every launch form folds in groups of n, so the forms stay bitwise equal)
+  if (room_env < 0) { const char* e = getenv("KF_ICP_BATCHED_ROOM"); room_env = e ? atoi(e) : 0; }
+  const int room = c->loop_occupancy_batched >= 1 ? ((room_env >= 16 && room_env <= c->num_cus * c->loop_occupancy_batched) ? room_env : c->num_cus - c->num_cus / 5) : 0;      // 256 CUs: 205 resident workgroups, 51 CUs left to the riders
+  const bool batched = beyond && batched_env && !coop_env && room >= 16 && grid0 <= KF_ICP_LOOP_MAX_WG;
   // fold_group: the publishers of a batched launch.  Every launch form of such an image adds the partial sums of the workgroups g, g + fold_group, ... first
   // (the batched loop's resident workgroup g plays exactly those): the forms stay bitwise equal
-  int fold_group = 0;
-  {
-    const bool beyond = c->loop_occupancy < 1 || (long long)grid0 > (long long)c->loop_occupancy * c->num_cus;
-    static int room_env = -1;                                // KF_ICP_BATCHED_ROOM=n: resident workgroups of the batched loop (A/B; every launch form folds in groups of n, so the forms stay bitwise equal)
-    if (room_env < 0) { const char* e = getenv("KF_ICP_BATCHED_ROOM"); room_env = e ? atoi(e) : 0; }
-    const int room = c->loop_occupancy_batched >= 1 ? ((room_env >= 16 && room_env <= c->num_cus * c->loop_occupancy_batched) ? room_env : c->num_cus - c->num_cus / 5) : 0;      // 256 CUs: 205 resident workgroups, 51 CUs left to the riders
-    const bool can_batch = beyond && batched_env && !coop_env && room >= 16 && grid0 <= KF_ICP_LOOP_MAX_WG;
-    if (can_batch) fold_group = room;
-    if (use_loop && beyond) {
-      if (can_batch) { batched = true; n_resident = room; }
-      else use_loop = false;
-    }
-  }
-  if (use_loop && c->persistent_backoff > 0) { --c->persistent_backoff; use_loop = false; }
+  const int fold_group = batched ? room : 0;
+  IcpLoopArgs L; memset(&L, 0, sizeof(L));
+  const bool use_loop = kf_loop_admit(c, persistent_env && grid0 <= KF_ICP_LOOP_MAX_WG && n_steps <= KF_ICP_LOOP_STEPS && (!beyond || batched), L);
   // ICP.cpp:57-63: the four pyramids + the loop's set-up, one launch -- unless every pyramid describes its level 0 already (the raycast launch
   // left the model maps' behind, its riders the prefetched frame's: raycast.hip) AND the persistent loop runs, which reads nothing of that
   // set-up but the committed pose and writes its whole verdict itself: the steady-state frame then has no pyramid launch at all
   const bool pyramids_done = c->levels == 3 && c->new_pyr_ok && c->model_pyr_ok;
   if (!(use_loop && !coop_env && pyramids_done) && (st = kf_launch_pyramids_and_begin(c, 1))) return st;
   if (use_loop) {
-    IcpLoopArgs L; memset(&L, 0, sizeof(L));
     for (int l = 0; l < c->levels; ++l) {
       L.new_v[l] = c->new_v[l]; L.new_n[l] = c->new_n[l]; L.model_v[l] = c->model_v[l]; L.model_n[l] = c->model_n[l];
-      L.cam[l] = to_cam(&cams[l]); L.iters[l] = iters[l];
+      L.cam[l] = level_cam(cam0, l); L.iters[l] = iters[l];
     }
     L.levels = c->levels;
-    { TrackArgs th; set_thresholds(th, icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
-      L.dist_thres = th.dist_thres; L.sin_thres = th.sin_thres; L.dist_shake = th.dist_shake; L.angle_shake = th.angle_shake;
-      L.cos_shake = th.cos_shake; L.dist_shake2 = th.dist_shake2; L.dist_thres2 = th.dist_thres2; L.sin_thres2 = th.sin_thres2; }
-    c->icp_loop_seq += 64u;                                  // tags of one launch never collide with an earlier launch's slots
-    L.slots = c->icp_loop_slots; L.tag_base = c->icp_loop_seq; L.track = c->track;
-    L.stall_word = stall_word;
-    if (c->inject_stall > 0) { L.play_dead = 1; --c->inject_stall; }
+    L.th = track_thresholds(icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
     { static int em = -1; if (em < 0) em = KF_EXP_ENV("KF_ICP_EXP"); L.exp_mode = em; }
-    L.n_loop = n_resident; L.n_virtual = grid0;
+    L.n_loop = batched ? room : grid0; L.n_virtual = grid0;
     // a pending kf_prefetch_frame: the next frame's filter rides in this launch (see IcpLoopArgs) and leaves the gated + filtered image in
     // the alternate buffers; the raycast launch that follows carries its tile tables (the fusion pass in between clears them) and its
     // vertices / normals.  Not under a cooperative launch, whose whole grid would have to be resident.
@@ -1759,7 +1622,7 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
       (void)hipGetLastError();                               // refused: this device / configuration cannot hold the loop -- per-step from now on
       c->loop_refused = 1;
     } else {
-      if (batched) hipLaunchKernelGGL(k_icp_loop_batched, dim3((unsigned)n_resident + n_riders), dim3(ICP_THREADS), 0, c->stream, L);
+      if (batched) hipLaunchKernelGGL(k_icp_loop_batched, dim3((unsigned)L.n_loop + n_riders), dim3(ICP_THREADS), 0, c->stream, L);
       else hipLaunchKernelGGL(k_icp_loop, dim3((unsigned)grid0 + n_riders), dim3(ICP_THREADS), 0, c->stream, L);
       c->last_track_form = 1;
       kf_evt_end(c, KF_STAGE_TRACK);
@@ -1769,14 +1632,14 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
   // one launch per Gauss-Newton step: the same pixel dealing, the same reduction and fold orders as the loop -> the same pose bits
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.use_state = 1;
-  set_thresholds(a, icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
+  a.th = track_thresholds(icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   a.fold_group = fold_group;
   int step = 0, prev_grid = 0;
   for (int l = c->levels - 1; l >= 0; --l)                   // coarse -> fine, ICP.cpp:65
     for (int it = 0; it < iters[l]; ++it) {
       a.new_v = c->new_v[l]; a.new_n = c->new_n[l]; a.model_v = c->model_v[l]; a.model_n = c->model_n[l];
-      a.cam = to_cam(&cams[l]);
+      a.cam = level_cam(cam0, l);
       a.step = step; a.consume = step > 0; a.n_prev_wg = prev_grid;
       icp_level_geometry(a.cam.cols * a.cam.rows, grid0, l, a.px_l, a.deal_grid);
       const int grid = a.deal_grid;
@@ -1801,11 +1664,6 @@ extern "C" int kf_icp_partition_begin(kf_ctx* c, uint32_t frame_id) {
   if (frame_id != 0) kf_evt_begin(c, KF_STAGE_TRACK);       // (the stage timer runs from here to kf_icp_partition_finish: it includes the caller's all-reduces)
   return kf_launch_pyramids_and_begin(c, frame_id == 0 ? 0 : 1);
 }
-static int icp_iters(int levels, int iters[KF_MAX_LEVELS]) {                // ICP.cpp:14-35
-  iters[0] = iters[1] = iters[2] = 0;
-  if (levels == 1) iters[0] = 3; else if (levels == 2) { iters[0] = 10; iters[1] = 5; } else if (levels == 3) { iters[0] = 10; iters[1] = 5; iters[2] = 4; } else return 0;
-  return iters[0] + iters[1] + iters[2];
-}
 extern "C" int kf_icp_partition_steps(kf_ctx* c) { int it[KF_MAX_LEVELS]; return c ? icp_iters(c->levels, it) : 0; }
 extern "C" int kf_icp_partition_step(kf_ctx* c, uint32_t step, const kf_icp_params* icp, const kf_camera_params* cam0,
                                      uint32_t part, uint32_t parts, float* dev_sums) {
@@ -1815,13 +1673,11 @@ extern "C" int kf_icp_partition_step(kf_ctx* c, uint32_t step, const kf_icp_para
   if ((int)step >= total) return KF_ERR_ARG;
   int l = c->levels - 1, s = (int)step;                                     // coarse -> fine
   while (s >= iters[l]) { s -= iters[l]; --l; }
-  kf_camera_params cam = *cam0;
-  for (int k = 0; k < l; ++k) { cam.cols /= 2; cam.rows /= 2; cam.cx /= 2; cam.cy /= 2; cam.fx /= 2; cam.fy /= 2; }
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.use_state = 1;
   a.new_v = c->new_v[l]; a.new_n = c->new_n[l]; a.model_v = c->model_v[l]; a.model_n = c->model_n[l];
-  a.cam = to_cam(&cam);
-  set_thresholds(a, icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
+  a.cam = level_cam(cam0, l);
+  a.th = track_thresholds(icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   a.step = (int)step; a.consume = step > 0; a.ext_prev = step > 0 ? dev_sums : nullptr;
   const int rows_per = kf_div_up(a.cam.rows, (int)parts);                    // whole image rows per rank
@@ -1840,7 +1696,7 @@ extern "C" int kf_icp_partition_finish(kf_ctx* c, const kf_icp_params* icp, cons
   int iters[KF_MAX_LEVELS];
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.use_state = 1; a.consume = 1; a.step = icp_iters(c->levels, iters); a.ext_prev = dev_sums;
-  set_thresholds(a, icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake); a.partials = c->icp_partials; a.track = c->track;
+  a.th = track_thresholds(icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake); a.partials = c->icp_partials; a.track = c->track;
   hipLaunchKernelGGL(k_track_finish, dim3(1), dim3(ICP_THREADS), 0, c->stream, a);
   kf_evt_end(c, KF_STAGE_TRACK);
   return (int)hipGetLastError();
@@ -1860,7 +1716,7 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
   c->last_track_form = 0;
   { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
   if (frame_id == 0) {                                       // SDF.cpp:46-49
-    hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 0, c->grid_barrier);
+    hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 0);
     return (int)hipGetLastError();
   }
   kf_evt_begin(c, KF_STAGE_TRACK);
@@ -1869,21 +1725,16 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
   {
     static int loop_env = -1;
     if (loop_env < 0) { const char* e = getenv("KF_SDF_PERSISTENT"); const char* e2 = getenv("KF_ICP_PERSISTENT"); loop_env = (e ? atoi(e) : 1) && (e2 ? atoi(e2) : 1); }
-    unsigned* stall_word = (unsigned*)((char*)c->host_pinned + KF_PINNED_STALL_WORD);
-    if (__atomic_load_n(stall_word, __ATOMIC_RELAXED)) { __atomic_store_n(stall_word, 0u, __ATOMIC_RELAXED); kf_note_loop_stall(c); }
-    else if (c->persistent_backoff == 0 && c->persistent_backoff_len && ++c->loop_clean_frames >= 1024) { c->persistent_backoff_len = 0; c->loop_clean_frames = 0; }
     const bool buf = sdf_buffer_addressing(c->vol);
-    bool use_loop = loop_env && !c->loop_refused && sp->max_iter_nums >= 1 && sp->max_iter_nums <= KF_ICP_LOOP_STEPS &&
-                    kf_live_contexts(c->cfg.device) == 1 && !kf_device_shared(c->cfg.device);
-    if (use_loop && c->sdf_loop_occupancy == 0) {
+    const bool fits = loop_env && sp->max_iter_nums >= 1 && sp->max_iter_nums <= KF_ICP_LOOP_STEPS;
+    if (fits && c->sdf_loop_occupancy == 0) {
       int per_cu = 0;
       const hipError_t e = buf ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sdf_loop<SdfBufAddr>, SDF_THREADS, 0)
                                : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sdf_loop<SdfFlatAddr>, SDF_THREADS, 0);
       c->sdf_loop_occupancy = (e == hipSuccess && per_cu >= 1) ? per_cu : -1;
     }
-    if (use_loop && c->sdf_loop_occupancy < 1) use_loop = false;
-    if (use_loop && c->persistent_backoff > 0) { --c->persistent_backoff; use_loop = false; }
-    if (use_loop) {
+    SdfLoopArgs L; memset(&L, 0, sizeof(L));
+    if (kf_loop_admit(c, fits && c->sdf_loop_occupancy >= 1, L)) {
       const int npx = c->cols * c->rows;
       static int wg_env = -1;
       if (wg_env < 0) { const char* e = getenv("KF_SDF_LOOP_WG"); wg_env = e ? atoi(e) : 0; }
@@ -1892,15 +1743,10 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
       n_loop = n_loop > KF_ICP_LOOP_MAX_WG ? KF_ICP_LOOP_MAX_WG : n_loop;
       const int need = kf_div_up(kf_div_up(c->cols, 8) * kf_div_up(c->rows, 8), SDF_THREADS / 64);
       if (n_loop > need) n_loop = need;
-      SdfLoopArgs L; memset(&L, 0, sizeof(L));
       L.vol = c->vol; L.depth = c->trunced_depth; L.cam = to_cam(cam); L.max_iter = (int)sp->max_iter_nums;
-      { TrackArgs th; set_thresholds(th, 0.f, 0.f, sp->dist_shake, sp->angle_shake);
-        L.dist_shake = th.dist_shake; L.angle_shake = th.angle_shake; L.cos_shake = th.cos_shake; L.dist_shake2 = th.dist_shake2; }
-      c->icp_loop_seq += 64u;
-      L.slots = c->icp_loop_slots; L.tag_base = c->icp_loop_seq; L.track = c->track; L.stall_word = stall_word;
+      L.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
       const int n_tiles = kf_div_up(c->cols, 8) * kf_div_up(c->rows, 8);      // 8x8 pixel tiles, one per wave and round
       L.n_loop = n_loop; L.px_l = kf_div_up(n_tiles, (SDF_THREADS / 64) * n_loop);
-      if (c->inject_stall > 0) { L.play_dead = 1; --c->inject_stall; }
       if (kf_arm_tail_cull(c, cam, n_loop, SDF_THREADS / 64, L.cull)) L.cull_on = 1;
       if (buf) hipLaunchKernelGGL(k_sdf_loop<SdfBufAddr>, dim3((unsigned)n_loop), dim3(SDF_THREADS), 0, c->stream, L);
       else hipLaunchKernelGGL(k_sdf_loop<SdfFlatAddr>, dim3((unsigned)n_loop), dim3(SDF_THREADS), 0, c->stream, L);
@@ -1909,11 +1755,11 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
       return (int)hipGetLastError();
     }
   }
-  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 1, c->grid_barrier);
+  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 1);
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.use_state = 1; a.sdf = 1;
   a.cam = to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
-  set_thresholds(a, 0.f, 0.f, sp->dist_shake, sp->angle_shake);
+  a.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   const int grid = track_grid(c->cols * c->rows);
   int step = 0;
@@ -1940,7 +1786,7 @@ extern "C" int kf_sdf_partition_begin(kf_ctx* c, uint32_t frame_id) {
   { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
   c->last_track_form = 0;
   if (frame_id != 0) kf_evt_begin(c, KF_STAGE_TRACK);       // (ends in kf_sdf_partition_finish: the caller's all-reduces are inside)
-  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, frame_id == 0 ? 0 : 1, c->grid_barrier);
+  hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, frame_id == 0 ? 0 : 1);
   return (int)hipGetLastError();
 }
 static int sdf_partition_args(kf_ctx* c, const kf_sdf_tracker_params* sp, const kf_camera_params* cam, TrackArgs& a) {
@@ -1953,7 +1799,7 @@ static int sdf_partition_args(kf_ctx* c, const kf_sdf_tracker_params* sp, const 
   memset(&a, 0, sizeof(a));
   a.use_state = 1; a.sdf = 1; a.slab_pixels = 1;
   a.cam = to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
-  set_thresholds(a, 0.f, 0.f, sp->dist_shake, sp->angle_shake);
+  a.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   return 0;
 }

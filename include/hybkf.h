@@ -76,7 +76,8 @@ typedef struct kf_track_result {
   int32_t  launch_form;     /* how the last kf_icp_track / kf_sdf_track call was launched: 0 none (frame 0), 1 persistent device loop, 2 one launch per
                              * Gauss-Newton step / iteration (GPU shared, a second context, after a stall), 3 persistent loop that timed
                              * out waiting for a workgroup that was not resident and was finished by one workgroup alone (the frame is kept,
-                             * milliseconds late); the same pose bits in every form */
+                             * milliseconds late).  ICP: the same pose bits in every form.  SDF: forms 1 and 3 give the same bits, form 2
+                             * agrees with them to tolerance only (it deals pixels and maps the increment differently) */
 } kf_track_result;
 
 typedef struct kf_volume_stats {
