@@ -222,6 +222,7 @@ struct kf_ctx {
   unsigned* mc_block_counts; size_t mc_blocks_cap;
   unsigned* mc_list; unsigned* mc_nbr_bits; unsigned* mc_partials;   // extraction scratch, allocated by the first kf_marching_cubes
   unsigned short* mc_codes; unsigned char* mc_surv; unsigned* mc_block_bits; uint2* mc_recs; unsigned* mc_d1_list;   // voxel classes, sieve bits, cell records, brick list (mcubes.hip), same scratch
+  struct KfWeld* weld;           // scratch and indexed mesh of kf_weld_mesh (weld.hip), allocated by the first weld
   unsigned long long* layer_work; int layer_work_frames;   // per-brick-layer update counts of the next `layer_work_frames` integrate calls (kf_count_layer_work)
   int defer_override;            // kf_set_defer: -1 follow the environment (default), 0 never defer, 1 defer
   kf_fusion_form fusion_form;    // what the last kf_integrate_volume launched (kf_get_fusion_form)
@@ -615,4 +616,5 @@ int kf_device_shared(int device);
 int kf_materialize_raw_depth(kf_ctx* ctx);
 int kf_pending_depth_consumed(kf_ctx* ctx);
 int kf_tail_cull_discard(kf_ctx* ctx);   // a cull that ran as the tail of a tracking launch and will not be consumed: its queue counter back to zero
+void kf_weld_free(kf_ctx* ctx);          // (weld.hip) what kf_weld_release frees, for kf_destroy: the caller has synchronised the stream
 int kf_upload_wait_for(kf_ctx* ctx, const uint16_t* dev_mm);   // dev_mm is about to be read on the context's stream: wait for its staged copy, if it is one

@@ -17,6 +17,7 @@
 // The triangle table is packed into 256 x 64-bit words (16 nibbles per case) instead of the reference's 16 KiB int table; the
 // 12-bit edge mask is derived from it.
 #include "kf_internal.h"
+#include "scan.h"
 
 __constant__ unsigned long long c_tri_words[256] = {
 #include "mc_tables.inc"
@@ -46,7 +47,7 @@ struct McArgs {
   unsigned* recs_overflow;
   unsigned recs_cap;
 };
-#define MC_CHUNK 4096u             // block counts scanned by one workgroup (16 per lane)
+#define MC_CHUNK KF_SCAN_CHUNK     // block counts scanned by one workgroup (scan.h)
 
 __device__ __forceinline__ float sel8(const float d[8], int k) {
   float r = d[0];
@@ -396,20 +397,6 @@ __device__ __forceinline__ bool mc_cell_of(const McArgs& a, unsigned blk, unsign
   return true;
 }
 
-// workgroup-wide exclusive prefix of one value per lane (256 lanes); s_wave: 4 words; the trailing barrier frees s_wave again
-__device__ __forceinline__ unsigned mc_block_excl_scan(unsigned local, unsigned* s_wave, unsigned& total) {
-  unsigned inc = local;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) { const unsigned t = __shfl_up(inc, off, 64); if ((threadIdx.x & 63) >= (unsigned)off) inc += t; }
-  if ((threadIdx.x & 63) == 63) s_wave[threadIdx.x >> 6] = inc;
-  __syncthreads();
-  unsigned wave_off = 0;
-  for (int w = 0; w < (int)(threadIdx.x >> 6); ++w) wave_off += s_wave[w];
-  total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-  __syncthreads();
-  return wave_off + inc - local;
-}
-
 // count pass: persistent workgroups take MC_BATCH listed blocks at a time.  The surviving cells of the whole batch -- a few per
 // block where the surface crosses the x-rows, all 256 where it runs along them -- are queued in LDS in (block, x) order, one lane
 // per sieve BYTE (eight cells) doing the queueing, and evaluated by dense waves; a prefix over the queue gives every cell with
@@ -445,7 +432,7 @@ __global__ void __launch_bounds__(256) MC_COUNT_ATTR k_mc_count(McArgs a) {
 #pragma unroll
     for (unsigned p = 0; p < MC_BATCH / 8; ++p) {                                // queue positions: blocks in batch order, cells in x order
       unsigned total;
-      unsigned at = nq + mc_block_excl_scan((unsigned)__popc(sv[p]), s_wave, total);
+      unsigned at = nq + kf_block_excl_scan((unsigned)__popc(sv[p]), s_wave, total);
       if ((threadIdx.x & 31u) == 0) s_qstart[p * 8u + (threadIdx.x >> 5)] = at;
       const unsigned q0 = ((p * 8u + (threadIdx.x >> 5)) << 8) | (8u * (threadIdx.x & 31u));
       for (unsigned m = sv[p]; m; m &= m - 1u) s_q[at++] = (unsigned short)(q0 + (unsigned)__builtin_ctz(m));
@@ -465,7 +452,7 @@ __global__ void __launch_bounds__(256) MC_COUNT_ATTR k_mc_count(McArgs a) {
         n = eval_cell(a, cx, cy, cz, e);
       }
       unsigned total;
-      const unsigned excl = carry + mc_block_excl_scan((unsigned)n, s_wave, total);
+      const unsigned excl = carry + kf_block_excl_scan((unsigned)n, s_wave, total);
       if (i < nq && i == s_qstart[b]) s_bstart[b] = excl;                        // the prefix at the block's first queued cell
       __syncthreads();
       const unsigned long long m = __ballot(n > 0);
@@ -483,53 +470,6 @@ __global__ void __launch_bounds__(256) MC_COUNT_ATTR k_mc_count(McArgs a) {
     if (threadIdx.x < nbat) a.block_counts[a.list[base + threadIdx.x]] = s_cnt[threadIdx.x];
     __syncthreads();
   }
-}
-
-// ---- exclusive prefix sum of the block counts, in place, in three parallel steps ----------------------------------------------
-// (1) every workgroup sums its chunk of MC_CHUNK counts; (2) one workgroup turns the chunk sums into their exclusive prefix (a
-// few thousand values even at 2048^3); (3) every workgroup rescans its chunk on top of its offset.  total -> counts[n].
-__global__ void __launch_bounds__(256) k_mc_scan_reduce(const unsigned* __restrict__ counts, unsigned n, unsigned* __restrict__ partials) {
-  __shared__ unsigned s_wave[4];
-  const unsigned i0 = blockIdx.x * MC_CHUNK + threadIdx.x * 16u;
-  unsigned local = 0;
-  if (i0 + 16u <= n) {
-    const uint4* p = reinterpret_cast<const uint4*>(counts + i0);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { const uint4 q = p[k]; local += q.x + q.y + q.z + q.w; }
-  } else for (unsigned k = 0; k < 16u; ++k) if (i0 + k < n) local += counts[i0 + k];
-  unsigned total;
-  mc_block_excl_scan(local, s_wave, total);
-  if (threadIdx.x == 0) partials[blockIdx.x] = total;
-}
-__global__ void __launch_bounds__(256) k_mc_scan_partials(unsigned* partials, unsigned n_chunks, unsigned* counts, unsigned n, KfCounters* cnt) {
-  __shared__ unsigned s_wave[4]; __shared__ unsigned s_carry;
-  if (threadIdx.x == 0) s_carry = 0;
-  __syncthreads();
-  for (unsigned base = 0; base < n_chunks; base += 1024u) {
-    const unsigned i0 = base + threadIdx.x * 4u;
-    unsigned v[4]; unsigned local = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { v[k] = (i0 + k < n_chunks) ? partials[i0 + k] : 0u; local += v[k]; }
-    unsigned total;
-    unsigned excl = s_carry + mc_block_excl_scan(local, s_wave, total);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { if (i0 + k < n_chunks) partials[i0 + k] = excl; excl += v[k]; }
-    __syncthreads();
-    if (threadIdx.x == 0) s_carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { counts[n] = s_carry; cnt->scan_total = s_carry; }
-}
-__global__ void __launch_bounds__(256) k_mc_scan_apply(unsigned* __restrict__ counts, unsigned n, const unsigned* __restrict__ partials) {
-  __shared__ unsigned s_wave[4];
-  const unsigned i0 = blockIdx.x * MC_CHUNK + threadIdx.x * 16u;
-  unsigned v[16]; unsigned local = 0;
-#pragma unroll
-  for (int k = 0; k < 16; ++k) { v[k] = (i0 + k < n) ? counts[i0 + k] : 0u; local += v[k]; }
-  unsigned total;
-  unsigned excl = partials[blockIdx.x] + mc_block_excl_scan(local, s_wave, total);
-#pragma unroll
-  for (int k = 0; k < 16; ++k) { if (i0 + k < n) counts[i0 + k] = excl; excl += v[k]; }
 }
 
 // triangles of an evaluated cell -> fixed positions start, start + 1, ... (marchingcube.cu:28-38, :129-136)
@@ -593,7 +533,7 @@ __global__ void __launch_bounds__(256) k_mc_emit(McArgs a) {
       n = eval_cell(a, cx, cy, cz, e);
     }
     unsigned total;
-    const unsigned off0 = mc_block_excl_scan((unsigned)n, s_wave, total);
+    const unsigned off0 = kf_block_excl_scan((unsigned)n, s_wave, total);
     mc_write_triangles(a, e, n, a.cnt->n_triangles + my_base + off0);
   }
 }
@@ -614,7 +554,6 @@ extern "C" int kf_marching_cubes(kf_ctx* c, int has_color, float thr) {
   const size_t n_cells = (size_t)(a.z1 - a.z0) * c->vol.res * c->vol.res;
   a.n_blocks = (unsigned)((n_cells + 255) / 256);
   if (a.n_blocks > c->mc_blocks_cap) return KF_ERR_STATE;
-  const unsigned n_chunks = (a.n_blocks + MC_CHUNK - 1) / MC_CHUNK;
   if (!c->mc_list) {                                       // extraction scratch: allocated by the first extraction, not by every context
     KF_CHECK(hipSetDevice(c->cfg.device));                 // (per 4-KiB brick: 128 B of voxel classes + 64 B of sieve bits + 8 B of row bits)
     // all or nothing: the pointers are committed to the context only once every allocation has succeeded (at 2048^3 the scratch is
@@ -662,9 +601,7 @@ extern "C" int kf_marching_cubes(kf_ctx* c, int has_color, float thr) {
   const unsigned lgx = list_wgs < 65535u ? list_wgs : 65535u, lgy = (list_wgs + lgx - 1) / lgx;
   hipLaunchKernelGGL(k_mc_list, dim3(lgx, lgy), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(k_mc_count, dim3(walk), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(k_mc_scan_reduce, dim3(n_chunks), dim3(256), 0, c->stream, a.block_counts, a.n_blocks, a.partials);
-  hipLaunchKernelGGL(k_mc_scan_partials, dim3(1), dim3(256), 0, c->stream, a.partials, n_chunks, a.block_counts, a.n_blocks, c->counters);
-  hipLaunchKernelGGL(k_mc_scan_apply, dim3(n_chunks), dim3(256), 0, c->stream, a.block_counts, a.n_blocks, a.partials);
+  kf_scan_in_place(a.block_counts, a.n_blocks, a.partials, &c->counters->scan_total, c->stream);   // scan.h: reduce / partials / apply
   hipLaunchKernelGGL(k_mc_emit_recs, dim3(walk), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(k_mc_emit, dim3(walk), dim3(256), 0, c->stream, a);              // returns at once unless the record list overflowed
   hipLaunchKernelGGL(k_mc_finish, dim3(1), dim3(64), 0, c->stream, c->counters, c->max_triangles);

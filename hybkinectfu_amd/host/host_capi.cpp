@@ -92,6 +92,8 @@ int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_fa
   if (n_faces) *n_faces = (unsigned)(g_mesh->mesh().faces.size() / 3);
   return ok ? 1 : 0;
 }
+// MeshGeneratorMarchingcube::setDeviceWeld: the application's saveMesh welds on the device from now on (0: on the host again)
+int hkf_app_set_device_weld(int on) { if (!g_mesh) return -1; g_mesh->setDeviceWeld(on != 0); return 0; }
 
 // ---- GPU-free mesh post-processing on a caller-supplied triangle soup (kf_triangle layout) ---------------------------------------
 static MeshGeneratorMarchingcube* g_soup = nullptr;

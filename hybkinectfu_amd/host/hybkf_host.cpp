@@ -545,9 +545,24 @@ void MeshGeneratorMarchingcube::weldMesh() {                    // :69-84
   _meshes.removeDuplicateFaces();
   _meshes.computeVertexNormals();
 }
+bool MeshGeneratorMarchingcube::weldOnDevice() {                // :69-86 as kf_weld_mesh; false (mesh untouched) when there is nothing to weld or the device refuses
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (!dm->ctx() || triangleCount() == 0) return false;
+  const bool col = AppParams::instance()->_switch_params.useRGBData;
+  uint32_t nv = 0, nf = 0;
+  if (kf_weld_mesh(dm->ctx(), col, 0.0001f) != 0 || kf_mesh_counts(dm->ctx(), &nv, &nf, nullptr) != 0) return false;
+  MeshData m;
+  m.vertices.resize((size_t)nv * 3); m.normals.resize((size_t)nv * 3); m.faces.resize((size_t)nf * 3);
+  if (col) m.colors.resize((size_t)nv * 4);
+  if (kf_read_mesh(dm->ctx(), m.vertices.data(), m.normals.data(), col ? m.colors.data() : nullptr, m.faces.data()) != 0) return false;
+  _meshes = std::move(m);
+  return true;
+}
 bool MeshGeneratorMarchingcube::saveMesh(const std::string& filename) {   // :61-96
-  if (!copyTrianglesToCPU()) return false;
-  weldMesh();
+  if (!_device_weld || !weldOnDevice()) {
+    if (!copyTrianglesToCPU()) return false;
+    weldMesh();
+  }
   // the reference returns 0 here even on success (:95); we report whether the file was written
   return _meshes.saveToFile(filename);
 }

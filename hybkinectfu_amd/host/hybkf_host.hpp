@@ -264,7 +264,13 @@ public:
   // against the reference's own ml::MeshData, tests/golden/mesh_*.npz)
   void setTriangles(const kf_triangle* tris, unsigned n, bool with_color);   // :39-58
   void weldMesh();                                                           // :69-84 index buffer, weld, dedupe, normals
+  // saveMesh welds on the device (kf_weld_mesh: the same mesh, bit for bit) and reads the indexed mesh back instead of the soup.
+  // Off by default; if the device weld fails, saveMesh welds on the host as before.
+  void setDeviceWeld(bool on) { _device_weld = on; }
+  bool deviceWeld() const { return _device_weld; }
 protected:
   bool copyTrianglesToCPU();
+  bool weldOnDevice();                                                       // :61-86 without the 72 bytes per triangle crossing to the host
   MeshData _meshes;
+  bool _device_weld = false;
 };

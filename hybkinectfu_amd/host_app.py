@@ -74,6 +74,11 @@ class App:
         ok = self.h.hkf_app_save_mesh(filename.encode(), C.byref(nv), C.byref(nf))
         return bool(ok), nv.value, nf.value
 
+    def set_device_weld(self, on=True):
+        """save_mesh welds on the device (kf_weld_mesh) instead of on one host thread; same mesh, same files.  Default off."""
+        if self.h.hkf_app_set_device_weld(int(bool(on))) != 0:
+            raise K.KfError("hkf_app_set_device_weld: no application")
+
     def close(self):
         self.h.hkf_app_shutdown()
 

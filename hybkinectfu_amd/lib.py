@@ -110,6 +110,7 @@ SYMBOLS = [
     "kf_download_volume_device", "kf_upload_volume_device", "kf_resize_slab", "kf_count_layer_work", "kf_read_layer_work",
     "kf_upload_depth_mm_next", "kf_take_next_depth", "kf_cull_tail_counts", "kf_count_observed_voxels", "kf_get_fusion_counters",
     "kf_get_fusion_form", "kf_get_raycast_form",
+    "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
 ]
 
 
@@ -443,6 +444,34 @@ class Context:
         if n.value:
             _chk(self.lib.kf_read_triangles(self.h, _p(out), 0, n.value), "kf_read_triangles")
         return out
+
+    def write_triangles(self, tris, first=0):
+        """host triangles (lib.TRI_DTYPE) into the buffer at `first`; the triangle count becomes first + len(tris)"""
+        tris = np.ascontiguousarray(tris)
+        assert tris.dtype.itemsize == 72
+        _chk(self.lib.kf_write_triangles(self.h, _p(tris), int(first), len(tris)), "kf_write_triangles")
+
+    def weld_mesh(self, has_color=False, thresh=1e-4):
+        """the buffer's triangles welded into an indexed mesh on the device (what saveMesh's host weld makes of them, bit for bit)"""
+        _chk(self.lib.kf_weld_mesh(self.h, int(has_color), C.c_float(thresh)), "kf_weld_mesh")
+
+    def mesh_counts(self):
+        """(vertices, faces, rounds of the cell selection) of the last weld_mesh"""
+        nv, nf, nr = C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_mesh_counts(self.h, C.byref(nv), C.byref(nf), C.byref(nr)), "kf_mesh_counts")
+        return nv.value, nf.value, nr.value
+
+    def read_mesh(self, with_color=False):
+        """the last weld_mesh's mesh: dict of vertices / normals (n, 3) f32, colors (n, 4) f32 -- (0, 4) without colour --, faces (m, 3) u32"""
+        nv, nf, _ = self.mesh_counts()
+        v, n = np.empty((nv, 3), np.float32), np.empty((nv, 3), np.float32)
+        c = np.empty((nv if with_color else 0, 4), np.float32)
+        f = np.empty((nf, 3), np.uint32)
+        _chk(self.lib.kf_read_mesh(self.h, _p(v), _p(n), _p(c) if with_color else None, _p(f)), "kf_read_mesh")
+        return dict(vertices=v, normals=n, colors=c, faces=f)
+
+    def weld_release(self):
+        _chk(self.lib.kf_weld_release(self.h), "kf_weld_release")
 
     def download_volume(self, z0=None, z1=None, color=False):
         z0 = self.stored[0] if z0 is None else z0

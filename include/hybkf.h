@@ -298,6 +298,29 @@ int kf_marching_cubes(kf_ctx* ctx, int has_color, float threshold_marchingcube);
 int kf_clear_triangles(kf_ctx* ctx);                                   /* MarchingcubeData::clearData */
 int kf_triangle_count(kf_ctx* ctx, uint32_t* count);                   /* MarchingcubeData::triangleNums, blocking */
 int kf_read_triangles(kf_ctx* ctx, kf_triangle* dst, uint32_t first, uint32_t count);   /* MarchingcubeData::clone(CPU) */
+/* the counterpart of kf_read_triangles (MarchingcubeData::clone towards the device, src/cuda/MarchingcubeData.h:129): host triangles into
+ * [first, first + count) of the buffer; the triangle count becomes first + count.  KF_ERR_ARG beyond max_triangles.  Blocking.
+ * What welds a soup that did not come from this context's volume. */
+int kf_write_triangles(kf_ctx* ctx, const kf_triangle* src, uint32_t first, uint32_t count);
+
+/* The indexed mesh of the triangles in the buffer, made on the device: what MeshGeneratorMarchingcube::saveMesh does on one host thread
+ * between its copy and its file writer (src/MeshGeneratorMarchingcube.cpp:69-86) -- MeshData::mergeCloseVertices(thresh, approx)
+ * with its closing removeDegeneratedFaces (src/utils/mesh/meshData.cpp:179-310), removeDuplicateFaces (:42-82) and
+ * computeVertexNormals (src/utils/mesh/meshData.h:713-736).  Same vertices, face indices and normals, bit for bit, whatever the
+ * scheduling.  The reference welds with thresh = 0.0001f.  The soup is only read: kf_read_triangles returns it unchanged afterwards.
+ * Scratch and mesh live in the context: allocated on the call, kept for the next one, freed by kf_weld_release / kf_destroy.
+ * KF_ERR_ARG: thresh <= 0, more than 2^32 / 3 triangles.  KF_ERR_ALLOC: no memory for the scratch (also above ~357 M triangles).  An
+ * empty buffer gives an empty mesh.  Blocks a few times on a 4-byte read-back (one per round of the cell selection, see n_rounds). */
+int kf_weld_mesh(kf_ctx* ctx, int has_color, float thresh);
+/* sizes of the last kf_weld_mesh's mesh and the rounds its cell selection took (1 - 3 on real soups); KF_ERR_STATE before a weld.  Blocking.
+ * (the sizes of MeshData's m_Vertices and m_FaceIndicesVertices, src/utils/mesh/meshData.h:561-569) */
+int kf_mesh_counts(kf_ctx* ctx, uint32_t* n_vertices, uint32_t* n_faces, uint32_t* n_rounds);
+/* the mesh itself (MeshData's m_Vertices, m_Normals, m_Colors, m_FaceIndicesVertices, src/utils/mesh/meshData.h:561-569, as MeshGeneratorMarchingcube.cpp:39-58 fills them):
+ * vertices / normals 3 floats, colours 4 floats (rgba: the triangle's colour with x and z swapped, a = 1, :53; written only after a weld
+ * with has_color), faces 3 indices each.  Any pointer may be NULL.  KF_ERR_STATE before a weld.  Blocking. */
+int kf_read_mesh(kf_ctx* ctx, float* vertices, float* normals, float* colors, uint32_t* faces);
+/* frees the weld's scratch and mesh (MeshData::clear, src/utils/mesh/meshData.h:440); the next kf_weld_mesh allocates again */
+int kf_weld_release(kf_ctx* ctx);
 
 /* CudaMap2D::clone(CPU) / copyDataFrom on the singleton's maps (debug + parity; blocking) */
 int kf_download_map(kf_ctx* ctx, int map_id, uint32_t level, void* dst, size_t dst_bytes);
