@@ -419,6 +419,14 @@ extern "C" int kf_upload_rgb(kf_ctx* c, const uint8_t* host_bgr, uint32_t cols, 
   return (int)hipGetLastError();
 }
 
+// the counterpart of kf_set_depth_mm_device: a BGR frame (3 bytes per pixel) that is already in HBM -- widened into raw_rgb where the stream stands
+extern "C" int kf_set_rgb_device(kf_ctx* c, const uint8_t* dev_bgr, uint32_t cols, uint32_t rows) {
+  if (!c || !dev_bgr || !c->raw_rgb || cols != c->cfg.rgb_camera.cols || rows != c->cfg.rgb_camera.rows) return KF_ERR_ARG;
+  const size_t n = (size_t)cols * rows;
+  hipLaunchKernelGGL(k_rgb3_to_rgb4, dim3(kf_div_up((int)n, 256)), dim3(256), 0, c->stream, dev_bgr, c->raw_rgb, (int)n);
+  return (int)hipGetLastError();
+}
+
 // ---- map download / upload (CudaMap2D::clone(CPU), DataMap.h) -----------------------------------------------------
 static int map_ptr(kf_ctx* c, int id, uint32_t level, void** p, size_t* bytes, bool* is_rgb) {
   *is_rgb = false;

@@ -45,7 +45,8 @@ __global__ void __launch_bounds__(KF_GROUP_BLOCK) k_group_min_u64(GroupReduceArg
   }
 }
 
-// normal candidates: exactly one member contributes non-zero bits per pixel, so the integer sum is that member's bits (-0.0 included)
+// normal candidates (3 words per pixel; a colour group: 4, the colour word last): exactly one member contributes non-zero bits per pixel, so the integer
+// sum is that member's bits (-0.0 included).  The kernel reduces a flat run of words: nothing in it knows the stride
 template <int M>
 __global__ void __launch_bounds__(KF_GROUP_BLOCK) k_group_sum_u32(GroupReduceArgs a) {
   const unsigned stride = gridDim.x * KF_GROUP_BLOCK;
@@ -104,6 +105,12 @@ struct kf_group {
   float* spec[KF_GROUP_MAX_MEMBERS] = {};
   float* cand[KF_GROUP_MAX_MEMBERS] = {};
   uint16_t* depth[KF_GROUP_MAX_MEMBERS] = {};
+  // a colour group (kf_group_create_color): speculation and candidates carry 4 words per pixel, members integrate / extract with colour, and a
+  // host-fed frame's BGR image has a buffer per device like the depth frame
+  bool color = false;
+  int angle_weight = 0;
+  uint32_t words = 3;
+  uint8_t* rgb[KF_GROUP_MAX_MEMBERS] = {};
   // LOCAL: the group stream and the two group buffers every member reads after a reduction
   hipStream_t stream = nullptr;
   uint64_t* ta_min = nullptr;
@@ -134,7 +141,7 @@ uint32_t needed_halo(const kf_config* base, const kf_group_params* p) {
 }
 
 int validate(const kf_config* base, const kf_group_params* p, int backend, uint32_t members, const uint32_t* z_cuts, const int32_t* devices,
-             uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world) {
+             uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world, bool color) {
   if (!base || !p || !z_cuts) return KF_GROUP_ERR_ARG;
   if (members < 1 || members > KF_GROUP_MAX_MEMBERS) return KF_GROUP_ERR_ARG;
   if (backend != KF_GROUP_LOCAL && backend != KF_GROUP_RCCL_ALL && backend != KF_GROUP_RCCL_RANK) return KF_GROUP_ERR_ARG;
@@ -154,7 +161,7 @@ int validate(const kf_config* base, const kf_group_params* p, int backend, uint3
       if (z_cuts[i + 1] <= z_cuts[i] || z_cuts[i + 1] % 8) return KF_GROUP_ERR_ARG;
   }
   if (halo != 0 && halo < needed_halo(base, p)) return KF_GROUP_ERR_ARG;
-  if (base->has_color) return KF_GROUP_ERR_ARG;
+  if (color ? (base->has_color != 1 || base->rgb_camera.cols == 0 || base->rgb_camera.rows == 0) : base->has_color != 0) return KF_GROUP_ERR_ARG;
   if (base->depth_camera.cols == 0 || base->depth_camera.rows == 0) return KF_GROUP_ERR_ARG;
   for (uint32_t i = 0; i < members; ++i) {
     const int32_t di = devices ? devices[i] : base->device;
@@ -179,7 +186,7 @@ void release(kf_group* g) {
     hipSetDevice(g->dev[i]);
     if (g->comm[i]) ncclCommDestroy(g->comm[i]);
     if (g->m[i]) kf_destroy(g->m[i]);            // (a member on the group stream returns to its own stream first)
-    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i]};
+    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i], g->rgb[i]};
     for (void* b : bufs) if (b) hipFree(b);
   }
   if (g->n) hipSetDevice(g->dev[0]);
@@ -208,10 +215,12 @@ int build(kf_group* g, const uint8_t* unique_id) {
     if ((st = kf_create(&c, &g->m[i]))) return st;
     if ((st = hipSetDevice(g->dev[i]))) return st;
     if ((st = group_alloc((void**)&g->ta[i], npx * 8))) return st;
-    if ((st = group_alloc((void**)&g->spec[i], npx * 12))) return st;
-    if ((st = group_alloc((void**)&g->cand[i], npx * 12))) return st;
+    if ((st = group_alloc((void**)&g->spec[i], npx * 4 * g->words))) return st;
+    if ((st = group_alloc((void**)&g->cand[i], npx * 4 * g->words))) return st;
     if (g->backend != KF_GROUP_LOCAL && (st = group_alloc((void**)&g->ta_own[i], npx * 8))) return st;
     if ((g->backend != KF_GROUP_LOCAL || i == 0) && (st = group_alloc((void**)&g->depth[i], npx * 2))) return st;
+    if (g->color && (g->backend != KF_GROUP_LOCAL || i == 0) &&
+        (st = group_alloc((void**)&g->rgb[i], (size_t)g->base.rgb_camera.cols * g->base.rgb_camera.rows * 3))) return st;
     kf_mat44 pose0;                                   // HybKinectfu::init: identity, camera at the centre of the front face, trunc_min in front of it
     memset(&pose0, 0, sizeof(pose0));
     pose0.m[0] = pose0.m[5] = pose0.m[10] = pose0.m[15] = 1.f;
@@ -224,7 +233,7 @@ int build(kf_group* g, const uint8_t* unique_id) {
     if ((st = (int)hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking))) return st;
     for (uint32_t i = 0; i < g->n; ++i) if ((st = kf_set_stream(g->m[i], g->stream))) return st;   // one stream: ordering is implicit
     if ((st = group_alloc((void**)&g->ta_min, npx * 8))) return st;
-    if ((st = group_alloc((void**)&g->cand_sum, npx * 12))) return st;
+    if ((st = group_alloc((void**)&g->cand_sum, npx * 4 * g->words))) return st;
     int cus = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, g->dev[0]) != hipSuccess || cus <= 0) cus = 256;
     g->grid = 4 * cus;
@@ -238,7 +247,7 @@ int reduce_local(kf_group* g, bool words) {
   memset(&a, 0, sizeof(a));
   for (uint32_t i = 0; i < g->n; ++i) a.src[i] = words ? (const void*)g->ta[i] : (const void*)g->cand[i];
   a.dst = words ? (void*)g->ta_min : (void*)g->cand_sum;
-  const size_t elems = words ? npx : 3 * npx, per16 = words ? 2 : 4;
+  const size_t elems = words ? npx : g->words * npx, per16 = words ? 2 : 4;
   a.n16 = (unsigned)(elems / per16);
   a.tail = (unsigned)(elems % per16);
   const unsigned need = (a.n16 + KF_GROUP_BLOCK - 1) / KF_GROUP_BLOCK;
@@ -248,9 +257,19 @@ int reduce_local(kf_group* g, bool words) {
   return (int)hipGetLastError();
 }
 
+// steps 7 and 9 of the frame in the group's kind: the colour forms carry the fourth word
+int member_normals(kf_group* g, uint32_t i, const uint64_t* ta_min, const uint64_t* ta_own) {
+  const kf_group_params& p = g->p;
+  return g->color ? kf_slab_ray_normals_color(g->m[i], nullptr, &p.raycast, &g->base.depth_camera, p.trunc_min, p.trunc_max, ta_min, ta_own, g->spec[i], g->cand[i])
+                  : kf_slab_ray_normals_spec(g->m[i], nullptr, &p.raycast, &g->base.depth_camera, p.trunc_min, p.trunc_max, ta_min, ta_own, g->spec[i], g->cand[i]);
+}
+int member_maps(kf_group* g, uint32_t i, const uint64_t* ta_min, const float* cand) {
+  return g->color ? kf_set_model_maps_rays_color(g->m[i], nullptr, &g->base.depth_camera, ta_min, cand)
+                  : kf_set_model_maps_rays(g->m[i], nullptr, &g->base.depth_camera, ta_min, cand);
+}
+
 // steps 6-9 of the frame
 int merge(kf_group* g) {
-  const kf_group_params& p = g->p;
   const kf_camera_params* cam = &g->base.depth_camera;
   const uint32_t n = g->n;
   const size_t npx = (size_t)cam->cols * cam->rows;
@@ -258,10 +277,10 @@ int merge(kf_group* g) {
   if (g->backend == KF_GROUP_LOCAL) {
     if ((st = reduce_local(g, true))) return st;
     for (uint32_t i = 0; i < n; ++i)
-      if ((st = kf_slab_ray_normals_spec(g->m[i], nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta_min, g->ta[i], g->spec[i], g->cand[i]))) return st;
+      if ((st = member_normals(g, i, g->ta_min, g->ta[i]))) return st;
     if ((st = reduce_local(g, false))) return st;
     for (uint32_t i = 0; i < n; ++i)
-      if ((st = kf_set_model_maps_rays(g->m[i], nullptr, cam, g->ta_min, g->cand_sum))) return st;
+      if ((st = member_maps(g, i, g->ta_min, g->cand_sum))) return st;
     return 0;
   }
   if ((st = nccl_status(ncclGroupStart()))) return st;
@@ -271,24 +290,27 @@ int merge(kf_group* g) {
   if (st || st_end) return st ? st : st_end;
   for (uint32_t i = 0; i < n; ++i) {
     if ((st = hipSetDevice(g->dev[i]))) return st;
-    if ((st = kf_slab_ray_normals_spec(g->m[i], nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], g->ta_own[i], g->spec[i], g->cand[i]))) return st;
+    if ((st = member_normals(g, i, g->ta[i], g->ta_own[i]))) return st;
   }
   if ((st = nccl_status(ncclGroupStart()))) return st;
   for (uint32_t i = 0; i < n && !st; ++i)
-    st = nccl_status(ncclAllReduce(g->cand[i], g->cand[i], 3 * npx, ncclInt32, ncclSum, g->comm[i], member_stream(g, i)));
+    st = nccl_status(ncclAllReduce(g->cand[i], g->cand[i], g->words * npx, ncclInt32, ncclSum, g->comm[i], member_stream(g, i)));
   const int st_end2 = nccl_status(ncclGroupEnd());
   if (st || st_end2) return st ? st : st_end2;
   for (uint32_t i = 0; i < n; ++i) {
     if ((st = hipSetDevice(g->dev[i]))) return st;
-    if ((st = kf_set_model_maps_rays(g->m[i], nullptr, cam, g->ta[i], g->cand[i]))) return st;
+    if ((st = member_maps(g, i, g->ta[i], g->cand[i]))) return st;
   }
   return 0;
 }
 
-int frame(kf_group* g, const uint16_t* const* dev_mm, const uint16_t* host_mm, uint32_t frame_id) {
+// dev_bgr / host_bgr: a colour group's BGR frame, where the depth frame lies (both null for a colourless group)
+int frame(kf_group* g, const uint16_t* const* dev_mm, const uint16_t* host_mm, uint32_t frame_id, const uint8_t* const* dev_bgr = nullptr,
+          const uint8_t* host_bgr = nullptr) {
   const kf_group_params& p = g->p;
   const kf_camera_params* cam = &g->base.depth_camera;
-  const size_t bytes = (size_t)cam->cols * cam->rows * sizeof(uint16_t);
+  const kf_camera_params* rcam = &g->base.rgb_camera;
+  const size_t bytes = (size_t)cam->cols * cam->rows * sizeof(uint16_t), rgb_bytes = (size_t)rcam->cols * rcam->rows * 3;
   int st = 0;
   for (uint32_t i = 0; i < g->n; ++i) {
     kf_ctx* c = g->m[i];
@@ -300,11 +322,25 @@ int frame(kf_group* g, const uint16_t* const* dev_mm, const uint16_t* host_mm, u
       mm = g->depth[slot];
     }
     if ((st = kf_set_depth_mm_device(c, mm, cam->cols, cam->rows))) return st;
+    if (g->color) {
+      const uint8_t* bgr = dev_bgr ? dev_bgr[i] : nullptr;
+      if (host_bgr) {
+        const uint32_t slot = g->backend == KF_GROUP_LOCAL ? 0 : i;     // once per device
+        if (slot == i && (st = (int)hipMemcpyAsync(g->rgb[slot], host_bgr, rgb_bytes, hipMemcpyHostToDevice, member_stream(g, i)))) return st;
+        bgr = g->rgb[slot];
+      }
+      if ((st = kf_set_rgb_device(c, bgr, rcam->cols, rcam->rows))) return st;
+    }
     if ((st = kf_preprocess(c, p.trunc_min, p.trunc_max, p.sigma_pixel, p.sigma_depth, cam))) return st;
     if ((st = kf_icp_track(c, frame_id, &p.icp, cam))) return st;
-    if ((st = kf_integrate_volume(c, 0, 0, nullptr, &p.integrate, cam, cam))) return st;
-    if ((st = kf_raycast_volume_slab_cross_spec(c, nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i],
-                                                g->backend == KF_GROUP_LOCAL ? g->ta[i] : g->ta_own[i], g->spec[i]))) return st;
+    uint64_t* own = g->backend == KF_GROUP_LOCAL ? g->ta[i] : g->ta_own[i];
+    if (g->color) {
+      if ((st = kf_integrate_volume(c, 1, g->angle_weight, nullptr, &p.integrate, cam, rcam))) return st;
+      if ((st = kf_raycast_volume_slab_cross_spec_color(c, nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i]))) return st;
+    } else {
+      if ((st = kf_integrate_volume(c, 0, 0, nullptr, &p.integrate, cam, cam))) return st;
+      if ((st = kf_raycast_volume_slab_cross_spec(c, nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i]))) return st;
+    }
   }
   hipEvent_t e1 = nullptr;
   if (g->timing && g->ev_used < KF_GROUP_MAX_TIMED_FRAMES) {          // (a full pool: this frame's merge goes untimed until the next read)
@@ -345,19 +381,26 @@ int kf_group_unique_id(uint8_t out[128]) {
 
 int kf_group_validate(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
                       const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world) {
-  return validate(base, params, backend, members, z_cuts, devices, halo, unique_id, rank, world);
+  return validate(base, params, backend, members, z_cuts, devices, halo, unique_id, rank, world, false);
 }
 
-int kf_group_create(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
-                    const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world, kf_group** out) {
+int kf_group_validate_color(const kf_config* base, const kf_group_params* params, int use_angle_weight_color, int backend, uint32_t members,
+                            const uint32_t* z_cuts, const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world) {
+  (void)use_angle_weight_color;                          // any value is a valid switch
+  return validate(base, params, backend, members, z_cuts, devices, halo, unique_id, rank, world, true);
+}
+
+static int group_create(const kf_config* base, const kf_group_params* params, bool color, int use_angle_weight_color, int backend, uint32_t members,
+                        const uint32_t* z_cuts, const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world, kf_group** out) {
   if (!out) return KF_GROUP_ERR_ARG;
   *out = nullptr;
-  int st = validate(base, params, backend, members, z_cuts, devices, halo, unique_id, rank, world);
+  int st = validate(base, params, backend, members, z_cuts, devices, halo, unique_id, rank, world, color);
   if (st) return st;
   DeviceGuard guard;
   kf_group* g = new (std::nothrow) kf_group();
   if (!g) return KF_GROUP_ERR_ALLOC;
   g->backend = backend; g->n = members; g->base = *base; g->p = *params;
+  g->color = color; g->angle_weight = use_angle_weight_color ? 1 : 0; g->words = color ? 4 : 3;
   g->p.icp.pyramid_levels = base->pyramid_levels;
   g->halo = halo ? halo : needed_halo(base, params);
   g->rank = backend == KF_GROUP_RCCL_RANK ? rank : 0;
@@ -367,6 +410,17 @@ int kf_group_create(const kf_config* base, const kf_group_params* params, int ba
   if ((st = build(g, unique_id))) { release(g); delete g; return st; }
   *out = g;
   return 0;
+}
+
+int kf_group_create(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
+                    const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world, kf_group** out) {
+  return group_create(base, params, false, 0, backend, members, z_cuts, devices, halo, unique_id, rank, world, out);
+}
+
+int kf_group_create_color(const kf_config* base, const kf_group_params* params, int use_angle_weight_color, int backend, uint32_t members,
+                          const uint32_t* z_cuts, const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world,
+                          kf_group** out) {
+  return group_create(base, params, true, use_angle_weight_color, backend, members, z_cuts, devices, halo, unique_id, rank, world, out);
 }
 
 int kf_group_destroy(kf_group* g) {
@@ -386,7 +440,7 @@ int kf_group_members(kf_group* g, uint32_t* members, uint32_t* halo) {
 
 int kf_group_frame(kf_group* g, const uint16_t* mm, int on_device, uint32_t cols, uint32_t rows, uint32_t frame_id) {
   if (!g || !mm || cols != g->base.depth_camera.cols || rows != g->base.depth_camera.rows) return KF_GROUP_ERR_ARG;
-  if (g->failed) return KF_GROUP_ERR_STATE;
+  if (g->failed || g->color) return KF_GROUP_ERR_STATE;      // (a colour group takes kf_group_frame_color: nothing is enqueued, the group stays usable)
   DeviceGuard guard;
   if (!on_device) return fail(g, frame(g, nullptr, mm, frame_id));
   const uint16_t* per[KF_GROUP_MAX_MEMBERS];
@@ -397,9 +451,28 @@ int kf_group_frame(kf_group* g, const uint16_t* mm, int on_device, uint32_t cols
 int kf_group_frame_members(kf_group* g, const uint16_t* const* dev_mm, uint32_t cols, uint32_t rows, uint32_t frame_id) {
   if (!g || !dev_mm || cols != g->base.depth_camera.cols || rows != g->base.depth_camera.rows) return KF_GROUP_ERR_ARG;
   for (uint32_t i = 0; i < g->n; ++i) if (!dev_mm[i]) return KF_GROUP_ERR_ARG;
-  if (g->failed) return KF_GROUP_ERR_STATE;
+  if (g->failed || g->color) return KF_GROUP_ERR_STATE;
   DeviceGuard guard;
   return fail(g, frame(g, dev_mm, nullptr, frame_id));
+}
+
+int kf_group_frame_color(kf_group* g, const uint16_t* mm, const uint8_t* bgr, int on_device, uint32_t cols, uint32_t rows, uint32_t frame_id) {
+  if (!g || !mm || !bgr || cols != g->base.depth_camera.cols || rows != g->base.depth_camera.rows) return KF_GROUP_ERR_ARG;
+  if (g->failed || !g->color) return KF_GROUP_ERR_STATE;     // (a colourless group takes kf_group_frame)
+  DeviceGuard guard;
+  if (!on_device) return fail(g, frame(g, nullptr, mm, frame_id, nullptr, bgr));
+  const uint16_t* per[KF_GROUP_MAX_MEMBERS];
+  const uint8_t* per_bgr[KF_GROUP_MAX_MEMBERS];
+  for (uint32_t i = 0; i < g->n; ++i) { per[i] = mm; per_bgr[i] = bgr; }
+  return fail(g, frame(g, per, nullptr, frame_id, per_bgr, nullptr));
+}
+
+int kf_group_frame_members_color(kf_group* g, const uint16_t* const* dev_mm, const uint8_t* const* dev_bgr, uint32_t cols, uint32_t rows, uint32_t frame_id) {
+  if (!g || !dev_mm || !dev_bgr || cols != g->base.depth_camera.cols || rows != g->base.depth_camera.rows) return KF_GROUP_ERR_ARG;
+  for (uint32_t i = 0; i < g->n; ++i) if (!dev_mm[i] || !dev_bgr[i]) return KF_GROUP_ERR_ARG;
+  if (g->failed || !g->color) return KF_GROUP_ERR_STATE;
+  DeviceGuard guard;
+  return fail(g, frame(g, dev_mm, nullptr, frame_id, dev_bgr, nullptr));
 }
 
 int kf_group_track_result(kf_group* g, kf_track_result* out, int check_lockstep) {
@@ -452,7 +525,7 @@ int kf_group_marching_cubes(kf_group* g, float threshold) {
   DeviceGuard guard;
   for (uint32_t i = 0; i < g->n; ++i) {
     int st = (int)hipSetDevice(g->dev[i]);
-    if (!st) st = kf_marching_cubes(g->m[i], 0, threshold);
+    if (!st) st = kf_marching_cubes(g->m[i], g->color ? 1 : 0, threshold);
     if (st) return fail(g, st);
   }
   return 0;

@@ -234,6 +234,10 @@ __device__ __forceinline__ void rc_pixel_ray(const KfCam& cam, const float* T, i
   dir.z = (dir.z == 0.f) ? (float)1e-15 : dir.z;
 }
 
+// a colour as the fourth word of the z-slab merge's candidates (b, g, r from the low byte up, as the uchar4 lies in memory); all-zero bits: none
+__device__ __forceinline__ unsigned rc_color_word(uchar4 c) { return (unsigned)c.x | ((unsigned)c.y << 8) | ((unsigned)c.z << 16) | ((unsigned)c.w << 24); }
+__device__ __forceinline__ uchar4 rc_word_color(unsigned w) { return make_uchar4((unsigned char)(w & 255u), (unsigned char)((w >> 8) & 255u), (unsigned char)((w >> 16) & 255u), (unsigned char)(w >> 24)); }
+
 // [t_min, t_max) of a ray: getMinTime / getMaxTime (raycastingVolume.cu:44-63) clipped by the near / far planes (:152-153)
 __device__ __forceinline__ void rc_ray_interval(float S, float near_plane, float far_plane, float3 org, float3 dir, float3 cam_dir, float& tmin, float& tmax) {
   tmin = fmaxf(fmaxf(((dir.x > 0 ? 0.f : S) - org.x) / dir.x, ((dir.y > 0 ? 0.f : S) - org.y) / dir.y), ((dir.z > 0 ? 0.f : S) - org.z) / dir.z);
@@ -351,6 +355,9 @@ __device__ __forceinline__ void rc_tile_bounds(const RaycastArgs& a, const unsig
 }
 
 // one 32x16 pixel tile (tile_x, tile_y) by the 512 threads of a workgroup; s_tables: the workgroup's dynamic LDS
+// SPEC_COLOR (compile time; kf_raycast_volume_slab_cross_spec_color): the z-slab speculation carries a fourth word per pixel, interpolateColor at the
+// vertex under the same ownership test as the gradient -- out_spec then has 4 words per pixel.  false: the code of every other form, unchanged.
+template <bool SPEC_COLOR>
 __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, int tile_y, unsigned* s_tables) {
   const KfVolume& v = a.vol;
   // Packed bit tables live in LDS so that the empty-space walk costs LDS reads instead of dependent L2 round trips: one bit
@@ -449,6 +456,8 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
           int gzv = kf_f2i(kf_div(vtx.z * (float)v.res, rS));
           gzv = max(0, min(gzv, v.res - 1));
           want = a.out_spec != nullptr && __float_as_uint(alpha) != 0u && gzv >= v.own_z0 && gzv < v.own_z1;
+          // the colour at the vertex (:91-92), before and independently of the gradient: it stays whether or not a normal is found
+          if (SPEC_COLOR && want) { uchar4 c = make_uchar4(0, 0, 0, 0); kf_interpolate_color(v, vtx, c); out_c = c; }
         } else if (a.has_color) { uchar4 c = make_uchar4(0, 0, 0, 0); kf_interpolate_color(v, vtx, c); out_c = c; }
         float3 grad;
         if (want && gradient_for_point_either<RC_GRAD_BATCH, RC_GRAD_ROUNDS>(a.shared_grad, ((tile_x + tile_y + wave) & 1) != 0, v, last_pos, vtx, rS, rcell, grad)) {
@@ -468,6 +477,10 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
   if (a.out_ta) {
     const unsigned long long word = ((unsigned long long)__float_as_uint(t_cross) << 32) | (unsigned long long)(t_cross < inf ? __float_as_uint(out_alpha) : 0u);
     a.out_ta[pix] = word;
+    if (SPEC_COLOR) {
+      a.own_ta[pix] = word; a.out_spec[4 * pix] = out_n.x; a.out_spec[4 * pix + 1] = out_n.y; a.out_spec[4 * pix + 2] = out_n.z;
+      a.out_spec[4 * pix + 3] = __uint_as_float(rc_color_word(out_c));
+    } else
     if (a.out_spec) { a.own_ta[pix] = word; a.out_spec[3 * pix] = out_n.x; a.out_spec[3 * pix + 1] = out_n.y; a.out_spec[3 * pix + 2] = out_n.z; }
   }
   else { a.out_v[pix] = out_v; a.out_n[pix] = out_n; }
@@ -502,7 +515,12 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
 
 __global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast(RaycastArgs a) {
   extern __shared__ unsigned s_dyn[];
-  raycast_tile(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn);
+  raycast_tile<false>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn);
+}
+// kf_raycast_volume_slab_cross_spec_color: the crossing words, their second copy and 4 speculative words per pixel (normal, colour)
+__global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast_slab_color(RaycastArgs a) {
+  extern __shared__ unsigned s_dyn[];
+  raycast_tile<true>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn);
 }
 
 // The raycast with the NEXT frame's depth conversion + gate + bilateral filter riding along (kf_prefetch_frame, fused form).  The raycast
@@ -523,7 +541,7 @@ __global__ void __launch_bounds__(RAYCAST_THREADS) __attribute__((amdgpu_waves_p
   extern __shared__ unsigned s_dyn[];
   if ((int)blockIdx.x < n_rc) {
     __builtin_amdgcn_s_setprio(2);
-    raycast_tile(a, (int)blockIdx.x % rc_gx, (int)blockIdx.x / rc_gx, s_dyn);
+    raycast_tile<false>(a, (int)blockIdx.x % rc_gx, (int)blockIdx.x / rc_gx, s_dyn);
   } else {
     const int half = (int)(threadIdx.x >> 8), t = ((int)blockIdx.x - n_rc) * 2 + half, tid = (int)(threadIdx.x & 255);
     // a tile index past the last one names a row below the image: its threads touch nothing but still meet the barrier
@@ -545,10 +563,11 @@ __global__ void __launch_bounds__(RAYCAST_THREADS) __attribute__((amdgpu_waves_p
 
 static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
                           float near_plane, float far_plane, float* out_t, float4* out_v, float4* out_n, unsigned long long* out_ta = nullptr,
-                          unsigned long long* own_ta = nullptr, float* out_spec = nullptr) {
+                          unsigned long long* own_ta = nullptr, float* out_spec = nullptr, bool spec_color = false) {
   if (!c || !rp || !cam) return KF_ERR_ARG;
   if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
   if (has_color && (!c->vol.color || !c->raycast_rgb)) return KF_ERR_STATE;
+  if (spec_color && (!c->vol.color || !out_ta || !own_ta || !out_spec)) return KF_ERR_STATE;
   RaycastArgs a;
   a.vol = c->vol;
   a.cam.cols = (int)cam->cols; a.cam.rows = (int)cam->rows; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.fx = cam->fx; a.cam.fy = cam->fy;
@@ -600,7 +619,15 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
     const size_t pyr_lds = model_pyr ? (size_t)(32 * 16 + 16 * 8) * 2 * sizeof(float4) : 0;      // the tile's two maps and their level 1
     const size_t lds = macro_bytes + (size_t)a.neg_words * 4 > pyr_lds ? macro_bytes + (size_t)a.neg_words * 4 : pyr_lds;
     const bool timed = kf_evt_attach(c, KF_STAGE_RAYCAST_KERNEL, &ke0, &ke1);
-    if (c->fp_pending && c->alt_raw) {
+    if (spec_color) {
+      // the colour form of the z-slab speculation: a kernel of its own, no riders (a pending kf_prefetch_frame note stays where it is and is void at
+      // the next kf_preprocess: the frame is then preprocessed by its own launches, same bits)
+      form.kernel = KF_RC_PLAIN; form.grid = grid.x * grid.y;
+      if (timed) {
+        hipExtLaunchKernelGGL(k_raycast_slab_color, grid, dim3(RAYCAST_THREADS), (unsigned)lds, c->stream, ke0, ke1, 0, a);
+        kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
+      } else hipLaunchKernelGGL(k_raycast_slab_color, grid, dim3(RAYCAST_THREADS), lds, c->stream, a);
+    } else if (c->fp_pending && c->alt_raw) {
       // kf_prefetch_frame left a note: the next frame's u16 -> f32 + gate + bilateral rides in this launch (k_raycast_prefetch), its vertices /
       // normals follow; the set lands in the alternate buffers and kf_preprocess adopts it when it is asked for exactly that frame
       c->fp_pending = 0;
@@ -736,9 +763,21 @@ extern "C" int kf_raycast_volume_slab_cross_spec(kf_ctx* c, const kf_mat44* tran
   if (st) return st;
   return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr, (unsigned long long*)dev_ta, (unsigned long long*)dev_ta_own, dev_spec);
 }
+// The colour forms of the three calls (a context with a colour plane): the candidate is 4 words per pixel, the normal's three and the uchar4 colour
+// word of interpolateColor at the VERTEX (raycastingVolume.cu:91-92, tsdfVolume.h:123-148) -- evaluated by the vertex's owner like the gradient, before
+// and independently of it, so a pixel without a normal can carry a colour, as in the whole-volume march.  All-zero bits: no colour.
+extern "C" int kf_raycast_volume_slab_cross_spec_color(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
+                                                       float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec) {
+  if (!c || !rp || !dev_ta || !dev_ta_own || !dev_spec) return KF_ERR_ARG;
+  const int st = slab_halo_check(c, rp);
+  if (st) return st;
+  return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr, (unsigned long long*)dev_ta, (unsigned long long*)dev_ta_own, dev_spec, true);
+}
 struct SlabNormalArgs { KfVolume vol; KfCam cam; const float* pose; KfMat pose_val; const unsigned long long* ta; float* cand; float inc, near_plane, far_plane; int shared_grad;
-                        const unsigned long long* own_ta; const float* spec; };   // own_ta / spec: kf_raycast_volume_slab_cross_spec's second outputs, or null   // cand: 3 floats per pixel
-__global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) {
+                        const unsigned long long* own_ta; const float* spec; };   // own_ta / spec: kf_raycast_volume_slab_cross_spec's second outputs, or null   // cand, spec: 3 floats per pixel (the colour forms: 4)
+// COLOR (compile time; kf_slab_ray_normals_color): spec and cand have 4 words per pixel, the fourth the colour at the vertex
+template <bool COLOR>
+__device__ __forceinline__ void slab_ray_normals_body(SlabNormalArgs a) {
   // (a workgroup is a 32x8 pixel tile, a wave an 8x8 patch of it: its 64 vertices stay inside a few bricks -- fewer cache lines per gather instruction)
   const int x = (int)blockIdx.x * 32 + (int)(threadIdx.x >> 6) * 8 + (int)(threadIdx.x & 7), y = (int)blockIdx.y * 8 + (int)((threadIdx.x >> 3) & 7);
   if (x >= a.cam.cols || y >= a.cam.rows) return;
@@ -748,10 +787,13 @@ __global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) {
   const float t_cross = __uint_as_float((unsigned)(w >> 32));
   const unsigned alpha_bits = (unsigned)w;
   float3 out = kf3(0.f, 0.f, 0.f);                                             // all-zero bits: not this rank's vertex, or no gradient (a found gradient is a unit vector)
+  unsigned out_c = 0u;                                                         // (COLOR) all-zero bits: not this rank's vertex, or no colour there
+  constexpr int W = COLOR ? 4 : 3;
   if (t_cross < __builtin_huge_valf() && alpha_bits != 0u && a.own_ta && a.own_ta[i] == w) {
     // this context's own crossing won: its march has evaluated the vertex already, if the vertex is this context's (zeros otherwise: the owner's
     // own crossing word differs from the winner's, so the owner takes the branch below)
-    out = kf3(a.spec[3 * i], a.spec[3 * i + 1], a.spec[3 * i + 2]);
+    out = kf3(a.spec[W * i], a.spec[W * i + 1], a.spec[W * i + 2]);
+    if (COLOR) out_c = __float_as_uint(a.spec[W * i + 3]);
   } else if (t_cross < __builtin_huge_valf() && alpha_bits != 0u) {
     float3 org, dir, cam_dir;
     rc_pixel_ray(a.cam, a.pose ? a.pose : a.pose_val.m, x, y, org, dir, cam_dir);
@@ -760,6 +802,7 @@ __global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) {
     int gz = kf_f2i(kf_div(vtx.z * (float)v.res, rS));                       // the vertex's voxel layer (tsdfVolume.h:50-56), clamped: exactly one owner
     gz = max(0, min(gz, v.res - 1));
     if (gz >= v.own_z0 && gz < v.own_z1) {
+      if (COLOR) { uchar4 c = make_uchar4(0, 0, 0, 0); kf_interpolate_color(v, vtx, c); out_c = rc_color_word(c); }     // before the gradient, whatever it finds
       float tmin, tmax;
       rc_ray_interval(v.size, a.near_plane, a.far_plane, org, dir, cam_dir, tmin, tmax);
       float t = tmin, t_prev = tmin;
@@ -769,12 +812,17 @@ __global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) {
       if (gradient_for_point_either<6, RC_SLAB_GRAD_ROUNDS>(a.shared_grad, ((blockIdx.x + blockIdx.y + (threadIdx.x >> 6)) & 1u) != 0u, v, last_pos, vtx, rS, rcell, grad)) out = grad;                  // (the six taps' 48 gathers in one batch: this kernel has the registers)
     }
   }
-  a.cand[3 * i] = out.x; a.cand[3 * i + 1] = out.y; a.cand[3 * i + 2] = out.z;
+  a.cand[W * i] = out.x; a.cand[W * i + 1] = out.y; a.cand[W * i + 2] = out.z;
+  if (COLOR) a.cand[W * i + 3] = __uint_as_float(out_c);
 }
+__global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) { slab_ray_normals_body<false>(a); }
+__global__ void __launch_bounds__(256) k_slab_ray_normals_color(SlabNormalArgs a) { slab_ray_normals_body<true>(a); }
 static int slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
-                            float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand) {
+                            float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand,
+                            bool color = false) {
   if (!c || !rp || !cam || !dev_ta_min || !dev_cand) return KF_ERR_ARG;
   if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
+  if (color && !c->vol.color) return KF_ERR_STATE;
   SlabNormalArgs a;
   a.vol = c->vol; a.ta = (const unsigned long long*)dev_ta_min; a.cand = dev_cand;
   a.own_ta = (dev_ta_own && dev_spec) ? (const unsigned long long*)dev_ta_own : nullptr; a.spec = dev_spec;
@@ -783,8 +831,15 @@ static int slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_rayca
   a.shared_grad = rc_shared_grad_for(c->vol);
   if (transform) { for (int k = 0; k < 16; ++k) a.pose_val.m[k] = transform->m[k]; a.pose = nullptr; }
   else a.pose = c->track->pose;
-  hipLaunchKernelGGL(k_slab_ray_normals, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
+  if (color) hipLaunchKernelGGL(k_slab_ray_normals_color, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL(k_slab_ray_normals, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
   return (int)hipGetLastError();
+}
+// dev_ta_own and dev_spec (4 words per pixel) may both be NULL: then every owned vertex is evaluated here
+extern "C" int kf_slab_ray_normals_color(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
+                                         float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand) {
+  if ((dev_ta_own == nullptr) != (dev_spec == nullptr)) return KF_ERR_ARG;
+  return slab_ray_normals(c, transform, rp, cam, near_plane, far_plane, dev_ta_min, dev_ta_own, dev_spec, dev_cand, true);
 }
 extern "C" int kf_slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
                                    float near_plane, float far_plane, const uint64_t* dev_ta_min, float* dev_cand) {
@@ -795,16 +850,20 @@ extern "C" int kf_slab_ray_normals_spec(kf_ctx* c, const kf_mat44* transform, co
   if (!dev_ta_own || !dev_spec) return KF_ERR_ARG;
   return slab_ray_normals(c, transform, rp, cam, near_plane, far_plane, dev_ta_min, dev_ta_own, dev_spec, dev_cand);
 }
-struct SlabUnpackArgs { const unsigned long long* ta; const float* cand; float4* v; float4* n; KfCam cam; const float* pose; KfMat pose_val; KfPyrOut pyr; };   // cand: 3 floats per pixel
+struct SlabUnpackArgs { const unsigned long long* ta; const float* cand; float4* v; float4* n; KfCam cam; const float* pose; KfMat pose_val; KfPyrOut pyr; };   // cand: 3 floats per pixel (the colour form: 4)
 // one 32x8 pixel tile per workgroup: the tile's whole 2x2 and 4x4 blocks also give levels 1 and 2 of the model maps' pyramids (kf_tile_pyramid),
 // so the tracker that follows finds them done, as after a single-GPU raycast
-__global__ void __launch_bounds__(256) k_slab_rays_unpack(SlabUnpackArgs a) {
+// COLOR (compile time; kf_set_model_maps_rays_color): cand has 4 words per pixel and the fourth goes to rgb (KF_MAP_RAYCAST_RGB), normal or not
+template <bool COLOR>
+__device__ __forceinline__ void slab_rays_unpack_body(SlabUnpackArgs a, uchar4* rgb) {
   __shared__ float4 s_v[32 * 8], s_n[32 * 8], s1_v[16 * 4], s1_n[16 * 4];
   const int x = (int)blockIdx.x * 32 + (int)(threadIdx.x & 31), y = (int)blockIdx.y * 8 + (int)(threadIdx.x >> 5);
   float4 v = make_float4(0.f, 0.f, 0.f, 0.f), n = v;
   if (x < a.cam.cols && y < a.cam.rows) {
     const int i = y * a.cam.cols + x;
-    const float3 cd = kf3(a.cand[3 * i], a.cand[3 * i + 1], a.cand[3 * i + 2]);
+    constexpr int W = COLOR ? 4 : 3;
+    const float3 cd = kf3(a.cand[W * i], a.cand[W * i + 1], a.cand[W * i + 2]);
+    if (COLOR) rgb[i] = rc_word_color(__float_as_uint(a.cand[W * i + 3]));
     if ((__float_as_uint(cd.x) | __float_as_uint(cd.y) | __float_as_uint(cd.z)) != 0u) {     // the vertex's owner found a gradient (a unit vector: some bit is set): vertex = org + dir * alpha (raycastingVolume.cu:90), w = 1
       float3 org, dir, cam_dir;
       rc_pixel_ray(a.cam, a.pose ? a.pose : a.pose_val.m, x, y, org, dir, cam_dir);
@@ -819,9 +878,12 @@ __global__ void __launch_bounds__(256) k_slab_rays_unpack(SlabUnpackArgs a) {
     kf_tile_pyramid<32, 8>(a.pyr, (int)blockIdx.x * 32, (int)blockIdx.y * 8, (int)threadIdx.x, s_v, s_n, s1_v, s1_n, [] { __syncthreads(); });
   }
 }
-extern "C" int kf_set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, const kf_camera_params* cam, const uint64_t* dev_ta_min, const float* dev_cand) {
+__global__ void __launch_bounds__(256) k_slab_rays_unpack(SlabUnpackArgs a) { slab_rays_unpack_body<false>(a, nullptr); }
+__global__ void __launch_bounds__(256) k_slab_rays_unpack_color(SlabUnpackArgs a, uchar4* rgb) { slab_rays_unpack_body<true>(a, rgb); }
+static int set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, const kf_camera_params* cam, const uint64_t* dev_ta_min, const float* dev_cand, bool color) {
   if (!c || !cam || !dev_ta_min || !dev_cand) return KF_ERR_ARG;
   if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
+  if (color && !c->raycast_rgb) return KF_ERR_STATE;
   SlabUnpackArgs a;
   c->model_pyr_ok = 0;
   memset(&a.pyr, 0, sizeof(a.pyr));
@@ -833,9 +895,16 @@ extern "C" int kf_set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, cons
   a.cam.cols = (int)cam->cols; a.cam.rows = (int)cam->rows; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.fx = cam->fx; a.cam.fy = cam->fy;
   if (transform) { for (int k = 0; k < 16; ++k) a.pose_val.m[k] = transform->m[k]; a.pose = nullptr; }
   else a.pose = c->track->pose;                       // the pose the raycast used: nothing moves it between the raycast and this call
-  hipLaunchKernelGGL(k_slab_rays_unpack, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
+  if (color) hipLaunchKernelGGL(k_slab_rays_unpack_color, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a, c->raycast_rgb);
+  else hipLaunchKernelGGL(k_slab_rays_unpack, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
   if (a.pyr.v1) c->model_pyr_ok = 1;
   return (int)hipGetLastError();
+}
+extern "C" int kf_set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, const kf_camera_params* cam, const uint64_t* dev_ta_min, const float* dev_cand) {
+  return set_model_maps_rays(c, transform, cam, dev_ta_min, dev_cand, false);
+}
+extern "C" int kf_set_model_maps_rays_color(kf_ctx* c, const kf_mat44* transform, const kf_camera_params* cam, const uint64_t* dev_ta_min, const float* dev_cand) {
+  return set_model_maps_rays(c, transform, cam, dev_ta_min, dev_cand, true);
 }
 
 extern "C" int kf_set_model_maps_device(kf_ctx* c, const float* dev_v, const float* dev_n) {

@@ -26,6 +26,7 @@ SYMBOLS = [
     "kf_group_frame", "kf_group_frame_members", "kf_group_track_result", "kf_group_member", "kf_group_marching_cubes",
     "kf_group_triangle_count", "kf_group_read_triangles", "kf_group_merge_timing", "kf_group_read_merge_ms", "kf_group_synchronize",
     "kf_group_stream",
+    "kf_group_create_color", "kf_group_validate_color", "kf_group_frame_color", "kf_group_frame_members_color",
 ]
 
 
@@ -96,6 +97,13 @@ def validate_status(cfg, params, backend, cuts, devices=None, halo=0, uid=None, 
                                     len(cuts) - 1, cuts_a, devs_a, halo, uid_a, rank, world)
 
 
+def validate_color_status(cfg, params, backend, cuts, devices=None, halo=0, uid=None, rank=0, world=1, angle_weight=True):
+    """kf_group_validate_color: the argument checks of kf_group_create_color alone"""
+    cuts_a, devs_a, uid_a = _args(cuts, devices, uid)
+    return load().kf_group_validate_color(C.byref(cfg) if cfg is not None else None, C.byref(params) if params is not None else None, int(angle_weight),
+                                          backend, len(cuts) - 1, cuts_a, devs_a, halo, uid_a, rank, world)
+
+
 def create_status(cfg, params, backend, cuts, devices=None, halo=0, uid=None, rank=0, world=1):
     """kf_group_create's status alone (the group, if made, is destroyed at once): the validation tests"""
     lib = load()
@@ -119,20 +127,25 @@ class Group:
     """One kf_group.  Use the constructors local / rccl_all / rccl_rank."""
 
     def __init__(self, kcam, res, size, backend, cuts, devices=None, halo=0, params=None, max_weight=None, levels=3, max_triangles=0,
-                 uid=None, rank=0, world=1):
+                 uid=None, rank=0, world=1, has_color=False, angle_weight=True):
         self.lib = load()
         self.cam, self.res, self.size, self.levels = kcam, int(res), float(size), int(levels)
         self.cuts = [int(z) for z in cuts]
         self.n = len(self.cuts) - 1
         self.params = params if params is not None else stock_params(levels=levels)
         device = devices[0] if devices else 0
-        self.cfg = base_config(kcam, res, size, max_weight, levels, max_triangles, device)
+        self.has_color, self.angle_weight = bool(has_color), bool(angle_weight)
+        self.cfg = base_config(kcam, res, size, max_weight, levels, max_triangles, device, has_color=self.has_color)
         cuts_a = (C.c_uint32 * len(self.cuts))(*self.cuts)
         devs_a = (C.c_int32 * self.n)(*devices) if devices is not None else None
         uid_a = (C.c_uint8 * UNIQUE_ID_BYTES).from_buffer_copy(uid) if uid is not None else None
         self.h = C.c_void_p()
-        _chk(self.lib.kf_group_create(C.byref(self.cfg), C.byref(self.params), backend, self.n, cuts_a, devs_a, int(halo), uid_a, rank, world,
-                                      C.byref(self.h)), "kf_group_create")
+        if self.has_color:
+            _chk(self.lib.kf_group_create_color(C.byref(self.cfg), C.byref(self.params), int(self.angle_weight), backend, self.n, cuts_a, devs_a, int(halo),
+                                                uid_a, rank, world, C.byref(self.h)), "kf_group_create_color")
+        else:
+            _chk(self.lib.kf_group_create(C.byref(self.cfg), C.byref(self.params), backend, self.n, cuts_a, devs_a, int(halo), uid_a, rank, world,
+                                          C.byref(self.h)), "kf_group_create")
         _LIVE.add(self)
         n, hl = C.c_uint32(), C.c_uint32()
         _chk(self.lib.kf_group_members(self.h, C.byref(n), C.byref(hl)), "kf_group_members")
@@ -168,16 +181,30 @@ class Group:
     def set_pose(self, pose):
         _chk(self.lib.kf_group_set_pose(self.h, C.byref(K.Mat44.of(pose))), "kf_group_set_pose")
 
-    def frame(self, mm, frame_id):
-        """mm: a host u16 image (numpy) or the device address (int) of one that every member can read"""
-        if isinstance(mm, np.ndarray):
+    def frame(self, mm, frame_id, rgb=None):
+        """mm: a host u16 image (numpy) or the device address (int) of one that every member can read; rgb (a colour group's frames): the
+        BGR image, rows x cols x 3 bytes, where mm lies (numpy with numpy, device address with device address).  The kind of call follows
+        `rgb`, so a colour group without one -- or a colourless group with one -- gets the library's ERR_STATE"""
+        if rgb is not None:
+            if isinstance(mm, np.ndarray):
+                mm, rgb = np.ascontiguousarray(mm, np.uint16), np.ascontiguousarray(rgb, np.uint8)
+                _chk(self.lib.kf_group_frame_color(self.h, mm.ctypes.data_as(C.c_void_p), rgb.ctypes.data_as(C.c_void_p), 0, self.cam.cols, self.cam.rows,
+                                                   frame_id), "kf_group_frame_color")
+            else:
+                _chk(self.lib.kf_group_frame_color(self.h, C.c_void_p(int(mm)), C.c_void_p(int(rgb)), 1, self.cam.cols, self.cam.rows, frame_id),
+                     "kf_group_frame_color")
+        elif isinstance(mm, np.ndarray):
             mm = np.ascontiguousarray(mm, np.uint16)
             _chk(self.lib.kf_group_frame(self.h, mm.ctypes.data_as(C.c_void_p), 0, self.cam.cols, self.cam.rows, frame_id), "kf_group_frame")
         else:
             _chk(self.lib.kf_group_frame(self.h, C.c_void_p(int(mm)), 1, self.cam.cols, self.cam.rows, frame_id), "kf_group_frame")
 
-    def frame_members(self, dev_ptrs, frame_id):
+    def frame_members(self, dev_ptrs, frame_id, rgb_ptrs=None):
         arr = (C.c_void_p * self.n)(*[int(p) for p in dev_ptrs])
+        if rgb_ptrs is not None:
+            rgb = (C.c_void_p * self.n)(*[int(p) for p in rgb_ptrs])
+            _chk(self.lib.kf_group_frame_members_color(self.h, arr, rgb, self.cam.cols, self.cam.rows, frame_id), "kf_group_frame_members_color")
+            return
         _chk(self.lib.kf_group_frame_members(self.h, arr, self.cam.cols, self.cam.rows, frame_id), "kf_group_frame_members")
 
     def track_result(self, check_lockstep=True):

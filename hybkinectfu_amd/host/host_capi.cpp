@@ -70,6 +70,16 @@ int hkf_app_process_frame(const uint16_t* mm, int on_device, unsigned frame_id, 
   if (!g_app->processNewFrame(d, col)) return -2;
   return g_app->lastTracked() ? 1 : 0;
 }
+// the same with the frame's BGR image (host memory, rgb camera's size; used when hkf_app_configure_io switched useRGBData on)
+int hkf_app_process_frame_color(const uint16_t* mm, const uint8_t* bgr, unsigned frame_id, double stamp) {
+  if (!g_app) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  const CameraParams& rc = AppParams::instance()->_rgb_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.time_stamp = stamp; d.on_device = false;
+  ColorFrameData col; col.bgr = bgr; col.cols = (int)rc.cols; col.rows = (int)rc.rows; col.frame_id = frame_id; col.time_stamp = stamp;
+  if (!g_app->processNewFrame(d, col)) return -2;
+  return g_app->lastTracked() ? 1 : 0;
+}
 // streaming: no host synchronisation
 int hkf_app_enqueue_frame(const uint16_t* mm, int on_device, unsigned frame_id) {
   if (!g_app) return -1;

@@ -19,7 +19,8 @@ bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectf
   cfg.depth_camera = p->_depth_camera_params; cfg.rgb_camera = p->_rgb_camera_params;
   cfg.volume.resolution = p->_volume_params.nResolution; cfg.volume.size_m = p->_volume_params.fVolumeMeterSize; cfg.volume.max_weight = p->_volume_params.fWeightMax;
   cfg.pyramid_levels = p->_icp_params.nPyramidLevels; cfg.max_triangles = p->_marchingcube_params.uMaxTriangles;
-  cfg.has_color = 0; cfg.device = p->device;
+  _color = p->_switch_params.useRGBData;                       // as HybKinectfu does (CudaDeviceDataMan::init)
+  cfg.has_color = _color ? 1 : 0; cfg.device = p->device;
   kf_group_params gp; memset(&gp, 0, sizeof(gp));
   gp.trunc_min = p->_depth_prepocess_params.fMinTrunc; gp.trunc_max = p->_depth_prepocess_params.fMaxTrunc;
   gp.sigma_pixel = p->_depth_prepocess_params.fSigmaPixel; gp.sigma_depth = p->_depth_prepocess_params.fSigmaDepth;
@@ -32,9 +33,12 @@ bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectf
   if (!layout.devices.empty() && layout.devices.size() != members) return check(KF_GROUP_ERR_ARG);
   if (layout.backend == KF_GROUP_RCCL_RANK && layout.unique_id.size() != KF_GROUP_UNIQUE_ID_BYTES) return check(KF_GROUP_ERR_ARG);
   std::vector<int32_t> devs(layout.devices.begin(), layout.devices.end());
-  if (!check(kf_group_create(&cfg, &gp, layout.backend, members, layout.cuts.data(), devs.empty() ? nullptr : devs.data(), layout.halo,
-                             layout.unique_id.empty() ? nullptr : layout.unique_id.data(), layout.rank, layout.world, &_group)))
-    return false;
+  const uint8_t* uid = layout.unique_id.empty() ? nullptr : layout.unique_id.data();
+  const int st = _color ? kf_group_create_color(&cfg, &gp, p->_switch_params.colorAngleWeight ? 1 : 0, layout.backend, members, layout.cuts.data(),
+                                                devs.empty() ? nullptr : devs.data(), layout.halo, uid, layout.rank, layout.world, &_group)
+                        : kf_group_create(&cfg, &gp, layout.backend, members, layout.cuts.data(), devs.empty() ? nullptr : devs.data(), layout.halo,
+                                          uid, layout.rank, layout.world, &_group);
+  if (!check(st)) return false;
   Mat44 camera_pose0 = Mat44::getIdentity();                   // the same expression as HybKinectfu::init
   camera_pose0.setTranslation((float)(p->_volume_params.fVolumeMeterSize / 2.0), (float)(p->_volume_params.fVolumeMeterSize / 2.0),
                               -p->_depth_prepocess_params.fMinTrunc);
@@ -45,9 +49,16 @@ bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectf
   return true;
 }
 
-bool HybKinectfuSlabs::enqueueFrame(const DepthFrameData& d, const ColorFrameData&) {
+bool HybKinectfuSlabs::enqueueFrame(const DepthFrameData& d, const ColorFrameData& c) {
   if (!_inited) return false;
-  if (!check(kf_group_frame(_group, d.mm, d.on_device ? 1 : 0, (uint32_t)d.cols, (uint32_t)d.rows, d.frameId()))) return false;
+  if (_color) {
+    // useRGBData: the frame's BGR image goes to every member (where the depth frame lies: host or device).  A frame without one is refused -- it
+    // would fuse whatever the members' rgb maps held before
+    if (!c.bgr) return check(KF_GROUP_ERR_ARG);
+    const CameraParams& rc = AppParams::instance()->_rgb_camera_params;      // the members read a whole rgb-camera image (kf_upload_rgb's check)
+    if (c.cols != (int)rc.cols || c.rows != (int)rc.rows) return check(KF_GROUP_ERR_ARG);
+    if (!check(kf_group_frame_color(_group, d.mm, c.bgr, d.on_device ? 1 : 0, (uint32_t)d.cols, (uint32_t)d.rows, d.frameId()))) return false;
+  } else if (!check(kf_group_frame(_group, d.mm, d.on_device ? 1 : 0, (uint32_t)d.cols, (uint32_t)d.rows, d.frameId()))) return false;
   _pending = true;
   return true;
 }
@@ -91,7 +102,7 @@ bool HybKinectfuSlabs::saveMesh(const std::string& filename) {   // :61-96 on th
   if (n == 0) return false;
   std::vector<kf_triangle> tris(n);
   if (!check(kf_group_read_triangles(_group, tris.data(), 0, n))) return false;
-  _mesh.setTriangles(tris.data(), n, false);
+  _mesh.setTriangles(tris.data(), n, _color);
   _mesh.weldMesh();
   return _mesh.mesh().saveToFile(filename);
 }

@@ -1,7 +1,8 @@
 // hybkf_slabs.hpp -- HybKinectfuSlabs: the reference's HybKinectfu surface (src/HybKinectfu.h) over a slab group (include/hybkf_group.h),
 // for C++ callers that want more than one GPU -- or the z-slab protocol on one GPU.  It reads the same AppParams as HybKinectfu (camera,
 // volume, ICP, depth preprocess, integrate, raycast) plus a SlabLayout.  HybKinectfu itself stays the one-context class and ignores
-// AppParams::slab_*.  Built as libhybkf_slabs.so, above libhybkf_host.so, libhybkf_group.so and libhybkf.so.
+// AppParams::slab_*.  It honours _switch_params.useRGBData / colorAngleWeight as HybKinectfu does: a colour group (kf_group_create_color), every frame's
+// ColorFrameData::bgr handed to the members, coloured triangles and a coloured mesh; with useRGBData set a frame without a BGR image is refused.  Built as libhybkf_slabs.so, above libhybkf_host.so, libhybkf_group.so and libhybkf.so.
 #pragma once
 #include <stdint.h>
 #include <string>
@@ -46,6 +47,6 @@ private:
   kf_group* _group = nullptr;
   MeshGeneratorMarchingcube _mesh;
   Mat44 _pose = Mat44::getIdentity();
-  bool _inited = false, _last_tracked = true, _pending = false;
+  bool _inited = false, _last_tracked = true, _pending = false, _color = false;
   int _err = 0;
 };

@@ -3,6 +3,7 @@
 #include <string.h>
 
 static HybKinectfuSlabs* g_slabs = nullptr;
+static struct { bool use_rgb = false, angle_weight = true; } g_switch;      // [Switch] useRGBData / colorAngleWeight, applied by hkf_slabs_init
 
 extern "C" {
 
@@ -20,6 +21,8 @@ int hkf_slabs_init(unsigned volume_res, float volume_size, unsigned depth_cols, 
   if (integrate_dist > 0) p->_integrate_params.fMaxIntegrateDist = integrate_dist;
   if (trunc_max > 0) p->_depth_prepocess_params.fMaxTrunc = trunc_max;
   p->device = device;
+  p->_switch_params.useRGBData = g_switch.use_rgb;
+  if (g_switch.use_rgb) p->_switch_params.colorAngleWeight = g_switch.angle_weight;
   delete g_slabs; g_slabs = nullptr;
   SlabLayout layout;
   layout.backend = backend;
@@ -31,6 +34,8 @@ int hkf_slabs_init(unsigned volume_res, float volume_size, unsigned depth_cols, 
   if (!g_slabs->init(layout)) { const int e = g_slabs->lastError(); delete g_slabs; g_slabs = nullptr; return e ? e : KF_GROUP_ERR_STATE; }
   return 0;
 }
+// call BEFORE hkf_slabs_init: useRGBData (and, with it, colorAngleWeight) for the next init; off until called
+void hkf_slabs_configure_color(int use_rgb, int angle_weight) { g_switch.use_rgb = use_rgb != 0; g_switch.angle_weight = angle_weight != 0; }
 void hkf_slabs_shutdown() { delete g_slabs; g_slabs = nullptr; }
 void* hkf_slabs_group() { return g_slabs ? (void*)g_slabs->group() : nullptr; }
 
@@ -48,6 +53,24 @@ int hkf_slabs_enqueue_frame(const uint16_t* mm, int on_device, unsigned frame_id
   const CameraParams& c = AppParams::instance()->_depth_camera_params;
   DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
   ColorFrameData col;
+  return g_slabs->enqueueFrame(d, col) ? 0 : -2;
+}
+// the same two with the frame's BGR image (rows x cols x 3 bytes, where mm lies: host or device; NULL: none)
+int hkf_slabs_process_frame_color(const uint16_t* mm, const uint8_t* bgr, int on_device, unsigned frame_id) {
+  if (!g_slabs) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  const CameraParams& rc = AppParams::instance()->_rgb_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
+  ColorFrameData col; col.bgr = bgr; col.cols = (int)rc.cols; col.rows = (int)rc.rows; col.frame_id = frame_id;
+  if (!g_slabs->processNewFrame(d, col)) return -2;
+  return g_slabs->lastTracked() ? 1 : 0;
+}
+int hkf_slabs_enqueue_frame_color(const uint16_t* mm, const uint8_t* bgr, int on_device, unsigned frame_id) {
+  if (!g_slabs) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  const CameraParams& rc = AppParams::instance()->_rgb_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
+  ColorFrameData col; col.bgr = bgr; col.cols = (int)rc.cols; col.rows = (int)rc.rows; col.frame_id = frame_id;
   return g_slabs->enqueueFrame(d, col) ? 0 : -2;
 }
 int hkf_slabs_get_pose(float out16[16]) {

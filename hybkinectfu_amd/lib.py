@@ -111,6 +111,7 @@ SYMBOLS = [
     "kf_upload_depth_mm_next", "kf_take_next_depth", "kf_cull_tail_counts", "kf_count_observed_voxels", "kf_get_fusion_counters",
     "kf_get_fusion_form", "kf_get_raycast_form",
     "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
+    "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
 ]
 
 
@@ -241,6 +242,10 @@ class Context:
     def upload_rgb(self, bgr):
         bgr = np.ascontiguousarray(bgr, np.uint8)
         _chk(self.lib.kf_upload_rgb(self.h, _p(bgr), bgr.shape[1], bgr.shape[0]), "kf_upload_rgb")
+
+    def set_rgb_device(self, dev_ptr):
+        """a BGR frame (rows x cols x 3 bytes) that is already on the device"""
+        _chk(self.lib.kf_set_rgb_device(self.h, C.c_void_p(dev_ptr), self.rgb_cam.cols, self.rgb_cam.rows), "kf_set_rgb_device")
 
     def upload_map(self, map_id, level, arr):
         arr = np.ascontiguousarray(arr)
@@ -424,6 +429,24 @@ class Context:
     def set_model_maps_rays(self, pose, dev_ta_min, dev_cand):
         tp = C.byref(Mat44.of(pose)) if pose is not None else None
         _chk(self.lib.kf_set_model_maps_rays(self.h, tp, C.byref(self.cam), C.c_void_p(dev_ta_min), C.c_void_p(dev_cand)), "kf_set_model_maps_rays")
+
+    # the colour forms: dev_spec / dev_cand hold 4 words per pixel (normal, colour word)
+    def raycast_slab_cross_spec_color(self, pose, inc, near, far, dev_ta, dev_ta_own, dev_spec):
+        rp = RaycastParams(inc)
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_raycast_volume_slab_cross_spec_color(self.h, tp, C.byref(rp), C.byref(self.cam), C.c_float(near), C.c_float(far), C.c_void_p(dev_ta),
+                                                              C.c_void_p(dev_ta_own), C.c_void_p(dev_spec)), "kf_raycast_volume_slab_cross_spec_color")
+
+    def slab_ray_normals_color(self, pose, inc, near, far, dev_ta_min, dev_ta_own, dev_spec, dev_cand):
+        """dev_ta_own / dev_spec None: every vertex this context owns is evaluated here (gradient and colour)"""
+        rp = RaycastParams(inc)
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_slab_ray_normals_color(self.h, tp, C.byref(rp), C.byref(self.cam), C.c_float(near), C.c_float(far), C.c_void_p(dev_ta_min),
+                                                C.c_void_p(dev_ta_own), C.c_void_p(dev_spec), C.c_void_p(dev_cand)), "kf_slab_ray_normals_color")
+
+    def set_model_maps_rays_color(self, pose, dev_ta_min, dev_cand):
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_set_model_maps_rays_color(self.h, tp, C.byref(self.cam), C.c_void_p(dev_ta_min), C.c_void_p(dev_cand)), "kf_set_model_maps_rays_color")
 
     def set_model_maps_device(self, dev_v, dev_n):
         _chk(self.lib.kf_set_model_maps_device(self.h, C.c_void_p(dev_v), C.c_void_p(dev_n)), "kf_set_model_maps_device")

@@ -115,6 +115,9 @@ int kf_upload_depth_mm_next(kf_ctx* ctx, const uint16_t* host_mm, uint32_t cols,
 int kf_take_next_depth(kf_ctx* ctx);
 int kf_set_depth_mm_device(kf_ctx* ctx, const uint16_t* dev_mm, uint32_t cols, uint32_t rows);   /* frame already in HBM */
 int kf_upload_rgb(kf_ctx* ctx, const uint8_t* host_bgr, uint32_t cols, uint32_t rows);
+/* the counterpart of kf_set_depth_mm_device for colour: a BGR frame (3 bytes per pixel, rgb_camera's size) already in HBM.  It is widened into the
+ * context's raw rgb map where the stream stands; the caller keeps dev_bgr unchanged until then (stream order, or kf_synchronize) */
+int kf_set_rgb_device(kf_ctx* ctx, const uint8_t* dev_bgr, uint32_t cols, uint32_t rows);
 
 /* cudaTruncDepth  src/cuda/DataPreprocesser.cu:80-88 */
 int kf_trunc_depth(kf_ctx* ctx, float trunc_min, float trunc_max);
@@ -264,6 +267,25 @@ int kf_raycast_volume_slab_cross_spec(kf_ctx* ctx, const kf_mat44* transform, co
                                       float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec);
 int kf_slab_ray_normals_spec(kf_ctx* ctx, const kf_mat44* transform, const kf_raycast_params* raycast_params, const kf_camera_params* depth_camera,
                              float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand);
+/* COLOUR FORMS of the ray-form merge, for contexts created with has_color (KF_ERR_STATE without a colour plane).  The candidate is 4 words per
+ * pixel: the normal's three, then the uchar4 colour word (b, g, r, 0 from the low byte up) of interpolateColor at the VERTEX org + dir * alpha
+ * (raycastingVolume.cu:91-92, tsdfVolume.h:123-148); all-zero bits = no colour.  The colour is the vertex OWNER's to evaluate, like the gradient (its
+ * eight voxels lie within one layer of the vertex's), and it is evaluated before and independently of the gradient: a pixel whose gradient fails keeps
+ * its colour, as in kf_raycast_volume(has_color = 1).  One contributor per pixel, so the integer SUM over 4 words returns its bits.
+ *   kf_raycast_volume_slab_cross_spec_color   kf_raycast_volume_slab_cross_spec with dev_spec of 4 words per pixel (normal, colour), zeros when the
+ *                                             vertex is not this context's.  A kernel of its own: a pending kf_prefetch_frame does not ride in it
+ *                                             (the note is void at the next kf_preprocess; same bits).
+ *   kf_slab_ray_normals_color                 both uses in one: with dev_ta_own / dev_spec it copies the speculated 4 words where the context's own
+ *                                             word won and evaluates gradient AND colour for the vertices it owns under another context's crossing;
+ *                                             with both NULL it evaluates every vertex it owns.  dev_cand: 4 words per pixel, zeros elsewhere.
+ *   kf_set_model_maps_rays_color              kf_set_model_maps_rays from 4-word candidates; also writes KF_MAP_RAYCAST_RGB from the fourth word, whatever
+ *                                             the normal.  Every pixel of the three maps is written.
+ * Colour excludes deferred weights (kf_set_defer): a colour context runs the plain fusion kernel at every volume size. */
+int kf_raycast_volume_slab_cross_spec_color(kf_ctx* ctx, const kf_mat44* transform, const kf_raycast_params* raycast_params, const kf_camera_params* depth_camera,
+                                            float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec);
+int kf_slab_ray_normals_color(kf_ctx* ctx, const kf_mat44* transform, const kf_raycast_params* raycast_params, const kf_camera_params* depth_camera,
+                              float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand);
+int kf_set_model_maps_rays_color(kf_ctx* ctx, const kf_mat44* transform, const kf_camera_params* depth_camera, const uint64_t* dev_ta_min, const float* dev_cand);
 /* MAP FORM of the merge (the earlier protocol, kept for per-kernel tests): the slab that meets a crossing evaluates the whole hit itself -- dev_t[px] =
  * the crossing's ray parameter (+inf if none), dev_v / dev_n[px] = float4 vertex / normal (zeros when the march gives up there) -- and the caller keeps,
  * per pixel, the entry with the smallest t (kf_slab_mask_candidates zeroes the losers for an integer SUM).  It drops the rare pixel whose extrapolated

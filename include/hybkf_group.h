@@ -15,6 +15,15 @@
  *   7. kf_slab_ray_normals_spec
  *   8. integer SUM all-reduce of the 3-word normal candidates
  *   9. kf_set_model_maps_rays        -> every member holds the merged model maps (and levels 1, 2 of their pyramids)
+ * A COLOUR group (kf_group_create_color, base->has_color = 1; frames through kf_group_frame_color / kf_group_frame_members_color) runs the same nine
+ * steps in their colour forms, still with two collectives:
+ *   1. depth and BGR in   the BGR frame is copied once per device like the depth frame; kf_set_rgb_device
+ *   4. kf_integrate_volume(has_color = 1, use_angle_weight_color)   (colour excludes deferred weights: the plain fusion kernel at every size)
+ *   5. kf_raycast_volume_slab_cross_spec_color     4 speculative words per pixel: the normal, then the colour at the vertex
+ *   7. kf_slab_ray_normals_color                   the vertex's owner contributes normal AND colour (a pixel without a normal may have a colour)
+ *   8. integer SUM all-reduce of 4 words per pixel
+ *   9. kf_set_model_maps_rays_color                -> model maps and KF_MAP_RAYCAST_RGB on every member
+ * and kf_group_marching_cubes extracts with colour.
  * with near / far planes trunc_min / trunc_max.  No host synchronisation and no memset / memcpy of a per-frame buffer inside
  * kf_group_frame: the kernels write every pixel of their outputs.
  *
@@ -67,7 +76,7 @@ int kf_group_unique_id(uint8_t out[128]);
  *   RCCL_RANK: members = 1 and z_cuts = {z0, z1}, this rank's own slab: multiples of 8, z0 < z1 <= resolution, z0 = 0 exactly for rank 0
  *   and z1 = resolution exactly for rank world - 1 (every rank passes its own pair; the pairs of ranks 0 .. world-1 must tile the volume);
  *   halo (0: computed) not thinner than ceil(ray_increment / voxel) + 2 rounded up to 8 layers (pipeline.slab_halo_layers);
- *   base->has_color == 0 (the slab raycast has no colour);
+ *   base->has_color == 0 (colour: kf_group_create_color);
  *   devices (NULL: base->device for every member): LOCAL all equal, RCCL_ALL all distinct, RCCL_RANK exactly one member;
  *   unique_id / rank < world only for RCCL_RANK (ignored otherwise).
  * base->slab_* are ignored: each member's slab comes from z_cuts. */
@@ -76,6 +85,13 @@ int kf_group_create(const kf_config* base, const kf_group_params* params, int ba
 /* the same checks alone, without creating anything (no HIP or RCCL call): 0 or KF_GROUP_ERR_ARG */
 int kf_group_validate(const kf_config* base, const kf_group_params* params, int backend, uint32_t members, const uint32_t* z_cuts,
                       const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world);
+/* A COLOUR group: the arguments of kf_group_create / kf_group_validate plus the colour weighting switch of kf_integrate_volume.  The same checks, except:
+ * base->has_color == 1 and a non-empty base->rgb_camera are REQUIRED (KF_GROUP_ERR_ARG otherwise).  kf_group_create / kf_group_validate keep refusing colour. */
+int kf_group_create_color(const kf_config* base, const kf_group_params* params, int use_angle_weight_color, int backend, uint32_t members,
+                          const uint32_t* z_cuts, const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world,
+                          kf_group** out);
+int kf_group_validate_color(const kf_config* base, const kf_group_params* params, int use_angle_weight_color, int backend, uint32_t members,
+                            const uint32_t* z_cuts, const int32_t* devices, uint32_t halo, const uint8_t* unique_id, uint32_t rank, uint32_t world);
 int kf_group_destroy(kf_group* g);
 int kf_group_members(kf_group* g, uint32_t* members, uint32_t* halo);
 /* every member's device-resident pose (kf_set_pose).  kf_group_create already sets HybKinectfu::init's: identity rotation, camera at
@@ -88,13 +104,19 @@ int kf_group_set_pose(kf_group* g, const kf_mat44* pose);
 int kf_group_frame(kf_group* g, const uint16_t* mm, int on_device, uint32_t cols, uint32_t rows, uint32_t frame_id);
 /* the same with one device frame per member (RCCL_ALL across devices: each member reads the copy on its own device) */
 int kf_group_frame_members(kf_group* g, const uint16_t* const* dev_mm, uint32_t cols, uint32_t rows, uint32_t frame_id);
+/* The frame calls of a colour group: the same with the frame's BGR image (3 bytes per pixel, base->rgb_camera's size), which lies where the depth frame
+ * lies -- host memory copied once per device (on_device = 0), or device memory every member can read / one device image per member.  cols, rows are the
+ * depth frame's.  A colour group refuses kf_group_frame / kf_group_frame_members and a colourless group refuses these two with KF_GROUP_ERR_STATE: nothing
+ * is enqueued, no collective is issued, and the group stays usable. */
+int kf_group_frame_color(kf_group* g, const uint16_t* mm, const uint8_t* bgr, int on_device, uint32_t cols, uint32_t rows, uint32_t frame_id);
+int kf_group_frame_members_color(kf_group* g, const uint16_t* const* dev_mm, const uint8_t* const* dev_bgr, uint32_t cols, uint32_t rows, uint32_t frame_id);
 /* member 0's kf_read_track_result (blocking).  check_lockstep: also compare every member's pose bits, verdict, status and
  * frames fused / lost with member 0's; a disagreement returns KF_GROUP_ERR_STATE (in-process members only: a RCCL_RANK
  * group compares nothing across processes). */
 int kf_group_track_result(kf_group* g, kf_track_result* out, int check_lockstep);
 /* borrowed: for read-backs (maps, volume, stats).  The group owns the context and its stream; do not destroy it or change its stream. */
 int kf_group_member(kf_group* g, uint32_t i, kf_ctx** out);
-/* kf_marching_cubes on every member (each extracts its own layers) */
+/* kf_marching_cubes on every member (each extracts its own layers); a colour group extracts with colour */
 int kf_group_marching_cubes(kf_group* g, float threshold);
 int kf_group_triangle_count(kf_group* g, uint32_t* count);                                     /* sum over the members, blocking */
 /* triangles [first, first + count) of the slab-major sequence: member 0's, then member 1's, ... = the whole volume's canonical order */
