@@ -757,8 +757,7 @@ extern "C" int kf_get_volume_stats(kf_ctx* c, kf_volume_stats* out) {
   // (0.25 ms at 512^3, 1.5 ms at 1024^3, 12 ms at 2048^3); one that asks again within 8 fused frames switches the fusion launches to their COUNT instantiations,
   // which add the voxels they observe for the first time to KfCounters::wgt0_shard (+3.6 us per frame at 512^3): from then on the count is a read-back.
   // KF_OBSERVED_COUNT=0: always sweep; 1: track from the first question on.
-  static int mode_env = -2;
-  if (mode_env == -2) { const char* e = getenv("KF_OBSERVED_COUNT"); mode_env = e ? atoi(e) : -1; }
+  const int mode_env = kf_switch(KF_SW_OBSERVED_COUNT);
   const bool frequent = c->wgt0_asked_before && c->wgt0_frames_unasked <= 8;
   c->wgt0_asked_before = 1; c->wgt0_frames_unasked = 0;
   if (mode_env == 0) c->wgt0_tracking = 0;

@@ -12,8 +12,6 @@
 //     updated-voxel count and the tsdf/weight bits match the CPU oracle exactly;
 //   * per-brick flags (observed / has-negative) are maintained here; raycast and marching cubes use them to skip space.
 #include "kf_internal.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
 #include <string.h>
 
 #include "cull.h"                 // IntegrateArgs, the cull's test of a macro cell (shared with the tracking launch's tail)
@@ -928,20 +926,14 @@ __global__ void __launch_bounds__(256) k_exp_brick_rmw(IntegrateArgs a) {
 }
 #endif
 
-static inline KfCam to_cam(const kf_camera_params* p) {
-  KfCam c; c.cols = (int)p->cols; c.rows = (int)p->rows; c.cx = p->cx; c.cy = p->cy; c.fx = p->fx; c.fy = p->fy; return c;
-}
-
 // Does this context defer whole-quarter free-space weight updates?  kf_set_defer(ctx, 0 | 1) decides when called; otherwise KF_INTEGRATE_SAT
 // (0: never, 2: always) and, by default, the volume's resolution: 768^3 and finer.  Measured on Scene S (profiles/r04_deferred_weights.txt, same
 // box): 1024^3 @ 6 m 1.83 k -> 2.67 k frames/s, 2048^3 @ 8 m 356 -> 663, but 512^3 @ 4 m with the stock 2 m integration gate 4.98 k -> 4.89 k --
 // there the fusion pass is start-up + instruction issue, not memory, two thirds of its waves are silhouette / band waves that
 // cannot defer, and the deferred form's bookkeeping (+2 us kernel, +1.4 us cull) is all that shows.  Results are bit-identical either way.
 bool kf_defer_enabled(const kf_ctx* c) {
-  static int sat_env = -1, pairs_env = -1;
-  if (sat_env < 0) { const char* e = getenv("KF_INTEGRATE_SAT"); sat_env = e ? atoi(e) : 1; }
-  if (pairs_env < 0) { const char* e = getenv("KF_INTEGRATE_PAIRS"); pairs_env = e ? atoi(e) : 1; }
-  if (!pairs_env || !c->vol.pend || !(c->vol.max_weight >= 1.f && c->vol.max_weight <= KF_PEND_MAX_WEIGHT)) return false;
+  const int sat_env = kf_switch(KF_SW_INTEGRATE_SAT);
+  if (!kf_switch(KF_SW_INTEGRATE_PAIRS) || !c->vol.pend || !(c->vol.max_weight >= 1.f && c->vol.max_weight <= KF_PEND_MAX_WEIGHT)) return false;
   if (c->defer_override >= 0) return c->defer_override != 0;
   return sat_env == 2 || (sat_env == 1 && c->vol.res >= 768);
 }
@@ -980,7 +972,7 @@ extern "C" int kf_set_defer(kf_ctx* c, int mode) {
 // What the cull reads of IntegrateArgs, for the context's current depth map and the device-resident pose (shared with the tracking launch's tail, track.hip)
 void kf_fill_cull_args(kf_ctx* c, IntegrateArgs& a, const kf_camera_params* dcam, float sdf_trunc, float max_dist) {
   memset(&a, 0, sizeof(a));
-  a.vol = c->vol; a.dcam = to_cam(dcam); a.rcam = a.dcam;
+  a.vol = c->vol; a.dcam = kf_to_cam(dcam); a.rcam = a.dcam;
   a.depth = c->trunced_depth;
   a.tile_max = c->tile_max_depth; a.queue = c->active_bricks; a.cnt = c->counters;
   a.queue_cap = (unsigned)c->n_stored_bricks;
@@ -993,19 +985,21 @@ void kf_fill_cull_args(kf_ctx* c, IntegrateArgs& a, const kf_camera_params* dcam
   // The 8-pixel table is four times larger and colder in the cull's caches (+2 us per launch at VGA); it pays when bricks are
   // small on screen -- 1024^3 @ 6 m: 4 px at the far end, queue -7 %, fusion -10 us -- not at 512^3 @ 4 m (16 px, -3 %, -0.4 us).
   a.fine_tiles = (8.f * c->vol.cell * a.dcam.fx / (a.max_dist > 0.f ? a.max_dist : 1.f)) < 12.f ? 1 : 0;
-  { static int fe = -2; if (fe == -2) { const char* e = getenv("KF_CULL_FINE"); fe = e ? atoi(e) : -1; } if (fe >= 0) a.fine_tiles = fe; }      // A/B
+  if (kf_switch(KF_SW_CULL_FINE) >= 0) a.fine_tiles = kf_switch(KF_SW_CULL_FINE);      // A/B
   a.fr_slope[0] = (-1.f - a.dcam.cx) / a.dcam.fx; a.fr_slope[1] = ((float)a.dcam.cols - a.dcam.cx) / a.dcam.fx;
   a.fr_slope[2] = (-1.f - a.dcam.cy) / a.dcam.fy; a.fr_slope[3] = ((float)a.dcam.rows - a.dcam.cy) / a.dcam.fy;
   for (int i = 0; i < 4; ++i) a.fr_norm[i] = sqrtf(1.f + a.fr_slope[i] * a.fr_slope[i]);
   a.tinv = c->track->pose_inv; a.track = c->track;       // kept current by whoever commits the device-resident pose
   a.parity = c->int_parity;
   a.n_tile_floats = c->n_tile_floats;
-  { static int md = -1; if (md < 0) { const char* e = getenv("KF_CULL_MACRO_DEPTH"); md = e ? atoi(e) : 1; } a.macro_depth = md; }
+  a.macro_depth = kf_switch(KF_SW_CULL_MACRO_DEPTH);
 }
-bool kf_cull_tail_fits(const kf_ctx* c, int n_wg, int waves) {
+// macro cells of the stored slab: what a cull looks at
+static long long cull_macro_cells(const kf_ctx* c) {
   const int nmxy = (c->vol.nb + 3) >> 2, nmz = ((c->vol.bz1 + 3) >> 2) - (c->vol.bz0 >> 2);
-  return (long long)nmxy * nmxy * nmz <= (long long)n_wg * waves * CULL_TAIL_ROUNDS;
+  return (long long)nmxy * nmxy * nmz;
 }
+bool kf_cull_tail_fits(const kf_ctx* c, int n_wg, int waves) { return cull_macro_cells(c) <= (long long)n_wg * waves * CULL_TAIL_ROUNDS; }
 extern "C" int kf_cull_tail_counts(kf_ctx* c, uint32_t* consumed, uint32_t* undone) {
   if (!c) return KF_ERR_ARG;
   if (consumed) *consumed = c->tail_cull.consumed;
@@ -1025,6 +1019,98 @@ extern "C" int kf_get_fusion_form(kf_ctx* c, kf_fusion_form* out) {
   return 0;
 }
 
+struct FuseResidency { unsigned one, four; };             // workgroups of the fusion pass's one-brick / four-brick form the device holds at once (asked once per process)
+static void fuse_form(kf_fusion_form& f, int kernel, int br, bool d, bool c, bool l, bool n) { f.kernel = kernel; f.bricks = br; f.defer = d; f.color = c; f.layers = l; f.count = n; }
+// What one kf_integrate_volume launches, from the context's state, the call and the switches -- nothing is touched: cull (unless the tracking launch's
+// tail ran it), kernel, template switches, grid.  kf_get_fusion_form reports this value and fusion_launch / cull_launch launch from it.
+static kf_fusion_form fusion_plan(const kf_ctx* c, bool has_color, bool defer, bool defer_cull, bool tail_culled, bool layers, FuseResidency resident) {
+  kf_fusion_form f; memset(&f, 0, sizeof(f));
+  // large volumes: the macro cells are sifted one per lane first (k_integrate_cull_sift); KF_CULL_SIFT=0 / 1 forces either form
+  const int sift_env = kf_switch(KF_SW_CULL_SIFT);
+  f.cull = tail_culled ? KF_CULL_TAIL : (sift_env >= 0 ? sift_env != 0 : cull_macro_cells(c) >= 100000) ? KF_CULL_SIFT : KF_CULL_MACRO;
+  f.cull_defer = (!tail_culled && defer_cull) ? 1 : 0;
+  // Workgroups walking the queue.  Large volumes (>= 2^20 stored bricks: the queue holds >~100k bricks): four bricks in flight per workgroup and
+  // EIGHT TIMES as many workgroups as the chip holds at once (6 per CU x 256 = 1536 -> 12288: whole rounds; 8192 = 5.33 rounds ended on a third
+  // of the chip: 305.6 -> 297 us at 1024^3, every multiple of 1536 from 7680 to 15360 within 1 % of that).  Smaller ones: ONE brick in flight and exactly as many workgroups as the chip holds at once (8 per CU) -- at 512^3 the queue
+  // is ~9 k bricks, i.e. 2.2 rounds of 4.5 k two-brick workgroups of which the last is a fifth full; 2048 resident workgroups that each walk
+  // 4-5 bricks with the look-ahead end together: 20.0 -> 18.5 us at 512^3, 11.8 -> 9.6 us at 256^3, one box (at 1024^3 the same form loses: 324 vs
+  // 304 us).  KF_INTEGRATE_GRID / KF_INTEGRATE_BR override.
+  // DEFER: one brick in flight whatever the size -- most waves end without touching a voxel, so there is little memory latency to cover and
+  // the four-brick form's extra registers (85 VGPRs + scalar spills) only cost: 1024^3 181 -> 130 us, 2048^3 795 -> 577 us (BR 4 x 12288 vs
+  // BR 1 x 8192 workgroups; BR 1 x 2048 157, x 4096 135, x 16384 132 us at 1024^3: profiles/r04_deferred_weights.txt)
+  const bool big = c->n_stored_bricks >= ((size_t)1 << 20);
+  const int grid_env = kf_switch(KF_SW_INTEGRATE_GRID), br_env = kf_switch(KF_SW_INTEGRATE_BR);
+  const unsigned grid_cap = (grid_env >= 64 && grid_env <= 65536) ? (unsigned)grid_env
+                          : (defer ? (big ? 4u * resident.one : resident.one) : (big && !has_color ? 8u * resident.four : (has_color ? 8192u : resident.one)));
+  f.grid = (unsigned)(c->n_stored_bricks < grid_cap ? c->n_stored_bricks : grid_cap);
+  const bool br_forced = br_env == 1 || br_env == 2 || br_env == 4;
+  if (has_color) {                                         // KF_INTEGRATE_COLOR_PAIRS=0: the scalar kernel (A/B)
+    if (kf_switch(KF_SW_INTEGRATE_COLOR_PAIRS)) fuse_form(f, KF_FUSE_PAIRS, br_forced ? br_env : 2, false, true, false, false);
+    else fuse_form(f, KF_FUSE_BRICKS, 1, false, true, false, false);
+    return f;
+  }
+  const int em = KF_EXP_ENV(INTEGRATE_EXP);                // (0 in the product library)
+  if ((em >= 4 && em <= 7) || em == 12) return f;           // k_exp_brick_rmw stands in for the fusion pass: noted as KF_FUSE_NONE
+  const int br = br_forced ? br_env : ((big && !defer) ? 4 : 1);
+  const int pipe_env = kf_switch(KF_SW_INTEGRATE_PIPE);    // negative: decided per call
+  const bool count = c->wgt0_tracking && c->wgt0_valid;    // the COUNT instantiations, while a host keeps asking kf_get_volume_stats for the observed-voxel count
+  if (!kf_switch(KF_SW_INTEGRATE_PAIRS)) fuse_form(f, KF_FUSE_BRICKS, br, false, false, false, false);     // the scalar kernel (A/B)
+  else if (layers) fuse_form(f, KF_FUSE_PAIRS, 1, defer, false, true, false);                                // a sampled frame (kf_count_layer_work): the one-brick form that also counts per brick layer
+  else if (br == 1 && (pipe_env < 0 ? defer : pipe_env != 0)) fuse_form(f, KF_FUSE_PIPE, 1, defer, false, false, count);     // the one-brick form as a two-stage pipeline: by default where workgroups walk many bricks
+  else fuse_form(f, KF_FUSE_PAIRS, br, defer, false, false, count && (br == 1 || (br == 4 && !defer)));      // (the forms that have a COUNT instantiation)
+  return f;
+}
+
+static int cull_launch(kf_ctx* c, const kf_fusion_form& f, const IntegrateArgs& a) {      // the form's cull: each of the 4 instantiations named once
+  const unsigned n_macro = (unsigned)cull_macro_cells(c);
+  const int n_wg = (int)((n_macro + SIFT_CELLS - 1) / SIFT_CELLS);            // sifted: one macro cell per lane
+  const dim3 cgrid((n_macro + CULL_WAVES - 1) / CULL_WAVES);                   // otherwise one wave per macro cell, sixteen per workgroup
+  switch (f.cull * 2 + f.cull_defer) {
+    case KF_CULL_SIFT * 2 + 1: hipLaunchKernelGGL(k_integrate_cull_sift<true>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg); return 0;
+    case KF_CULL_SIFT * 2 + 0: hipLaunchKernelGGL(k_integrate_cull_sift<false>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg); return 0;
+    case KF_CULL_MACRO * 2 + 1: hipLaunchKernelGGL(k_integrate_cull<true>, cgrid, dim3(CULL_WAVES * 64), 0, c->stream, a); return 0;
+    case KF_CULL_MACRO * 2 + 0: hipLaunchKernelGGL(k_integrate_cull<false>, cgrid, dim3(CULL_WAVES * 64), 0, c->stream, a); return 0;
+  }
+  return KF_ERR_STATE;
+}
+static FuseResidency fuse_residency(const kf_ctx* c) {
+  static FuseResidency r = {0, 0};
+  if (!r.one) {
+    int per_cu = 0, per_cu4 = 0; hipDeviceProp_t prop;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_integrate_pairs<1, false>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 8;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_integrate_pairs<4, false>, 256, 0) != hipSuccess || per_cu4 < 1) per_cu4 = 6;
+    const unsigned cus = (hipGetDeviceProperties(&prop, c->cfg.device) == hipSuccess && prop.multiProcessorCount > 0) ? (unsigned)prop.multiProcessorCount : 256u;
+    r.four = cus * (unsigned)per_cu4; r.one = cus * (unsigned)per_cu;
+  }
+  return r;
+}
+static constexpr int FUSE_KEY(int kind, int br, int d, int c, int l, int n) { return (kind << 8) | (br << 4) | (d << 3) | (c << 2) | (l << 1) | n; }
+// the form's fusion kernel: each of the 22 instantiations named once, keyed by the very template arguments it is noted with
+static int fusion_launch(kf_ctx* c, const kf_fusion_form& f, const KfKernelTimer& timer, const IntegrateArgs& a) {
+#define FUSE_CASE(KEY, ...) case KEY: kf_launch(timer, __VA_ARGS__, dim3(f.grid), dim3(256), 0, c->stream, a); return 0;
+#define FUSE_PAIRS(BR_, D_, C_, L_, N_) FUSE_CASE(FUSE_KEY(KF_FUSE_PAIRS, BR_, D_, C_, L_, N_), k_integrate_pairs<BR_, D_, C_, L_, N_>)
+#define FUSE_PIPE(D_, N_) FUSE_CASE(FUSE_KEY(KF_FUSE_PIPE, 1, D_, 0, 0, N_), k_integrate_pairs_pipe<D_, N_>)
+#define FUSE_BRICKS(C_, BR_) FUSE_CASE(FUSE_KEY(KF_FUSE_BRICKS, BR_, 0, C_, 0, 0), k_integrate_bricks<C_, BR_>)
+  switch (FUSE_KEY(f.kernel, f.bricks, f.defer, f.color, f.layers, f.count)) {
+    FUSE_PAIRS(1, 0, 1, 0, 0) FUSE_PAIRS(2, 0, 1, 0, 0) FUSE_PAIRS(4, 0, 1, 0, 0)                                  // colour
+    FUSE_BRICKS(1, 1)
+    FUSE_PAIRS(1, 1, 0, 1, 0) FUSE_PAIRS(1, 0, 0, 1, 0)                                                            // layer counts
+    FUSE_PIPE(1, 1) FUSE_PIPE(1, 0) FUSE_PIPE(0, 1) FUSE_PIPE(0, 0)
+    FUSE_PAIRS(1, 1, 0, 0, 1) FUSE_PAIRS(1, 1, 0, 0, 0) FUSE_PAIRS(2, 1, 0, 0, 0) FUSE_PAIRS(4, 1, 0, 0, 0)        // deferring
+    FUSE_PAIRS(1, 0, 0, 0, 1) FUSE_PAIRS(1, 0, 0, 0, 0) FUSE_PAIRS(2, 0, 0, 0, 0) FUSE_PAIRS(4, 0, 0, 0, 1) FUSE_PAIRS(4, 0, 0, 0, 0)
+    FUSE_BRICKS(0, 1) FUSE_BRICKS(0, 2) FUSE_BRICKS(0, 4)
+#ifdef KF_EXPERIMENTS
+    case 0: switch (a.exp_mode) {
+        FUSE_CASE(4, k_exp_brick_rmw<4, 0>) FUSE_CASE(5, k_exp_brick_rmw<4, 1>) FUSE_CASE(6, k_exp_brick_rmw<4, 2>) FUSE_CASE(7, k_exp_brick_rmw<4, 3>) FUSE_CASE(12, k_exp_brick_rmw<4, 4>) }
+#endif
+  }
+#undef FUSE_BRICKS
+#undef FUSE_PIPE
+#undef FUSE_PAIRS
+#undef FUSE_CASE
+  return KF_ERR_STATE;
+}
+
 extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weight_color, const kf_mat44* transform,
                                    const kf_integrate_params* ip, const kf_camera_params* dcam, const kf_camera_params* rcam) {
   if (!c || !ip || !dcam) return KF_ERR_ARG;
@@ -1032,20 +1118,17 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
   if (has_color && (!c->vol.color || !c->raw_rgb || !rcam)) return KF_ERR_STATE;
   IntegrateArgs a;
   kf_fill_cull_args(c, a, dcam, ip->sdf_truncation, ip->max_integrate_dist);
-  a.rcam = rcam ? to_cam(rcam) : a.dcam;
+  a.rcam = rcam ? kf_to_cam(rcam) : a.dcam;
   a.normals = c->new_n[0]; a.rgb = c->raw_rgb;
   a.has_color = has_color; a.color_angled = use_angle_weight_color;
-  { static int fs = -1; if (fs < 0) { const char* e = getenv("KF_INTEGRATE_FREESPACE"); fs = e ? atoi(e) : 1; }      // 0: always form the quotients (A/B)
-    a.free_ok = (fs && a.sdf_trunc > 0.f) ? 1 : 0; }
-  { static int em = -1; if (em < 0) em = KF_EXP_ENV("KF_INTEGRATE_EXP"); a.exp_mode = em; }
-  if (transform) {
+  a.free_ok = (kf_switch(KF_SW_INTEGRATE_FREESPACE) && a.sdf_trunc > 0.f) ? 1 : 0;      // 0: always form the quotients (A/B)
+  a.exp_mode = KF_EXP_ENV(INTEGRATE_EXP);
+  if (transform) {                                       // (otherwise the device-resident pose, as kf_fill_cull_args left it)
     kf_mat44_inverse(transform->m, a.tinv_val.m);        // integrateVolume.cu:84, same arithmetic as on the device
     a.tinv = nullptr; a.track = nullptr;
-  } else {
-    a.tinv = c->track->pose_inv; a.track = c->track;     // kept current by whoever commits the device-resident pose
   }
-  a.layer_work = nullptr;
-  if (c->layer_work_frames > 0 && c->layer_work) { a.layer_work = c->layer_work; --c->layer_work_frames; }
+  a.layer_work = (c->layer_work_frames > 0 && c->layer_work) ? c->layer_work : nullptr;
+  if (a.layer_work) --c->layer_work_frames;
   a.parity = c->int_parity; c->last_parity = c->int_parity; c->int_parity ^= 1;
   a.clear_tiles = 1; a.n_tile_floats = c->n_tile_floats;
   // deferred free-space weights (k_integrate_pairs<.., DEFER>): the packed-pair kernel without colour.  Any other fusion kernel knows nothing of
@@ -1053,139 +1136,38 @@ extern "C" int kf_integrate_volume(kf_ctx* c, int has_color, int use_angle_weigh
   const bool defer = !has_color && kf_defer_enabled(c);
   const bool legacy_over_words = !defer && c->pend_live;
   if (legacy_over_words) { const int fs = kf_flush_pending(c); if (fs) return fs; }
-  a.defer_cull = 0;                                      // decided below, once it is known whether the tile minima describe this depth map
   kf_evt_begin(c, KF_STAGE_INTEGRATE);
   // tile maxima: normally left behind by the fused preprocess kernel for exactly this depth map and distance
   const bool tiles_ready = c->tile_serial != 0 && c->tile_serial == c->trunc_serial && c->tile_built_dist == a.max_dist;
   if (!tiles_ready) { hipLaunchKernelGGL(k_integrate_prepare, dim3(a.tile_w[1] * a.tile_h[1]), dim3(256), 0, c->stream, a); c->tile_min_serial = c->trunc_serial; }
-  a.defer_cull = (defer && c->tile_min_serial == c->trunc_serial) ? 1 : 0;     // whole-brick retirement needs the minima of THIS depth map
+  a.defer_cull = (defer && c->tile_min_serial == c->trunc_serial) ? 1 : 0;     // (0 until here) whole-brick retirement needs the minima of THIS depth map
   c->fuse_max_dist = a.max_dist;                         // what the next preprocess builds the tables for
   c->tile_serial = 0; c->tiles_clear = 1;                // the fusion pass below clears the tables behind the cull
   c->fp_tiles = 0;                                       // (tables a raycast launch may have built for a prefetched frame are cleared with them)
   // The cull may have run already, as the tail of this frame's tracking launch (kf_icp_track, persistent loop): consumed when it saw what this call
   // would have shown it -- the device-resident pose, the same parameters, depth map, tile tables, slab and counter set; otherwise undone.
   bool culled = false;
-  kf_fusion_form form; memset(&form, 0, sizeof(form));                       // (kf_get_fusion_form) what this call launches, noted where it is launched
   if (c->tail_cull.armed) {
     const auto& t = c->tail_cull;
     culled = !transform && !defer && tiles_ready && t.parity == a.parity && t.sdf_trunc == a.sdf_trunc && t.max_dist == a.max_dist &&
              memcmp(&t.dcam, dcam, sizeof(*dcam)) == 0 && t.trunc_serial == c->trunc_serial && t.bz0 == c->vol.bz0 && t.bz1 == c->vol.bz1;
-    if (culled) { c->tail_cull.armed = 0; c->tail_cull.consumed++; form.cull = KF_CULL_TAIL; }
+    if (culled) { c->tail_cull.armed = 0; c->tail_cull.consumed++; }
     else { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
   }
   c->cull_hint.valid = transform ? 0 : 1;                // what the next tracking launch may cull for
   c->cull_hint.sdf_trunc = a.sdf_trunc; c->cull_hint.max_dist = a.max_dist; c->cull_hint.dcam = *dcam;
-  if (!culled) {
-    const int nmxy = (c->vol.nb + 3) >> 2, nmz = ((c->vol.bz1 + 3) >> 2) - (c->vol.bz0 >> 2);
-    const unsigned n_macro = (unsigned)nmxy * nmxy * nmz;                      // one wave per macro cell, sixteen per workgroup
-    const unsigned cgrid = (n_macro + CULL_WAVES - 1) / CULL_WAVES;
-    // large volumes: the macro cells are sifted one per lane first (k_integrate_cull_sift); KF_CULL_SIFT=0 / 1 forces either form
-    static int sift_env = -2;
-    if (sift_env == -2) { const char* e = getenv("KF_CULL_SIFT"); sift_env = e ? atoi(e) : -1; }
-    const bool sift = sift_env >= 0 ? sift_env != 0 : n_macro >= 100000u;
-    const int n_wg = (int)((n_macro + SIFT_CELLS - 1) / SIFT_CELLS);
-    form.cull = sift ? KF_CULL_SIFT : KF_CULL_MACRO; form.cull_defer = a.defer_cull ? 1 : 0;
-    if (sift && a.defer_cull) hipLaunchKernelGGL(k_integrate_cull_sift<true>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg);
-    else if (sift) hipLaunchKernelGGL(k_integrate_cull_sift<false>, dim3(n_wg), dim3(SIFT_THREADS), 0, c->stream, a, n_wg);
-    else if (a.defer_cull) hipLaunchKernelGGL(k_integrate_cull<true>, dim3(cgrid), dim3(CULL_WAVES * 64), 0, c->stream, a);
-    else hipLaunchKernelGGL(k_integrate_cull<false>, dim3(cgrid), dim3(CULL_WAVES * 64), 0, c->stream, a);
-  }
-  // Workgroups walking the queue.  Large volumes (>= 2^20 stored bricks: the queue holds >~100k bricks): four bricks in flight per workgroup and
-  // EIGHT TIMES as many workgroups as the chip holds at once (6 per CU x 256 = 1536 -> 12288: whole rounds; 8192 = 5.33 rounds ended on a third
-  // of the chip: 305.6 -> 297 us at 1024^3, every multiple of 1536 from 7680 to 15360 within 1 % of that).  Smaller ones: ONE brick in flight and exactly as many workgroups as the chip holds at once (8 per CU) -- at 512^3 the queue
-  // is ~9 k bricks, i.e. 2.2 rounds of 4.5 k two-brick workgroups of which the last is a fifth full; 2048 resident workgroups that each walk
-  // 4-5 bricks with the look-ahead end together: 20.0 -> 18.5 us at 512^3, 11.8 -> 9.6 us at 256^3, one box (at 1024^3 the same form loses: 324 vs
-  // 304 us).  KF_INTEGRATE_GRID / KF_INTEGRATE_BR override.
-  static unsigned grid_env = 0, resident = 0, resident4 = 0;
-  if (!grid_env) { const char* e = getenv("KF_INTEGRATE_GRID"); grid_env = e ? (unsigned)atoi(e) : 1u; if (grid_env != 1u && (grid_env < 64u || grid_env > 65536u)) grid_env = 1u; }
-  if (!resident) {
-    int per_cu = 0; hipDeviceProp_t prop;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_integrate_pairs<1, false>, 256, 0) != hipSuccess || per_cu < 1) per_cu = 8;
-    const unsigned cus = (hipGetDeviceProperties(&prop, c->cfg.device) == hipSuccess && prop.multiProcessorCount > 0) ? (unsigned)prop.multiProcessorCount : 256u;
-    resident = cus * (unsigned)per_cu;
-    int per_cu4 = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu4, k_integrate_pairs<4, false>, 256, 0) != hipSuccess || per_cu4 < 1) per_cu4 = 6;
-    resident4 = cus * (unsigned)per_cu4;
-  }
-  const bool big = c->n_stored_bricks >= ((size_t)1 << 20);
-  // DEFER: one brick in flight whatever the size -- most waves end without touching a voxel, so there is little memory latency to cover and
-  // the four-brick form's extra registers (85 VGPRs + scalar spills) only cost: 1024^3 181 -> 130 us, 2048^3 795 -> 577 us (BR 4 x 12288 vs
-  // BR 1 x 8192 workgroups; BR 1 x 2048 157, x 4096 135, x 16384 132 us at 1024^3: profiles/r04_deferred_weights.txt)
-  const unsigned grid_cap = grid_env != 1u ? grid_env : (defer ? (big ? 4u * resident : resident) : (big && !has_color ? 8u * resident4 : (has_color ? 8192u : resident)));
-  unsigned grid = (unsigned)(c->n_stored_bricks < grid_cap ? c->n_stored_bricks : grid_cap);
+  // (kf_get_fusion_form) what this call launches: the form is decided once, and the launches below come from it
+  kf_fusion_form form = fusion_plan(c, has_color != 0, defer, a.defer_cull != 0, culled, a.layer_work != nullptr, fuse_residency(c));
+  if (!culled) { const int cs = cull_launch(c, form, a); if (cs) return cs; }     // (defensive, here and below: fusion_plan gives no form without an instantiation)
   // the roofline kernel's live timer: the event pair rides on the dispatch itself (kf_evt_attach), so what is measured is the kernel, as rocprofv3 sees it
-  hipEvent_t ke0 = nullptr, ke1 = nullptr;
-  const bool timed = kf_evt_attach(c, KF_STAGE_INTEGRATE_KERNEL, &ke0, &ke1);
-  const bool count = c->wgt0_tracking && c->wgt0_valid;   // the COUNT instantiations, while a host keeps asking kf_get_volume_stats for the observed-voxel count
-#define FUSE_LAUNCH(K) do { if (timed) hipExtLaunchKernelGGL(K, dim3(grid), dim3(256), 0, c->stream, ke0, ke1, 0, a); \
-                            else hipLaunchKernelGGL(K, dim3(grid), dim3(256), 0, c->stream, a); } while (0)
-  // each instantiation is named once, and the form it is noted as comes from the same template arguments
-#define FUSE_NOTE(KIND, BR_, D_, C_, L_, N_) do { form.kernel = (KIND); form.bricks = (BR_); form.defer = (D_); form.color = (C_); form.layers = (L_); form.count = (N_); } while (0)
-#define FUSE_PAIRS(BR_, D_, C_, L_, N_) do { FUSE_NOTE(KF_FUSE_PAIRS, BR_, D_, C_, L_, N_); FUSE_LAUNCH((k_integrate_pairs<BR_, D_, C_, L_, N_>)); } while (0)
-#define FUSE_PIPE(D_, N_) do { FUSE_NOTE(KF_FUSE_PIPE, 1, D_, false, false, N_); FUSE_LAUNCH((k_integrate_pairs_pipe<D_, N_>)); } while (0)
-#define FUSE_BRICKS(C_, BR_) do { FUSE_NOTE(KF_FUSE_BRICKS, BR_, false, C_, false, false); FUSE_LAUNCH((k_integrate_bricks<C_, BR_>)); } while (0)
-  static int color_pairs = -1;                            // 1 (default): colour through the packed-pair kernel; 0: the scalar kernel (A/B)
-  if (color_pairs < 0) { const char* e = getenv("KF_INTEGRATE_COLOR_PAIRS"); color_pairs = e ? atoi(e) : 1; }
-  if (has_color && color_pairs) {
-    static int cbr = -1;                                   // bricks in flight per workgroup of the colour variant (KF_INTEGRATE_BR overrides)
-    if (cbr < 0) { const char* e = getenv("KF_INTEGRATE_BR"); cbr = e ? atoi(e) : 2; if (cbr != 1 && cbr != 2 && cbr != 4) cbr = 2; }
-    if (cbr == 1) FUSE_PAIRS(1, false, true, false, false);
-    else if (cbr == 2) FUSE_PAIRS(2, false, true, false, false);
-    else FUSE_PAIRS(4, false, true, false, false);
-  }
-  else if (has_color) FUSE_BRICKS(true, 1);
-  else {
-    // bricks in flight per workgroup (see the grid above): 1, or 4 for large volumes.  KF_INTEGRATE_BR overrides.
-    static int br_env = -1;
-    if (br_env < 0) { const char* e = getenv("KF_INTEGRATE_BR"); br_env = e ? atoi(e) : 0; if (br_env != 1 && br_env != 2 && br_env != 4) br_env = 0; }
-    const int br = br_env ? br_env : ((big && !defer) ? 4 : 1);
-    static int pipe_env = -1;
-    if (pipe_env == -1) { const char* e = getenv("KF_INTEGRATE_PIPE"); pipe_env = e ? atoi(e) : -2; }     // -2: decided per call below
-    static int pairs = -1;                               // 1 (default): the packed-pair kernel; 0: the scalar one (A/B and colour path)
-    if (pairs < 0) { const char* e = getenv("KF_INTEGRATE_PAIRS"); pairs = e ? atoi(e) : 1; }
-#ifdef KF_EXPERIMENTS
-    if (a.exp_mode == 4) FUSE_LAUNCH((k_exp_brick_rmw<4, 0>));
-    else if (a.exp_mode == 5) FUSE_LAUNCH((k_exp_brick_rmw<4, 1>));
-    else if (a.exp_mode == 6) FUSE_LAUNCH((k_exp_brick_rmw<4, 2>));
-    else if (a.exp_mode == 7) FUSE_LAUNCH((k_exp_brick_rmw<4, 3>));
-    else if (a.exp_mode == 12) FUSE_LAUNCH((k_exp_brick_rmw<4, 4>));
-    else
-#endif
-    if (pairs && a.layer_work) {                           // a sampled frame (kf_count_layer_work): the one-brick form that also counts per brick layer
-      if (defer) FUSE_PAIRS(1, true, false, true, false);
-      else FUSE_PAIRS(1, false, false, true, false);
-    } else if (pairs && br == 1 && (pipe_env < 0 ? defer : pipe_env != 0)) {     // the one-brick form as a two-stage pipeline: by default where workgroups walk many bricks (KF_INTEGRATE_PIPE=0 / 1 forces)
-      if (defer && count) FUSE_PIPE(true, true);
-      else if (defer) FUSE_PIPE(true, false);
-      else if (count) FUSE_PIPE(false, true);
-      else FUSE_PIPE(false, false);
-    } else if (pairs) {
-      if (defer) {
-        if (br == 1 && count) FUSE_PAIRS(1, true, false, false, true);
-        else if (br == 1) FUSE_PAIRS(1, true, false, false, false);
-        else if (br == 2) FUSE_PAIRS(2, true, false, false, false);
-        else FUSE_PAIRS(4, true, false, false, false);
-      } else if (br == 1 && count) FUSE_PAIRS(1, false, false, false, true);
-      else if (br == 1) FUSE_PAIRS(1, false, false, false, false);
-      else if (br == 2) FUSE_PAIRS(2, false, false, false, false);
-      else if (count) FUSE_PAIRS(4, false, false, false, true);
-      else FUSE_PAIRS(4, false, false, false, false);
-    } else if (br == 1) FUSE_BRICKS(false, 1);
-    else if (br == 2) FUSE_BRICKS(false, 2);
-    else FUSE_BRICKS(false, 4);
-  }
-#undef FUSE_BRICKS
-#undef FUSE_PIPE
-#undef FUSE_PAIRS
-#undef FUSE_NOTE
-#undef FUSE_LAUNCH
-  form.grid = grid; form.calls = c->fusion_form.calls + 1;
-  c->fusion_form = form;
+  KfKernelTimer timer; timer.on = kf_evt_attach(c, KF_STAGE_INTEGRATE_KERNEL, &timer.e0, &timer.e1);
+  { const int ls = fusion_launch(c, form, timer, a); if (ls) return ls; }
+  form.calls = c->fusion_form.calls + 1; c->fusion_form = form;
   // the running count of observed voxels (kf_get_volume_stats): a fusion launch that did not count leaves it behind the volume
   if (!form.count) c->wgt0_valid = 0;
   if (c->wgt0_frames_unasked < (1 << 30)) ++c->wgt0_frames_unasked;
   if (c->wgt0_tracking && c->wgt0_frames_unasked > 64) c->wgt0_tracking = 0;        // nobody has asked for 64 frames: the plain kernels again
-  if (timed) kf_evt_attached_done(c, KF_STAGE_INTEGRATE_KERNEL);
+  if (timer.on) kf_evt_attached_done(c, KF_STAGE_INTEGRATE_KERNEL);
   kf_evt_end(c, KF_STAGE_INTEGRATE);
   if (defer) c->pend_live = 1;
   if (legacy_over_words) { KF_CHECK(hipMemsetAsync(c->vol.pend, 0, c->n_stored_bricks * sizeof(unsigned long long), c->stream)); c->pend_live = 0; }

@@ -5,9 +5,11 @@
 // equal the reference's C++ semantics (see DESIGN.md "Parity").  Citations are relative to /root/reference.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stddef.h>
 #include "../../include/hybkf.h"
+#include "kf_switches.h"
 
 #define KF_BRICK 8                 // voxels per brick edge
 #define KF_BRICK_VOX 512           // voxels per brick: 4 KiB of (tsdf, weight) pairs, contiguous in HBM
@@ -35,13 +37,11 @@
 // libhybkf_exp.so, loaded by tools/ via KF_LIB).  In the product library the mode is the constant 0: the branches fold away
 // and the environment is never consulted for them.
 #ifdef KF_EXPERIMENTS
-#include <stdlib.h>
-static inline int kf_exp_env(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
 #define KF_EXP_MODE(a) ((a).exp_mode)
-#define KF_EXP_ENV(name) kf_exp_env(name)
+#define KF_EXP_ENV(id) kf_switch(KF_SW_##id)
 #else
 #define KF_EXP_MODE(a) 0
-#define KF_EXP_ENV(name) 0
+#define KF_EXP_ENV(id) 0
 #endif
 
 #define KF_PINNED_STALL_WORD 2048
@@ -260,6 +260,30 @@ static inline size_t kf_negbit_words(size_t n_bricks) { return ((n_bricks + 127)
 // ------------------------------------------------------------------------------------------------------------------
 struct KfMat { float m[16]; };
 struct KfCam { int cols, rows; float cx, cy, fx, fy; };
+
+// ---- host helpers the stage entry points share ---------------------------------------------------------------------
+static inline KfCam kf_to_cam(const kf_camera_params* p) {
+  KfCam c; c.cols = (int)p->cols; c.rows = (int)p->rows; c.cx = p->cx; c.cy = p->cy; c.fx = p->fx; c.fy = p->fy; return c;
+}
+// a kernel's pose pair: the caller's transform by value (pose null), or the context's device-resident pose
+static inline void kf_pose_arg(const kf_ctx* c, const kf_mat44* transform, const float*& pose, KfMat& pose_val) {
+  if (transform) { for (int i = 0; i < 16; ++i) pose_val.m[i] = transform->m[i]; pose = nullptr; }
+  else pose = c->track->pose;
+}
+// levels 1 and 2 of a map set as a kernel's pyramid outputs (KfPyrOut, bilateral_tile.h) for a cols x rows level 0
+template <typename PyrOut>
+static inline void kf_pyr_arg(PyrOut& o, float4* const* v, float4* const* n, int cols, int rows) {
+  o.v1 = v[0]; o.n1 = n[0]; o.v2 = v[1]; o.n2 = n[1];
+  o.c1 = cols >> 1; o.r1 = rows >> 1; o.c2 = o.c1 >> 1; o.r2 = o.r1 >> 1;
+}
+// One launch, timed by its own dispatch when an event pair was attached (kf_evt_attach: the pair rides on hipExtLaunchKernelGGL), plain otherwise.
+// The caller closes a timed launch with kf_evt_attached_done.
+struct KfKernelTimer { hipEvent_t e0 = nullptr, e1 = nullptr; bool on = false; };
+template <typename Kernel, typename... Args>
+static inline void kf_launch(const KfKernelTimer& t, Kernel kernel, dim3 grid, dim3 block, size_t lds, hipStream_t stream, const Args&... args) {
+  if (t.on) hipExtLaunchKernelGGL(kernel, grid, block, (unsigned)lds, stream, t.e0, t.e1, 0, args...);
+  else hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+}
 
 __device__ __forceinline__ float3 kf3(float x, float y, float z) { return make_float3(x, y, z); }
 __device__ __forceinline__ float3 kf_sub(float3 a, float3 b) { return kf3(a.x - b.x, a.y - b.y, a.z - b.z); }

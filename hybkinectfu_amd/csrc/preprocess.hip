@@ -7,11 +7,6 @@
 #include "kf_internal.h"
 #include "bilateral_tile.h"
 #include <string.h>
-#include <stdlib.h>
-
-static inline KfCam to_cam(const kf_camera_params* p) {
-  KfCam c; c.cols = (int)p->cols; c.rows = (int)p->rows; c.cx = p->cx; c.cy = p->cy; c.fx = p->fx; c.fy = p->fy; return c;
-}
 
 // DataPreprocesser.cu:17-36: keep d iff trunc_min < d < trunc_max (strict both sides)
 __global__ void __launch_bounds__(256) k_trunc_depth(const float* __restrict__ in, float* __restrict__ out, int n, float tmin, float tmax) {
@@ -197,7 +192,7 @@ extern "C" int kf_calculate_new_vertices(kf_ctx* c, const kf_camera_params* cam)
   if (!c || !cam || (int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
   dim3 grid(kf_div_up(c->cols, 64), kf_div_up(c->rows, 4));
   c->new_pyr_ok = 0;
-  hipLaunchKernelGGL(k_depth_to_vertices, grid, dim3(256), 0, c->stream, c->filtered_depth, c->new_v[0], to_cam(cam));
+  hipLaunchKernelGGL(k_depth_to_vertices, grid, dim3(256), 0, c->stream, c->filtered_depth, c->new_v[0], kf_to_cam(cam));
   return (int)hipGetLastError();
 }
 
@@ -227,7 +222,7 @@ void kf_bilateral_args(kf_ctx* c, const uint16_t* mm, const float* raw_in, float
 }
 int kf_launch_vertices_normals(kf_ctx* c, hipStream_t stream, const float* filtered, float4* v0, float4* n0, const kf_camera_params* cam) {
   dim3 grid2(kf_div_up(c->cols, 64), kf_div_up(c->rows, 4));
-  hipLaunchKernelGGL(k_vertices_normals, grid2, dim3(256), 0, stream, filtered, v0, n0, to_cam(cam));
+  hipLaunchKernelGGL(k_vertices_normals, grid2, dim3(256), 0, stream, filtered, v0, n0, kf_to_cam(cam));
   return (int)hipGetLastError();
 }
 // the two fused launches of kf_preprocess on a given stream and buffer set
@@ -336,9 +331,7 @@ extern "C" int kf_prefetch_frame(kf_ctx* c, const uint16_t* dev_mm, uint32_t col
   }
   c->alt_pyr_ok = 0;
   { const int st = kf_upload_wait_for(c, dev_mm); if (st) return st; }   // a frame staged by kf_upload_depth_mm_next: its readers follow on this stream
-  static int fused = -1;                                   // KF_PREFETCH_FUSED=0: the side-stream form (events between two streams)
-  if (fused < 0) { const char* e = getenv("KF_PREFETCH_FUSED"); fused = e ? atoi(e) : 1; }
-  if (fused) {
+  if (kf_switch(KF_SW_PREFETCH_FUSED)) {                   // 0: the side-stream form (events between two streams)
     // only a note: the next kf_raycast_volume* launch carries the filter along and leaves the preprocessed set in the alternate buffers
     // (they were last read by the frame BEFORE the current one, which lies behind us on the stream)
     c->fp_src = dev_mm; c->fp_params[0] = tmin; c->fp_params[1] = tmax; c->fp_params[2] = sigma_pixel; c->fp_params[3] = sigma_depth;

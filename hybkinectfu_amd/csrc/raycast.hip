@@ -14,16 +14,13 @@
 #include "kf_internal.h"
 #include "bilateral_tile.h"
 #include "grad_shared.h"
-#include <hip/hip_ext.h>
-#include <stdlib.h>
 #include <string.h>
 
 // KF_RAYCAST_SHARED_GRAD (0 / 1 / 2, see RaycastArgs::shared_grad) in bits 0-7, KF_RAYCAST_VIEW_HALF (tests: brick layers of the gathers' view on either side, 0 = most) above.
-// Read at every launch (two getenv calls), unlike the other switches: a test can then compare the forms on ONE context -- the only way at 2048^3, where a second process
+// Read at every launch (uncached in kf_switches.h), unlike the other switches: a test can then compare the forms on ONE context -- the only way at 2048^3, where a second process
 // would have to fuse 69 GB again.
 static int rc_shared_grad_env() {
-  const char* e = getenv("KF_RAYCAST_SHARED_GRAD"); const char* h = getenv("KF_RAYCAST_VIEW_HALF");
-  const int mode = e ? atoi(e) : 1, half = h ? atoi(h) : 0;
+  const int mode = kf_switch(KF_SW_RAYCAST_SHARED_GRAD), half = kf_switch(KF_SW_RAYCAST_VIEW_HALF);
   return mode <= 0 ? 0 : ((mode & 255) | ((half > 0 && half < 4096 ? half : 0) << 8));
 }
 // the gathers' view spans at least two brick layers: they must fit 32-bit offsets (they do up to 724 bricks per axis; beyond: six separate lookups)
@@ -561,48 +558,36 @@ __global__ void __launch_bounds__(RAYCAST_THREADS) __attribute__((amdgpu_waves_p
   }
 }
 
-static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
-                          float near_plane, float far_plane, float* out_t, float4* out_v, float4* out_n, unsigned long long* out_ta = nullptr,
-                          unsigned long long* own_ta = nullptr, float* out_spec = nullptr, bool spec_color = false) {
-  if (!c || !rp || !cam) return KF_ERR_ARG;
-  if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
-  if (has_color && (!c->vol.color || !c->raycast_rgb)) return KF_ERR_STATE;
-  if (spec_color && (!c->vol.color || !out_ta || !own_ta || !out_spec)) return KF_ERR_STATE;
-  RaycastArgs a;
-  a.vol = c->vol;
-  a.cam.cols = (int)cam->cols; a.cam.rows = (int)cam->rows; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.fx = cam->fx; a.cam.fy = cam->fy;
-  if (transform) { for (int i = 0; i < 16; ++i) a.pose_val.m[i] = transform->m[i]; a.pose = nullptr; }
-  else a.pose = c->track->pose;
-  if (!out_ta && (!out_v || !out_n)) c->model_pyr_ok = 0;             // the model maps' level 0 is rewritten
+// What a raycast launch writes: the context's model maps (KF_RC_OUT_MAPS: no pointer set), or what RaycastArgs calls out_t / out_v / out_n (KF_RC_OUT_T), out_ta
+// (KF_RC_OUT_TA), out_ta / own_ta / out_spec (KF_RC_OUT_TA_SPEC; with `color` the speculation carries the colour word too: 4 words per pixel, a kernel of its own)
+struct RaycastOut { int output; bool color; float* t; float4* v; float4* n; unsigned long long* ta; unsigned long long* own_ta; float* spec; };
+
+// The kernel's arguments, the LDS tables' placement (lds: bytes the plain kernel needs) and the form's description, all from the same quantities
+static int raycast_args(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
+                        float near_plane, float far_plane, const RaycastOut& out, RaycastArgs& a, kf_raycast_form& form, size_t& lds) {
+  const bool maps = out.output == KF_RC_OUT_MAPS;
+  a.vol = c->vol; a.cam = kf_to_cam(cam);
+  kf_pose_arg(c, transform, a.pose, a.pose_val);
   memset(&a.pyr, 0, sizeof(a.pyr));
-  static int pyr_env = -1;
-  if (pyr_env < 0) { const char* e = getenv("KF_RAYCAST_PYRAMID"); pyr_env = e ? atoi(e) : 1; }
-  const bool model_pyr = pyr_env && !out_ta && !out_v && !out_n && c->levels == 3;      // the model maps themselves, stock pyramid depth
-  if (model_pyr) {
-    a.pyr.v1 = c->model_v[1]; a.pyr.n1 = c->model_n[1]; a.pyr.v2 = c->model_v[2]; a.pyr.n2 = c->model_n[2];
-    a.pyr.c1 = c->cols >> 1; a.pyr.r1 = c->rows >> 1; a.pyr.c2 = a.pyr.c1 >> 1; a.pyr.r2 = a.pyr.r1 >> 1;
-  }
-  a.out_v = out_v ? out_v : c->model_v[0]; a.out_n = out_n ? out_n : c->model_n[0]; a.out_rgb = c->raycast_rgb; a.out_t = out_t; a.out_ta = out_ta;
-  a.own_ta = own_ta; a.out_spec = (out_ta && own_ta) ? out_spec : nullptr;
+  const bool model_pyr = kf_switch(KF_SW_RAYCAST_PYRAMID) && maps && c->levels == 3;      // the model maps themselves, stock pyramid depth
+  if (model_pyr) kf_pyr_arg(a.pyr, c->model_v + 1, c->model_n + 1, c->cols, c->rows);
+  a.out_v = out.v ? out.v : c->model_v[0]; a.out_n = out.n ? out.n : c->model_n[0]; a.out_rgb = c->raycast_rgb; a.out_t = out.t; a.out_ta = out.ta;
+  a.own_ta = out.own_ta; a.out_spec = out.spec;
   a.inc = rp->ray_increment; a.near_plane = near_plane; a.far_plane = far_plane; a.has_color = has_color;
-  { static int em = -1; if (em < 0) em = KF_EXP_ENV("KF_RAYCAST_EXP"); a.exp_mode = em; }
-  { static int tb = -1; if (tb < 0) { const char* e = getenv("KF_RAYCAST_BOUNDS"); tb = e ? atoi(e) : 1; } a.tile_bounds = tb; }
-  { static int bm = -1; if (bm < 0) { const char* e = getenv("KF_RAYCAST_BOUNDS_MESO"); bm = e ? atoi(e) : 1; } a.bounds_meso = bm; }
-  a.shared_grad = rc_shared_grad_for(c->vol);
+  a.exp_mode = KF_EXP_ENV(RAYCAST_EXP);
+  a.tile_bounds = kf_switch(KF_SW_RAYCAST_BOUNDS); a.bounds_meso = kf_switch(KF_SW_RAYCAST_BOUNDS_MESO); a.shared_grad = rc_shared_grad_for(c->vol);
   a.work = c->count_work ? c->counters : nullptr;
   size_t macro_bytes = (size_t)(c->vol.macro_words + c->vol.super_words) * 4;
   const size_t neg_bytes = kf_negbit_words(c->n_stored_bricks) * 4, meso_bytes = (size_t)c->vol.meso_words * 4;
   if (macro_bytes > RAYCAST_LDS_BYTES) return KF_ERR_STATE;
-  static int meso_env = -1;
-  if (meso_env < 0) { const char* e = getenv("KF_RAYCAST_MESO"); meso_env = e ? atoi(e) : 1; }
-  a.meso_words = (meso_env && macro_bytes + meso_bytes <= RAYCAST_LDS_BYTES) ? c->vol.meso_words : 0;      // (2048^3: 256 KiB, no)
+  a.meso_words = (kf_switch(KF_SW_RAYCAST_MESO) && macro_bytes + meso_bytes <= RAYCAST_LDS_BYTES) ? c->vol.meso_words : 0;      // (2048^3: 256 KiB, no)
   macro_bytes += (size_t)a.meso_words * 4;                  // from here on: everything in front of the per-brick bits
-  static int neg_env = -1;                                  // KF_RAYCAST_NEG_LDS=0 (tests): brick flags from global memory at any size
-  if (neg_env < 0) { const char* e = getenv("KF_RAYCAST_NEG_LDS"); neg_env = e ? atoi(e) : 1; }
-  a.neg_words = (neg_env && macro_bytes + neg_bytes <= RAYCAST_LDS_BYTES) ? (int)(neg_bytes / 4) : 0;
-  // (kf_get_raycast_form) what this launch is, noted where its arguments are final; the kernel and the grid where it is launched
-  kf_raycast_form form; memset(&form, 0, sizeof(form));
-  form.output = out_ta ? (a.out_spec ? KF_RC_OUT_TA_SPEC : KF_RC_OUT_TA) : out_t ? KF_RC_OUT_T : KF_RC_OUT_MAPS;
+  a.neg_words = (kf_switch(KF_SW_RAYCAST_NEG_LDS) && macro_bytes + neg_bytes <= RAYCAST_LDS_BYTES) ? (int)(neg_bytes / 4) : 0;
+  const size_t pyr_lds = model_pyr ? (size_t)(32 * 16 + 16 * 8) * 2 * sizeof(float4) : 0;      // the tile's two maps and their level 1
+  lds = macro_bytes + (size_t)a.neg_words * 4 > pyr_lds ? macro_bytes + (size_t)a.neg_words * 4 : pyr_lds;
+  // (kf_get_raycast_form) what this launch is; the kernel and the grid are noted where it is launched
+  memset(&form, 0, sizeof(form));
+  form.output = out.output;
   form.tile_bounds = a.tile_bounds ? 1 : 0;
   if (a.tile_bounds) {                                      // rc_tile_bounds' choice, from the same quantities
     const int nq = c->vol.nq, nm = c->vol.nm;
@@ -612,74 +597,68 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
   form.meso_lds = a.meso_words != 0; form.neg_lds = a.neg_words != 0;
   form.shared_grad = a.shared_grad & 255; form.view_half = a.shared_grad >> 8; form.pyramid = model_pyr ? 1 : 0;
   form.calls = c->raycast_form.calls + 1;
+  return 0;
+}
+
+// kf_prefetch_frame left a note: the next frame's u16 -> f32 + gate + bilateral rides in this launch (k_raycast_prefetch), its vertices /
+// normals follow; the set lands in the alternate buffers and kf_preprocess adopts it when it is asked for exactly that frame
+struct RaycastRiders { KfBilateralArgs b; KfFrontTail ft; bool fast, build_tiles; int bil_gx, bil_tiles; size_t lds; };
+static void raycast_riders(kf_ctx* c, RaycastRiders& r) {
+  c->fp_pending = 0;
+  const int behind = c->fp_filtered; c->fp_filtered = 0;                 // the filter rode in the tracking launch: the tile tables and the vertices / normals are left
+  r.build_tiles = c->tiles_clear && c->fuse_max_dist > 0.f;               // the fusion pass of this frame has cleared the tables: they can be built for the next depth map
+  kf_bilateral_args(c, c->fp_src, nullptr, c->alt_raw, c->alt_trunced, c->alt_filtered, c->fp_params[0], c->fp_params[1], c->fp_params[2], c->fp_params[3],
+                    r.build_tiles, &r.b, &r.fast);
+  memset(&r.ft, 0, sizeof(r.ft));
+  r.ft.behind = behind;
+  if (behind) {
+    r.ft.out_v = c->alt_v0; r.ft.out_n = c->alt_n0;
+    if (c->levels == 3 && c->alt_v12[0]) kf_pyr_arg(r.ft.pyr, c->alt_v12, c->alt_n12, c->cols, c->rows);
+    r.ft.cam = kf_to_cam(&c->fp_cam);
+  }
+  r.bil_gx = kf_div_up(c->cols, BIL_TX); r.bil_tiles = r.bil_gx * kf_div_up(c->rows, BIL_TY);
+  r.lds = behind ? (size_t)RIDER_LDS_BYTES : 2 * (BIL_TX + 8) * (BIL_TY + 8) * sizeof(float);
+}
+
+static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
+                          float near_plane, float far_plane, const RaycastOut& out) {
+  if (!c || !rp || !cam) return KF_ERR_ARG;
+  if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
+  if (has_color && (!c->vol.color || !c->raycast_rgb)) return KF_ERR_STATE;
+  if (out.color && !c->vol.color) return KF_ERR_STATE;
+  if (out.output == KF_RC_OUT_MAPS) c->model_pyr_ok = 0;                // the model maps' level 0 is rewritten
+  RaycastArgs a; kf_raycast_form form; size_t lds;
+  { const int st = raycast_args(c, has_color, transform, rp, cam, near_plane, far_plane, out, a, form, lds); if (st) return st; }
   kf_evt_begin(c, KF_STAGE_RAYCAST);
-  {
-    hipEvent_t ke0 = nullptr, ke1 = nullptr;               // the kernel's own timer rides on its dispatch (kf_evt_attach): the kernel as rocprofv3 sees it
-    const dim3 grid(kf_div_up(c->cols, 32), kf_div_up(c->rows, 16));
-    const size_t pyr_lds = model_pyr ? (size_t)(32 * 16 + 16 * 8) * 2 * sizeof(float4) : 0;      // the tile's two maps and their level 1
-    const size_t lds = macro_bytes + (size_t)a.neg_words * 4 > pyr_lds ? macro_bytes + (size_t)a.neg_words * 4 : pyr_lds;
-    const bool timed = kf_evt_attach(c, KF_STAGE_RAYCAST_KERNEL, &ke0, &ke1);
-    if (spec_color) {
-      // the colour form of the z-slab speculation: a kernel of its own, no riders (a pending kf_prefetch_frame note stays where it is and is void at
-      // the next kf_preprocess: the frame is then preprocessed by its own launches, same bits)
-      form.kernel = KF_RC_PLAIN; form.grid = grid.x * grid.y;
-      if (timed) {
-        hipExtLaunchKernelGGL(k_raycast_slab_color, grid, dim3(RAYCAST_THREADS), (unsigned)lds, c->stream, ke0, ke1, 0, a);
-        kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
-      } else hipLaunchKernelGGL(k_raycast_slab_color, grid, dim3(RAYCAST_THREADS), lds, c->stream, a);
-    } else if (c->fp_pending && c->alt_raw) {
-      // kf_prefetch_frame left a note: the next frame's u16 -> f32 + gate + bilateral rides in this launch (k_raycast_prefetch), its vertices /
-      // normals follow; the set lands in the alternate buffers and kf_preprocess adopts it when it is asked for exactly that frame
-      c->fp_pending = 0;
-      const int behind = c->fp_filtered; c->fp_filtered = 0;                 // the filter rode in the tracking launch: the tile tables and the vertices / normals are left
-      KfBilateralArgs b; bool fast;
-      const bool build_tiles = c->tiles_clear && c->fuse_max_dist > 0.f;      // the fusion pass of this frame has cleared the tables: they can be built for the next depth map
-      kf_bilateral_args(c, c->fp_src, nullptr, c->alt_raw, c->alt_trunced, c->alt_filtered, c->fp_params[0], c->fp_params[1], c->fp_params[2], c->fp_params[3],
-                        build_tiles, &b, &fast);
-      KfFrontTail ft; memset(&ft, 0, sizeof(ft));
-      ft.behind = behind;
-      if (behind) {
-        ft.out_v = c->alt_v0; ft.out_n = c->alt_n0;
-        if (c->levels == 3 && c->alt_v12[0]) {
-          ft.pyr.v1 = c->alt_v12[0]; ft.pyr.n1 = c->alt_n12[0]; ft.pyr.v2 = c->alt_v12[1]; ft.pyr.n2 = c->alt_n12[1];
-          ft.pyr.c1 = c->cols >> 1; ft.pyr.r1 = c->rows >> 1; ft.pyr.c2 = ft.pyr.c1 >> 1; ft.pyr.r2 = ft.pyr.r1 >> 1;
-        }
-        ft.cam.cols = (int)c->fp_cam.cols; ft.cam.rows = (int)c->fp_cam.rows; ft.cam.cx = c->fp_cam.cx; ft.cam.cy = c->fp_cam.cy; ft.cam.fx = c->fp_cam.fx; ft.cam.fy = c->fp_cam.fy;
-      }
-      const int bil_gx = kf_div_up(c->cols, BIL_TX), bil_tiles = bil_gx * kf_div_up(c->rows, BIL_TY);
-      const int n_rc = (int)(grid.x * grid.y), n_bil = (bil_tiles + 1) / 2;
-      const size_t rider_lds = behind ? (size_t)RIDER_LDS_BYTES : 2 * (BIL_TX + 8) * (BIL_TY + 8) * sizeof(float);
-      const size_t lds2 = lds > rider_lds ? lds : rider_lds;
-      const dim3 g2((unsigned)(n_rc + n_bil));
-      form.kernel = behind ? KF_RC_BEHIND : KF_RC_FILTER; form.fast = fast ? 1 : 0; form.grid = g2.x;
-      if (fast) {
-        if (timed) hipExtLaunchKernelGGL(k_raycast_prefetch<true>, g2, dim3(RAYCAST_THREADS), (unsigned)lds2, c->stream, ke0, ke1, 0, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
-        else hipLaunchKernelGGL(k_raycast_prefetch<true>, g2, dim3(RAYCAST_THREADS), lds2, c->stream, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
-      } else {
-        if (timed) hipExtLaunchKernelGGL(k_raycast_prefetch<false>, g2, dim3(RAYCAST_THREADS), (unsigned)lds2, c->stream, ke0, ke1, 0, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
-        else hipLaunchKernelGGL(k_raycast_prefetch<false>, g2, dim3(RAYCAST_THREADS), lds2, c->stream, a, b, ft, (int)grid.x, n_rc, bil_gx, bil_tiles);
-      }
-      if (timed) kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
-      if (!behind) {
-        const int st = kf_launch_vertices_normals(c, c->stream, c->alt_filtered, c->alt_v0, c->alt_n0, &c->fp_cam);
-        if (st) return st;
-      }
-      c->alt_pyr_ok = (behind && ft.pyr.v1) ? 1 : 0;
-      c->prefetch_src = c->fp_src; memcpy(c->prefetch_params, c->fp_params, sizeof(c->prefetch_params));
-      c->prefetch_cam = c->fp_cam;
-      c->prefetch_valid = 1; c->fp_done = 1;
-      c->fp_tiles = build_tiles ? 1 : 0; c->fp_tiles_dist = c->fuse_max_dist; c->fp_tiles_min = (build_tiles && b.acc.n) ? 1 : 0;
-      if (build_tiles) c->tiles_clear = 0;
-    } else {
-      form.kernel = KF_RC_PLAIN; form.grid = grid.x * grid.y;
-      if (timed) {
-        hipExtLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), (unsigned)lds, c->stream, ke0, ke1, 0, a);
-        kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
-      } else hipLaunchKernelGGL(k_raycast, grid, dim3(RAYCAST_THREADS), lds, c->stream, a);
+  KfKernelTimer timer; timer.on = kf_evt_attach(c, KF_STAGE_RAYCAST_KERNEL, &timer.e0, &timer.e1);      // the kernel's own timer rides on its dispatch: the kernel as rocprofv3 sees it
+  const dim3 grid(kf_div_up(c->cols, 32), kf_div_up(c->rows, 16)), block(RAYCAST_THREADS);
+  // the colour form of the z-slab speculation: a kernel of its own, no riders (a pending kf_prefetch_frame note stays where it is and is void at
+  // the next kf_preprocess: the frame is then preprocessed by its own launches, same bits)
+  RaycastRiders r; const bool riding = !out.color && c->fp_pending && c->alt_raw;
+  form.kernel = KF_RC_PLAIN; form.grid = grid.x * grid.y;
+  if (out.color) kf_launch(timer, k_raycast_slab_color, grid, block, lds, c->stream, a);
+  else if (riding) {
+    raycast_riders(c, r);
+    const int n_rc = (int)(grid.x * grid.y), n_bil = (r.bil_tiles + 1) / 2;
+    const dim3 g2((unsigned)(n_rc + n_bil)); const size_t lds2 = lds > r.lds ? lds : r.lds;
+    form.kernel = r.ft.behind ? KF_RC_BEHIND : KF_RC_FILTER; form.fast = r.fast ? 1 : 0; form.grid = g2.x;
+    if (r.fast) kf_launch(timer, k_raycast_prefetch<true>, g2, block, lds2, c->stream, a, r.b, r.ft, (int)grid.x, n_rc, r.bil_gx, r.bil_tiles);
+    else kf_launch(timer, k_raycast_prefetch<false>, g2, block, lds2, c->stream, a, r.b, r.ft, (int)grid.x, n_rc, r.bil_gx, r.bil_tiles);
+  } else kf_launch(timer, k_raycast, grid, block, lds, c->stream, a);
+  if (timer.on) kf_evt_attached_done(c, KF_STAGE_RAYCAST_KERNEL);
+  if (riding) {
+    if (!r.ft.behind) {
+      const int st = kf_launch_vertices_normals(c, c->stream, c->alt_filtered, c->alt_v0, c->alt_n0, &c->fp_cam);
+      if (st) return st;
     }
+    c->alt_pyr_ok = (r.ft.behind && r.ft.pyr.v1) ? 1 : 0;
+    c->prefetch_src = c->fp_src; memcpy(c->prefetch_params, c->fp_params, sizeof(c->prefetch_params));
+    c->prefetch_cam = c->fp_cam; c->prefetch_valid = 1; c->fp_done = 1;
+    c->fp_tiles = r.build_tiles ? 1 : 0; c->fp_tiles_dist = c->fuse_max_dist; c->fp_tiles_min = (r.build_tiles && r.b.acc.n) ? 1 : 0;
+    if (r.build_tiles) c->tiles_clear = 0;
   }
   kf_evt_end(c, KF_STAGE_RAYCAST);
-  if (model_pyr) c->model_pyr_ok = 1;
+  if (form.pyramid) c->model_pyr_ok = 1;
   c->raycast_form = form;
   return (int)hipGetLastError();
 }
@@ -693,7 +672,8 @@ extern "C" int kf_get_raycast_form(kf_ctx* c, kf_raycast_form* out) {
 
 extern "C" int kf_raycast_volume(kf_ctx* c, int has_color, const kf_mat44* transform, const kf_raycast_params* rp,
                                  const kf_camera_params* cam, float near_plane, float far_plane) {
-  return raycast_launch(c, has_color, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr);
+  RaycastOut out = {}; out.output = KF_RC_OUT_MAPS;
+  return raycast_launch(c, has_color, transform, rp, cam, near_plane, far_plane, out);
 }
 
 // z-slab variant, MAP FORM (the earlier protocol, kept for per-kernel tests: it evaluates the gradient in the slab that met the crossing and therefore
@@ -715,7 +695,8 @@ extern "C" int kf_raycast_volume_slab(kf_ctx* c, int has_color, const kf_mat44* 
   if (!c || !rp || !dev_t || !dev_v || !dev_n) return KF_ERR_ARG;
   const int st = slab_halo_check(c, rp);
   if (st) return st;
-  return raycast_launch(c, has_color, transform, rp, cam, near_plane, far_plane, dev_t, (float4*)dev_v, (float4*)dev_n);
+  RaycastOut out = {}; out.output = KF_RC_OUT_T; out.t = dev_t; out.v = (float4*)dev_v; out.n = (float4*)dev_n;
+  return raycast_launch(c, has_color, transform, rp, cam, near_plane, far_plane, out);
 }
 
 // after the MIN reduction of the crossing parameters over the slabs: keep this context's candidate where it IS the first
@@ -749,29 +730,29 @@ extern "C" int kf_slab_mask_candidates(kf_ctx* c, const float* dev_t, const floa
 //   4. the caller's integer SUM all-reduce (exactly one contributor per pixel: the winner's bits, -0.0 included) and kf_set_model_maps_rays, which writes
 //      the model maps and levels 1 and 2 of their pyramids.
 // Two collectives and three launches per frame; 8 + 12 bytes per pixel on the wire (round 4: 8 + 16 -- the fourth word only said "valid", which a unit normal says itself).
-extern "C" int kf_raycast_volume_slab_cross(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
-                                            float near_plane, float far_plane, uint64_t* dev_ta) {
-  if (!c || !rp || !dev_ta) return KF_ERR_ARG;
+static int raycast_slab_cross(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam, float near_plane, float far_plane,
+                              uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec, bool spec, bool color) {
+  if (!c || !rp || !dev_ta || (spec && (!dev_ta_own || !dev_spec))) return KF_ERR_ARG;
   const int st = slab_halo_check(c, rp);
   if (st) return st;
-  return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr, (unsigned long long*)dev_ta);
+  RaycastOut out = {}; out.output = spec ? KF_RC_OUT_TA_SPEC : KF_RC_OUT_TA; out.color = color;
+  out.ta = (unsigned long long*)dev_ta; out.own_ta = (unsigned long long*)dev_ta_own; out.spec = dev_spec;
+  return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, out);
+}
+extern "C" int kf_raycast_volume_slab_cross(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
+                                            float near_plane, float far_plane, uint64_t* dev_ta) {
+  return raycast_slab_cross(c, transform, rp, cam, near_plane, far_plane, dev_ta, nullptr, nullptr, false, false);
 }
 extern "C" int kf_raycast_volume_slab_cross_spec(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
                                                  float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec) {
-  if (!c || !rp || !dev_ta || !dev_ta_own || !dev_spec) return KF_ERR_ARG;
-  const int st = slab_halo_check(c, rp);
-  if (st) return st;
-  return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr, (unsigned long long*)dev_ta, (unsigned long long*)dev_ta_own, dev_spec);
+  return raycast_slab_cross(c, transform, rp, cam, near_plane, far_plane, dev_ta, dev_ta_own, dev_spec, true, false);
 }
 // The colour forms of the three calls (a context with a colour plane): the candidate is 4 words per pixel, the normal's three and the uchar4 colour
 // word of interpolateColor at the VERTEX (raycastingVolume.cu:91-92, tsdfVolume.h:123-148) -- evaluated by the vertex's owner like the gradient, before
 // and independently of it, so a pixel without a normal can carry a colour, as in the whole-volume march.  All-zero bits: no colour.
 extern "C" int kf_raycast_volume_slab_cross_spec_color(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
                                                        float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec) {
-  if (!c || !rp || !dev_ta || !dev_ta_own || !dev_spec) return KF_ERR_ARG;
-  const int st = slab_halo_check(c, rp);
-  if (st) return st;
-  return raycast_launch(c, 0, transform, rp, cam, near_plane, far_plane, nullptr, nullptr, nullptr, (unsigned long long*)dev_ta, (unsigned long long*)dev_ta_own, dev_spec, true);
+  return raycast_slab_cross(c, transform, rp, cam, near_plane, far_plane, dev_ta, dev_ta_own, dev_spec, true, true);
 }
 struct SlabNormalArgs { KfVolume vol; KfCam cam; const float* pose; KfMat pose_val; const unsigned long long* ta; float* cand; float inc, near_plane, far_plane; int shared_grad;
                         const unsigned long long* own_ta; const float* spec; };   // own_ta / spec: kf_raycast_volume_slab_cross_spec's second outputs, or null   // cand, spec: 3 floats per pixel (the colour forms: 4)
@@ -826,11 +807,10 @@ static int slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_rayca
   SlabNormalArgs a;
   a.vol = c->vol; a.ta = (const unsigned long long*)dev_ta_min; a.cand = dev_cand;
   a.own_ta = (dev_ta_own && dev_spec) ? (const unsigned long long*)dev_ta_own : nullptr; a.spec = dev_spec;
-  a.cam.cols = (int)cam->cols; a.cam.rows = (int)cam->rows; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.fx = cam->fx; a.cam.fy = cam->fy;
+  a.cam = kf_to_cam(cam);
   a.inc = rp->ray_increment; a.near_plane = near_plane; a.far_plane = far_plane;
   a.shared_grad = rc_shared_grad_for(c->vol);
-  if (transform) { for (int k = 0; k < 16; ++k) a.pose_val.m[k] = transform->m[k]; a.pose = nullptr; }
-  else a.pose = c->track->pose;
+  kf_pose_arg(c, transform, a.pose, a.pose_val);
   if (color) hipLaunchKernelGGL(k_slab_ray_normals_color, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
   else hipLaunchKernelGGL(k_slab_ray_normals, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
   return (int)hipGetLastError();
@@ -887,14 +867,10 @@ static int set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, const kf_ca
   SlabUnpackArgs a;
   c->model_pyr_ok = 0;
   memset(&a.pyr, 0, sizeof(a.pyr));
-  if (c->levels == 3) {
-    a.pyr.v1 = c->model_v[1]; a.pyr.n1 = c->model_n[1]; a.pyr.v2 = c->model_v[2]; a.pyr.n2 = c->model_n[2];
-    a.pyr.c1 = c->cols >> 1; a.pyr.r1 = c->rows >> 1; a.pyr.c2 = a.pyr.c1 >> 1; a.pyr.r2 = a.pyr.r1 >> 1;
-  }
+  if (c->levels == 3) kf_pyr_arg(a.pyr, c->model_v + 1, c->model_n + 1, c->cols, c->rows);
   a.ta = (const unsigned long long*)dev_ta_min; a.cand = dev_cand; a.v = c->model_v[0]; a.n = c->model_n[0];
-  a.cam.cols = (int)cam->cols; a.cam.rows = (int)cam->rows; a.cam.cx = cam->cx; a.cam.cy = cam->cy; a.cam.fx = cam->fx; a.cam.fy = cam->fy;
-  if (transform) { for (int k = 0; k < 16; ++k) a.pose_val.m[k] = transform->m[k]; a.pose = nullptr; }
-  else a.pose = c->track->pose;                       // the pose the raycast used: nothing moves it between the raycast and this call
+  a.cam = kf_to_cam(cam);
+  kf_pose_arg(c, transform, a.pose, a.pose_val);      // the pose the raycast used: nothing moves it between the raycast and this call
   if (color) hipLaunchKernelGGL(k_slab_rays_unpack_color, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a, c->raycast_rgb);
   else hipLaunchKernelGGL(k_slab_rays_unpack, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
   if (a.pyr.v1) c->model_pyr_ok = 1;

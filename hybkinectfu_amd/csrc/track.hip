@@ -25,7 +25,6 @@
 #include "bilateral_tile.h"
 #include "sdf_rows.h"
 #include <string.h>
-#include <stdlib.h>
 
 #define TRK_THREADS 256
 #define TRK_PX 2                   // 8x8 tiles per wave of the SDF step (grid-stride beyond that): the lookups want many waves, not long lanes
@@ -1425,14 +1424,11 @@ static inline TrackThresholds track_thresholds(float dist_thres, float sin_thres
   t.dist_thres2 = gate_square(dist_thres); t.sin_thres2 = gate_square(sin_thres);
   return t;
 }
-static inline KfCam to_cam(const kf_camera_params* p) {
-  KfCam c; c.cols = (int)p->cols; c.rows = (int)p->rows; c.cx = p->cx; c.cy = p->cy; c.fx = p->fx; c.fy = p->fy; return c;
-}
 // the camera of pyramid level l (ICP.cpp:36-48: every level halves the one above)
 static inline KfCam level_cam(const kf_camera_params* cam0, int l) {
   kf_camera_params p = *cam0;
   for (int k = 0; k < l; ++k) { p.cols /= 2; p.rows /= 2; p.cx /= 2; p.cy /= 2; p.fx /= 2; p.fy /= 2; }
-  return to_cam(&p);
+  return kf_to_cam(&p);
 }
 static int icp_iters(int levels, int iters[KF_MAX_LEVELS]) {                // ICP.cpp:14-35
   iters[0] = iters[1] = iters[2] = 0;
@@ -1466,7 +1462,7 @@ extern "C" int kf_cal_point_to_plane_solver_params(kf_ctx* c, uint32_t level, co
   if ((int)cam->cols != c->lvl_cols[level] || (int)cam->rows != c->lvl_rows[level]) return KF_ERR_ARG;
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.new_v = c->new_v[level]; a.new_n = c->new_n[level]; a.model_v = c->model_v[level]; a.model_n = c->model_n[level];
-  a.cam = to_cam(cam);
+  a.cam = kf_to_cam(cam);
   for (int i = 0; i < 16; ++i) { a.cur_val.m[i] = cur->m[i]; a.linv_val.m[i] = last_inv->m[i]; }
   a.th = track_thresholds(dist_thres, sin_thres, 0.f, 0.f);
   a.partials = c->icp_partials; a.track = c->track;
@@ -1482,7 +1478,7 @@ extern "C" int kf_cal_sdf_solver_params(kf_ctx* c, const kf_camera_params* cam, 
   if (!c || !cam || !cur) return KF_ERR_ARG;
   if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
   TrackArgs a; memset(&a, 0, sizeof(a));
-  a.cam = to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth; a.sdf = 1;
+  a.cam = kf_to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth; a.sdf = 1;
   for (int i = 0; i < 16; ++i) a.cur_val.m[i] = cur->m[i];
   a.partials = c->icp_partials; a.track = c->track;
   const int grid = track_grid(c->cols * c->rows);
@@ -1500,9 +1496,6 @@ extern "C" int kf_read_solver_params(kf_ctx* c, float out27[27]) {
   return 0;
 }
 
-#ifndef KF_ICP_COOPERATIVE_DEFAULT
-#define KF_ICP_COOPERATIVE_DEFAULT 0
-#endif
 // a persistent loop timed out and was finished by one workgroup alone (track_loop_end: the frame is kept, milliseconds late): back off to
 // per-step launches for a while (64 frames, doubling up to 4096 on repeats; 1024 clean loop frames in a row forget the history).  One episode
 // is noted once: launches of the loop that were already enqueued when the word was seen raise it again while the back-off is running.
@@ -1533,9 +1526,7 @@ static bool kf_loop_admit(kf_ctx* c, bool fits, TrackLoopArgs& L) {
 // parameters behind, the tile tables describe THIS frame's depth map, no deferred-weight words (their cull retires bricks: side effects nobody could undo) and
 // few enough macro cells for the launch's workgroups.  kf_integrate_volume consumes it, or undoes it when it is asked for something else.
 static bool kf_arm_tail_cull(kf_ctx* c, const kf_camera_params* cam0, int n_wg, int waves, IntegrateArgs& out) {
-  static int tail_env = -1;
-  if (tail_env < 0) { const char* e = getenv("KF_CULL_IN_TRACK"); tail_env = e ? atoi(e) : 1; }
-  if (!(tail_env && c->cull_hint.valid && !kf_defer_enabled(c) &&
+  if (!(kf_switch(KF_SW_CULL_IN_TRACK) && c->cull_hint.valid && !kf_defer_enabled(c) &&
         c->tile_serial != 0 && c->tile_serial == c->trunc_serial && c->tile_built_dist == c->cull_hint.max_dist &&
         memcmp(&c->cull_hint.dcam, cam0, sizeof(*cam0)) == 0 && kf_cull_tail_fits(c, n_wg, waves))) return false;
   kf_fill_cull_args(c, out, &c->cull_hint.dcam, c->cull_hint.sdf_trunc, c->cull_hint.max_dist);
@@ -1559,9 +1550,7 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
   int st;
   kf_evt_begin(c, KF_STAGE_TRACK);
   const int grid0 = icp_grid(c->cols * c->rows);
-  static int persistent_env = -1, coop_env = -1;
-  if (persistent_env < 0) { const char* e = getenv("KF_ICP_PERSISTENT"); persistent_env = e ? atoi(e) : 1; }
-  if (coop_env < 0) { const char* e = getenv("KF_ICP_COOPERATIVE"); coop_env = e ? atoi(e) : KF_ICP_COOPERATIVE_DEFAULT; }
+  const int persistent_env = kf_switch(KF_SW_ICP_PERSISTENT), coop_env = kf_switch(KF_SW_ICP_COOPERATIVE);
   if (c->loop_occupancy == 0) {                              // (asked once, whatever form this call takes: the per-step form folds in the batched loop's groups)
     // every workgroup must be resident at once (they wait for each other's tagged partial sums): ask the runtime how many 512-lane
     // workgroups of THESE kernels a CU holds (registers, LDS) instead of assuming one
@@ -1572,13 +1561,10 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
   }
   // Images whose level 0 needs more workgroups than the chip holds at once (1280x960: 800): the batched loop -- as many resident workgroups as the
   // VGA loop uses (the CU count less a share for the riders), each playing several workgroups of the dealing in turn.  KF_ICP_BATCHED=0: per step.
-  static int batched_env = -1;
-  if (batched_env < 0) { const char* e = getenv("KF_ICP_BATCHED"); batched_env = e ? atoi(e) : 1; }
   const bool beyond = c->loop_occupancy < 1 || (long long)grid0 > (long long)c->loop_occupancy * c->num_cus;
-  static int room_env = -1;                                  // KF_ICP_BATCHED_ROOM=n: resident workgroups of the batched loop (A/B; every launch form folds in groups of n, so the forms stay bitwise equal)
-  if (room_env < 0) { const char* e = getenv("KF_ICP_BATCHED_ROOM"); room_env = e ? atoi(e) : 0; }
+  const int room_env = kf_switch(KF_SW_ICP_BATCHED_ROOM);    // KF_ICP_BATCHED_ROOM=n: resident workgroups of the batched loop (A/B; every launch form folds in groups of n, so the forms stay bitwise equal)
   const int room = c->loop_occupancy_batched >= 1 ? ((room_env >= 16 && room_env <= c->num_cus * c->loop_occupancy_batched) ? room_env : c->num_cus - c->num_cus / 5) : 0;      // 256 CUs: 205 resident workgroups, 51 CUs left to the riders
-  const bool batched = beyond && batched_env && !coop_env && room >= 16 && grid0 <= KF_ICP_LOOP_MAX_WG;
+  const bool batched = beyond && kf_switch(KF_SW_ICP_BATCHED) && !coop_env && room >= 16 && grid0 <= KF_ICP_LOOP_MAX_WG;
   // fold_group: the publishers of a batched launch.  Every launch form of such an image adds the partial sums of the workgroups g, g + fold_group, ... first
   // (the batched loop's resident workgroup g plays exactly those): the forms stay bitwise equal
   const int fold_group = batched ? room : 0;
@@ -1596,15 +1582,13 @@ extern "C" int kf_icp_track(kf_ctx* c, uint32_t frame_id, const kf_icp_params* i
     }
     L.levels = c->levels;
     L.th = track_thresholds(icp->dist_thres, icp->norm_sin_thres, icp->dist_shake, icp->angle_shake);
-    { static int em = -1; if (em < 0) em = KF_EXP_ENV("KF_ICP_EXP"); L.exp_mode = em; }
+    L.exp_mode = KF_EXP_ENV(ICP_EXP);
     L.n_loop = batched ? room : grid0; L.n_virtual = grid0;
     // a pending kf_prefetch_frame: the next frame's filter rides in this launch (see IcpLoopArgs) and leaves the gated + filtered image in
     // the alternate buffers; the raycast launch that follows carries its tile tables (the fusion pass in between clears them) and its
     // vertices / normals.  Not under a cooperative launch, whose whole grid would have to be resident.
-    static int ride_env = -1;
-    if (ride_env < 0) { const char* e = getenv("KF_PREFETCH_IN_TRACK"); ride_env = e ? atoi(e) : 1; }
     unsigned n_riders = 0;
-    if (ride_env && !coop_env && c->fp_pending && c->alt_raw && !c->fp_filtered) {
+    if (kf_switch(KF_SW_PREFETCH_IN_TRACK) && !coop_env && c->fp_pending && c->alt_raw && !c->fp_filtered) {
       bool fast;
       kf_bilateral_args(c, c->fp_src, nullptr, c->alt_raw, c->alt_trunced, c->alt_filtered, c->fp_params[0], c->fp_params[1], c->fp_params[2], c->fp_params[3],
                         false, &L.bil, &fast);
@@ -1723,10 +1707,8 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
   // The whole loop in one launch (k_sdf_loop) under the conditions of the persistent ICP loop: this context alone on the device, no back-off after a
   // time-out, every workgroup resident.  KF_SDF_PERSISTENT=0 (or KF_ICP_PERSISTENT=0): one launch per iteration, as the z-slab partition runs it.
   {
-    static int loop_env = -1;
-    if (loop_env < 0) { const char* e = getenv("KF_SDF_PERSISTENT"); const char* e2 = getenv("KF_ICP_PERSISTENT"); loop_env = (e ? atoi(e) : 1) && (e2 ? atoi(e2) : 1); }
     const bool buf = sdf_buffer_addressing(c->vol);
-    const bool fits = loop_env && sp->max_iter_nums >= 1 && sp->max_iter_nums <= KF_ICP_LOOP_STEPS;
+    const bool fits = kf_switch(KF_SW_SDF_PERSISTENT) && kf_switch(KF_SW_ICP_PERSISTENT) && sp->max_iter_nums >= 1 && sp->max_iter_nums <= KF_ICP_LOOP_STEPS;
     if (fits && c->sdf_loop_occupancy == 0) {
       int per_cu = 0;
       const hipError_t e = buf ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_sdf_loop<SdfBufAddr>, SDF_THREADS, 0)
@@ -1736,14 +1718,12 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
     SdfLoopArgs L; memset(&L, 0, sizeof(L));
     if (kf_loop_admit(c, fits && c->sdf_loop_occupancy >= 1, L)) {
       const int npx = c->cols * c->rows;
-      static int wg_env = -1;
-      if (wg_env < 0) { const char* e = getenv("KF_SDF_LOOP_WG"); wg_env = e ? atoi(e) : 0; }
-      int n_loop = wg_env > 0 ? wg_env : c->num_cus;                           // one workgroup per CU
+      int n_loop = kf_switch(KF_SW_SDF_LOOP_WG) > 0 ? kf_switch(KF_SW_SDF_LOOP_WG) : c->num_cus;                           // one workgroup per CU
       n_loop = n_loop > c->num_cus * c->sdf_loop_occupancy ? c->num_cus * c->sdf_loop_occupancy : n_loop;
       n_loop = n_loop > KF_ICP_LOOP_MAX_WG ? KF_ICP_LOOP_MAX_WG : n_loop;
       const int need = kf_div_up(kf_div_up(c->cols, 8) * kf_div_up(c->rows, 8), SDF_THREADS / 64);
       if (n_loop > need) n_loop = need;
-      L.vol = c->vol; L.depth = c->trunced_depth; L.cam = to_cam(cam); L.max_iter = (int)sp->max_iter_nums;
+      L.vol = c->vol; L.depth = c->trunced_depth; L.cam = kf_to_cam(cam); L.max_iter = (int)sp->max_iter_nums;
       L.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
       const int n_tiles = kf_div_up(c->cols, 8) * kf_div_up(c->rows, 8);      // 8x8 pixel tiles, one per wave and round
       L.n_loop = n_loop; L.px_l = kf_div_up(n_tiles, (SDF_THREADS / 64) * n_loop);
@@ -1758,7 +1738,7 @@ extern "C" int kf_sdf_track(kf_ctx* c, uint32_t frame_id, const kf_sdf_tracker_p
   hipLaunchKernelGGL(k_track_begin, dim3(1), dim3(64), 0, c->stream, c->track, 1);
   TrackArgs a; memset(&a, 0, sizeof(a));
   a.use_state = 1; a.sdf = 1;
-  a.cam = to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
+  a.cam = kf_to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
   a.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   const int grid = track_grid(c->cols * c->rows);
@@ -1798,7 +1778,7 @@ static int sdf_partition_args(kf_ctx* c, const kf_sdf_tracker_params* sp, const 
   if ((c->vol.own_z0 > 0 && lo < need) || (c->vol.own_z1 < c->vol.res && hi < need)) return KF_ERR_ARG;
   memset(&a, 0, sizeof(a));
   a.use_state = 1; a.sdf = 1; a.slab_pixels = 1;
-  a.cam = to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
+  a.cam = kf_to_cam(cam); a.vol = c->vol; a.depth = c->trunced_depth;
   a.th = track_thresholds(0.f, 0.f, sp->dist_shake, sp->angle_shake);
   a.partials = c->icp_partials; a.track = c->track;
   return 0;
