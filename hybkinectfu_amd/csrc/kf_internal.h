@@ -238,6 +238,8 @@ struct kf_ctx {
   hipEvent_t ev[8][2][64];            // [stage][begin/end][ring]
   int ev_n[8];                        // pairs recorded and not yet folded
   double ev_ms[8]; unsigned ev_count[8];
+  // viewer frames (view.hip; kf_render_view, kf_view_model_maps): the context-owned BGRA image of the last view, grown on demand
+  unsigned* view_img; size_t view_cap_px; uint32_t view_cols, view_rows;   // view_cols == 0: no view yet
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,
@@ -641,4 +643,5 @@ int kf_materialize_raw_depth(kf_ctx* ctx);
 int kf_pending_depth_consumed(kf_ctx* ctx);
 int kf_tail_cull_discard(kf_ctx* ctx);   // a cull that ran as the tail of a tracking launch and will not be consumed: its queue counter back to zero
 void kf_weld_free(kf_ctx* ctx);          // (weld.hip) what kf_weld_release frees, for kf_destroy: the caller has synchronised the stream
+int kf_view_reserve(kf_ctx* ctx, uint32_t cols, uint32_t rows, unsigned** img);   // (view.hip) the view image for a cols x rows view about to be enqueued; it becomes "the last view"
 int kf_upload_wait_for(kf_ctx* ctx, const uint16_t* dev_mm);   // dev_mm is about to be read on the context's stream: wait for its staged copy, if it is one

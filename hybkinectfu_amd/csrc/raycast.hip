@@ -14,6 +14,7 @@
 #include "kf_internal.h"
 #include "bilateral_tile.h"
 #include "grad_shared.h"
+#include "view_pixel.h"
 #include <string.h>
 
 // KF_RAYCAST_SHARED_GRAD (0 / 1 / 2, see RaycastArgs::shared_grad) in bits 0-7, KF_RAYCAST_VIEW_HALF (tests: brick layers of the gathers' view on either side, 0 = most) above.
@@ -354,8 +355,11 @@ __device__ __forceinline__ void rc_tile_bounds(const RaycastArgs& a, const unsig
 // one 32x16 pixel tile (tile_x, tile_y) by the 512 threads of a workgroup; s_tables: the workgroup's dynamic LDS
 // SPEC_COLOR (compile time; kf_raycast_volume_slab_cross_spec_color): the z-slab speculation carries a fourth word per pixel, interpolateColor at the
 // vertex under the same ownership test as the gradient -- out_spec then has 4 words per pixel.  false: the code of every other form, unchanged.
-template <bool SPEC_COLOR>
-__device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, int tile_y, unsigned* s_tables) {
+// VIEW (compile time; kf_render_view): 0, or 1 + KF_VIEW_* -- the epilogue turns the lane's vertex, normal and colour into one display word in registers
+// (view_pixel.h) and stores it to view_img; the float4 maps only where the caller gave buffers (a.out_v / a.out_n may be null), no colour map, no
+// crossing words, no pyramid, no work counters.  a.cam is then the CALLER's camera: the grid, the tile bounds and the pixel index all follow it.
+template <bool SPEC_COLOR, int VIEW = 0>
+__device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, int tile_y, unsigned* s_tables, unsigned* view_img = nullptr) {
   const KfVolume& v = a.vol;
   // Packed bit tables live in LDS so that the empty-space walk costs LDS reads instead of dependent L2 round trips: one bit
   // per 32^3-voxel macro cell and per 128^3-voxel super cell of the whole volume (KfVolume::macrobits, kept current by the
@@ -471,6 +475,11 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
     out_n = make_float4((float)n_samp, (float)(n_macro & 0xFFFF), (float)(n_macro >> 16), 0.f);
   }
 #endif
+  if (VIEW) {
+    if (a.out_v) a.out_v[pix] = out_v;
+    if (a.out_n) a.out_n[pix] = out_n;
+    view_img[pix] = kf_view_pixel<(VIEW ? VIEW - 1 : 0)>(out_v, out_n, out_c, org);     // the eye is the pose's translation: the ray origin
+  } else
   if (a.out_ta) {
     const unsigned long long word = ((unsigned long long)__float_as_uint(t_cross) << 32) | (unsigned long long)(t_cross < inf ? __float_as_uint(out_alpha) : 0u);
     a.out_ta[pix] = word;
@@ -481,7 +490,7 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
     if (a.out_spec) { a.own_ta[pix] = word; a.out_spec[3 * pix] = out_n.x; a.out_spec[3 * pix + 1] = out_n.y; a.out_spec[3 * pix + 2] = out_n.z; }
   }
   else { a.out_v[pix] = out_v; a.out_n[pix] = out_n; }
-  if (a.work) {
+  if (!VIEW && a.work) {
     // what the REFERENCE's march reads for this ray (raycastingVolume.cu:65-119): one voxel per sample from t_min up to the
     // crossing (or t_max); a crossing is evaluated with 2 + 6 trilinear look-ups of 8 voxels each
     const float t_stop = t_cross < inf ? t_cross : ref_tmax;
@@ -493,14 +502,14 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
       atomicAdd(&a.work->rc_hits[sh * 16], (unsigned long long)hits);
     }
   }
-  if (a.out_t) a.out_t[pix] = t_cross;
-  if (a.has_color) a.out_rgb[pix] = out_c;
+  if (!VIEW && a.out_t) a.out_t[pix] = t_cross;
+  if (!VIEW && a.has_color) a.out_rgb[pix] = out_c;
   };
   if (live) march_pixel();
   // Levels 1 and 2 of the model maps' pyramids, which the NEXT frame's tracker reads first (ICP.cpp:57-60): a 32x16 tile holds whole 2x2 and
   // 4x4 blocks, so the workgroup that produced the texels averages them itself -- through the LDS the bit tables occupied until its last wave
   // left the march -- and the tracker's pyramid launch (a pass over four maps, ~8 us) has nothing left to do.
-  if (a.pyr.v1) {                                                            // uniform
+  if (!VIEW && a.pyr.v1) {                                                   // uniform
     __syncthreads();                                                         // every wave is done with the tables
     float4* s_v = reinterpret_cast<float4*>(s_tables);
     float4* s_n = s_v + 32 * 16, *s1_v = s_n + 32 * 16, *s1_n = s1_v + 16 * 8;
@@ -518,6 +527,13 @@ __global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast(RaycastArgs a) {
 __global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast_slab_color(RaycastArgs a) {
   extern __shared__ unsigned s_dyn[];
   raycast_tile<true>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn);
+}
+
+// kf_render_view: the caller's camera, one display word per pixel (mode = KF_VIEW_*: the epilogue is chosen at compile time)
+template <int MODE>
+__global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast_view(RaycastArgs a, unsigned* img) {
+  extern __shared__ unsigned s_dyn[];
+  raycast_tile<false, MODE + 1>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn, img);
 }
 
 // The raycast with the NEXT frame's depth conversion + gate + bilateral filter riding along (kf_prefetch_frame, fused form).  The raycast
@@ -660,6 +676,34 @@ static int raycast_launch(kf_ctx* c, int has_color, const kf_mat44* transform, c
   kf_evt_end(c, KF_STAGE_RAYCAST);
   if (form.pyramid) c->model_pyr_ok = 1;
   c->raycast_form = form;
+  return (int)hipGetLastError();
+}
+
+// ---- viewer frames: a free viewpoint through the volume, display bytes out (reference: the three DataViewer calls of src/HybKinectfu.cpp:145-158) --------
+// The march of kf_raycast_volume with the caller's camera -- same bit tables, tile bounds and KF_RAYCAST_* switches (raycast_args) -- whose epilogue writes
+// 4 bytes per pixel into the context's view image instead of 32 into the model maps.  It is a bystander: the model maps and model_pyr_ok, raycast_rgb,
+// kf_get_raycast_form's record, a pending kf_prefetch_frame note (no riders), the stage timers and the work counters are all left alone.
+static bool view_cam_ok(const kf_camera_params* cam) {
+  return cam && cam->cols >= 1 && cam->cols <= 4096 && cam->rows >= 1 && cam->rows <= 4096 && cam->fx != 0.f && cam->fy != 0.f &&
+         cam->fx == cam->fx && cam->fy == cam->fy && cam->cx == cam->cx && cam->cy == cam->cy;
+}
+extern "C" int kf_render_view(kf_ctx* c, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* rp,
+                              float near_plane, float far_plane, float* dev_v, float* dev_n) {
+  if (!c || !rp) return KF_ERR_ARG;
+  if (mode != KF_VIEW_NORMALS && mode != KF_VIEW_SHADED && mode != KF_VIEW_COLOR) return KF_ERR_ARG;
+  if (!view_cam_ok(view_cam)) return KF_ERR_ARG;
+  if (mode == KF_VIEW_COLOR && !c->vol.color) return KF_ERR_STATE;
+  if (c->vol.own_z0 > 0 || c->vol.own_z1 < c->vol.res) return KF_ERR_STATE;      // a z-slab sees only its own layers
+  unsigned* img = nullptr;
+  { const int st = kf_view_reserve(c, view_cam->cols, view_cam->rows, &img); if (st) return st; }
+  RaycastOut out = {}; out.output = -1;                                    // none of KF_RC_OUT_*: no pyramid, no crossing words
+  RaycastArgs a; kf_raycast_form form; size_t lds;
+  { const int st = raycast_args(c, mode == KF_VIEW_COLOR, pose, rp, view_cam, near_plane, far_plane, out, a, form, lds); if (st) return st; }
+  a.out_v = (float4*)dev_v; a.out_n = (float4*)dev_n; a.out_rgb = nullptr; a.work = nullptr;
+  const dim3 grid(kf_div_up((int)view_cam->cols, 32), kf_div_up((int)view_cam->rows, 16)), block(RAYCAST_THREADS);
+  if (mode == KF_VIEW_NORMALS) hipLaunchKernelGGL(k_raycast_view<KF_VIEW_NORMALS>, grid, block, lds, c->stream, a, img);
+  else if (mode == KF_VIEW_SHADED) hipLaunchKernelGGL(k_raycast_view<KF_VIEW_SHADED>, grid, block, lds, c->stream, a, img);
+  else hipLaunchKernelGGL(k_raycast_view<KF_VIEW_COLOR>, grid, block, lds, c->stream, a, img);
   return (int)hipGetLastError();
 }
 

@@ -94,6 +94,27 @@ int hkf_app_get_pose(float out16[16]) {
   memcpy(out16, m.entries, 64);
   return g_app->lastTracked() ? 1 : 0;
 }
+// HybKinectfu::renderView / viewModelMaps: the picture into `out` (cols * rows * 4 bytes: b, g, r, a).  pose16 NULL: the current camera pose.
+// returns 0, -1 without an application, -2 when the view failed (CudaDeviceDataMan::lastError has the status), -3 when `out` is too small
+static int copy_view(const std::vector<uint8_t>& img, uint8_t* out, size_t out_cap) {
+  if (!out || out_cap < img.size()) return -3;
+  memcpy(out, img.data(), img.size());
+  return 0;
+}
+int hkf_app_render_view(int mode, const float* pose16, unsigned cols, unsigned rows, float cx, float cy, float fx, float fy, uint8_t* out, size_t out_cap) {
+  if (!g_app) return -1;
+  Mat44 m; if (pose16) memcpy(m.entries, pose16, 64);
+  const kf_camera_params cam = {cols, rows, cx, cy, fx, fy};
+  std::vector<uint8_t> img;
+  if (!g_app->renderView(pose16 ? &m : nullptr, cam, mode, img)) return -2;
+  return copy_view(img, out, out_cap);
+}
+int hkf_app_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
+  if (!g_app) return -1;
+  std::vector<uint8_t> img;
+  if (!g_app->viewModelMaps(mode, img)) return -2;
+  return copy_view(img, out, out_cap);
+}
 int hkf_app_generate_mesh() { if (!g_mesh) return -1; g_mesh->generateMesh(); return (int)g_mesh->triangleCount(); }
 int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
   if (!g_mesh) return -1;

@@ -365,6 +365,31 @@ bool HybKinectfu::processNewFrame(const DepthFrameData& depth_frame, const Color
                                   p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc))) return false;
   return true;
 }
+// what DataViewer shows, without the maps crossing to the host (HybKinectfu.cpp:145-158): 4 bytes per pixel come back
+static bool read_view(CudaDeviceDataMan* dm, std::vector<uint8_t>& bgra) {
+  uint32_t cols = 0, rows = 0;
+  if (dm->check(kf_view_size(dm->ctx(), &cols, &rows))) return false;
+  bgra.resize((size_t)cols * rows * 4);
+  return dm->check(kf_read_view(dm->ctx(), bgra.data(), bgra.size())) == 0;
+}
+bool HybKinectfu::renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra) {
+  if (!_inited) return false;
+  const AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  // (a finder that keeps its pose on the host: "the current pose" is the host's copy)
+  kf_mat44 kp; const kf_mat44* tp = nullptr;
+  if (pose) { kp = to_kf(*pose); tp = &kp; }
+  else if (!_camera_pose_finder->deviceResident()) { kp = to_kf(_camera_pose_finder->getCameraPose()); tp = &kp; }
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
+  if (dm->check(kf_render_view(dm->ctx(), mode, tp, &cam, &rp, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, nullptr, nullptr))) return false;
+  return read_view(dm, bgra);
+}
+bool HybKinectfu::viewModelMaps(int mode, std::vector<uint8_t>& bgra) {
+  if (!_inited) return false;
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (dm->check(kf_view_model_maps(dm->ctx(), mode))) return false;
+  return read_view(dm, bgra);
+}
 bool HybKinectfu::lastTracked() {
   if (_pending && _camera_pose_finder) { _last_tracked = _camera_pose_finder->syncPose(); _pending = false; }
   return _last_tracked;

@@ -225,6 +225,12 @@ public:
   bool lastTracked();
   Mat44 getCameraPose();
   CameraPoseFinder* poseFinder() { return _camera_pose_finder; }
+  // The pictures the reference paints on the host after every frame (DataViewer::viewNormal / viewColors, HybKinectfu.cpp:145-158), made on the
+  // device (kf_render_view / kf_view_model_maps) and read back as cols * rows * 4 bytes (b, g, r, a); mode = KF_VIEW_*.  The increment and the
+  // planes come from AppParams, as processNewFrame uses them.  renderView: any camera, from `pose` (nullptr: the current camera pose); it leaves
+  // tracking state alone.  viewModelMaps: the tracking camera's view from the current model maps, no march.  Blocking (the read-back).
+  bool renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra);
+  bool viewModelMaps(int mode, std::vector<uint8_t>& bgra);
 private:
   void copyFrameToGPU(const DepthFrameData& depth_frame, const ColorFrameData& color_frame);
   CameraPoseFinder* _camera_pose_finder;

@@ -85,6 +85,18 @@ Mat44 HybKinectfuSlabs::getCameraPose() {
   return _pose;
 }
 
+// member 0 holds the merged model maps (and, in a colour group, KF_MAP_RAYCAST_RGB) after step 9 of the frame; its stream is where that step ran
+bool HybKinectfuSlabs::viewModelMaps(int mode, std::vector<uint8_t>& bgra) {
+  if (!_inited) return false;
+  kf_ctx* ctx = nullptr;
+  if (!check(kf_group_member(_group, 0, &ctx))) return false;
+  if (!check(kf_view_model_maps(ctx, mode))) return false;
+  uint32_t cols = 0, rows = 0;
+  if (!check(kf_view_size(ctx, &cols, &rows))) return false;
+  bgra.resize((size_t)cols * rows * 4);
+  return check(kf_read_view(ctx, bgra.data(), bgra.size()));
+}
+
 void HybKinectfuSlabs::generateMesh() {                        // MeshGeneratorMarchingcube::generateMesh, src/MeshGeneratorMarchingcube.cpp:23-29
   if (!_inited) return;
   const AppParams* p = AppParams::instance();

@@ -39,6 +39,9 @@ public:
   bool saveMesh(const std::string& filename);
   unsigned triangleCount();
   const MeshData& mesh() const { return _mesh.mesh(); }
+  // HybKinectfu::viewModelMaps through member 0: after a frame's merge every member holds the whole volume's model maps.  cols * rows * 4 bytes
+  // (b, g, r, a); mode = KF_VIEW_*, KF_VIEW_COLOR on a colour group only.  Blocking.  (No renderView: a member sees only its own layers.)
+  bool viewModelMaps(int mode, std::vector<uint8_t>& bgra);
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

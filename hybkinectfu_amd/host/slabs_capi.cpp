@@ -87,5 +87,14 @@ int hkf_slabs_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_
   if (n_faces) *n_faces = (unsigned)(g_slabs->mesh().faces.size() / 3);
   return ok ? 1 : 0;
 }
+// HybKinectfuSlabs::viewModelMaps into `out` (cols * rows * 4 bytes); 0, -1 without a group, -2 view failed, -3 `out` too small
+int hkf_slabs_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
+  if (!g_slabs) return -1;
+  std::vector<uint8_t> img;
+  if (!g_slabs->viewModelMaps(mode, img)) return -2;
+  if (!out || out_cap < img.size()) return -3;
+  memcpy(out, img.data(), img.size());
+  return 0;
+}
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

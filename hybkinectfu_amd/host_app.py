@@ -79,6 +79,26 @@ class App:
         if self.h.hkf_app_set_device_weld(int(bool(on))) != 0:
             raise K.KfError("hkf_app_set_device_weld: no application")
 
+    def render_view(self, mode, pose, cam):
+        """HybKinectfu::renderView: `cam` = (cols, rows, cx, cy, fx, fy) from `pose` (None: the current camera pose), mode = lib.VIEW_*;
+        returns (rows, cols, 4) uint8 (b, g, r, a).  Increment and planes are the application's."""
+        out = np.empty((cam[1], cam[0], 4), np.uint8)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16) if pose is not None else None
+        r = self.h.hkf_app_render_view(int(mode), p.ctypes.data_as(C.c_void_p) if p is not None else None, int(cam[0]), int(cam[1]),
+                                       C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
+                                       out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("renderView failed: %d" % r)
+        return out
+
+    def view_model_maps(self, mode):
+        """HybKinectfu::viewModelMaps: the tracking camera's view from the current model maps, (rows, cols, 4) uint8"""
+        out = np.empty((self.cam[1], self.cam[0], 4), np.uint8)
+        r = self.h.hkf_app_view_model_maps(int(mode), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("viewModelMaps failed: %d" % r)
+        return out
+
     def close(self):
         self.h.hkf_app_shutdown()
 

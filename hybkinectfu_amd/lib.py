@@ -93,6 +93,7 @@ TRI_DTYPE = np.dtype([("v", VERTEX_DTYPE, (3,))])
 MAP_RAW_DEPTH, MAP_TRUNCED_DEPTH, MAP_FILTERED_DEPTH = 0, 1, 2
 MAP_NEW_VERTICES, MAP_NEW_NORMALS, MAP_MODEL_VERTICES, MAP_MODEL_NORMALS = 3, 4, 5, 6
 MAP_RAW_RGB, MAP_RAYCAST_RGB = 7, 8
+VIEW_NORMALS, VIEW_SHADED, VIEW_COLOR = 0, 1, 2                      # kf_render_view / kf_view_model_maps: mode
 
 # every symbol include/hybkf.h declares (tests check that the library exports each of them)
 SYMBOLS = [
@@ -112,6 +113,7 @@ SYMBOLS = [
     "kf_get_fusion_form", "kf_get_raycast_form",
     "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
     "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
+    "kf_render_view", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
 ]
 
 
@@ -138,6 +140,7 @@ def load():
         _lib.kf_error_string.restype = C.c_char_p
         _lib.kf_version.restype = C.c_char_p
         _lib.kf_stream.restype = C.c_void_p
+        _lib.kf_view_device.restype = C.c_void_p
     return _lib
 
 
@@ -381,6 +384,36 @@ class Context:
         tp = C.byref(Mat44.of(pose)) if pose is not None else None
         _chk(self.lib.kf_raycast_volume(self.h, int(has_color), tp, C.byref(rp), C.byref(self.cam), C.c_float(near), C.c_float(far)),
              "kf_raycast_volume")
+
+    # ---- viewer frames ----
+    def render_view(self, mode, pose, cam, inc, near, far, dev_v=None, dev_n=None):
+        """a free viewpoint: march `cam` (lib.camera, any size) from `pose` (None: the device-resident pose) into the context's BGRA view image;
+        dev_v / dev_n: optional device addresses of float4 maps of cam's size.  Asynchronous; tracking state is left alone (kf_render_view)"""
+        rp = RaycastParams(inc)
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_render_view(self.h, int(mode), tp, C.byref(cam), C.byref(rp), C.c_float(near), C.c_float(far),
+                                     C.c_void_p(dev_v), C.c_void_p(dev_n)), "kf_render_view")
+
+    def view_model_maps(self, mode):
+        """the tracking camera's view from the current model maps, KF_MAP_RAYCAST_RGB and the device pose: no march (kf_view_model_maps)"""
+        _chk(self.lib.kf_view_model_maps(self.h, int(mode)), "kf_view_model_maps")
+
+    def view_size(self):
+        """(cols, rows) of the last view"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_view_size(self.h, C.byref(a), C.byref(b)), "kf_view_size")
+        return a.value, b.value
+
+    def view_device(self):
+        """device address of the last view's image (rows x cols x 4 bytes: b, g, r, a), valid in stream order; None before a view"""
+        return self.lib.kf_view_device(self.h)
+
+    def read_view(self):
+        """the last view as a (rows, cols, 4) uint8 array (b, g, r, a); blocking"""
+        cols, rows = self.view_size()
+        out = np.empty((rows, cols, 4), np.uint8)
+        _chk(self.lib.kf_read_view(self.h, _p(out), C.c_size_t(out.nbytes)), "kf_read_view")
+        return out
 
     def raycast_form(self):
         """what the last raycast launch took (kf_get_raycast_form): a dict of the kf_raycast_form fields"""

@@ -344,6 +344,34 @@ int kf_read_mesh(kf_ctx* ctx, float* vertices, float* normals, float* colors, ui
 /* frees the weld's scratch and mesh (MeshData::clear, src/utils/mesh/meshData.h:440); the next kf_weld_mesh allocates again */
 int kf_weld_release(kf_ctx* ctx);
 
+/* Viewer frames.  The reference shows three pictures per frame (src/HybKinectfu.cpp:145-158): DataViewer::viewNormal on the new and the model
+ * normals and DataViewer::viewColors on the raycast colours -- each a blocking clone(CPU) of a whole map and a loop on one host thread
+ * (src/DataViewer.cpp:13-44).  Here the picture is made on the device, 4 bytes per pixel (b, g, r, a from the low byte up) in a context-owned image
+ * that grows on demand and is freed by kf_destroy; both producers are asynchronous on the context's stream, so a view enqueued after
+ * kf_integrate_volume sees that frame's volume.  Bytes 0-2 by mode, byte 3 = 255 on a hit (vertex w == 1), else 0; fp32, one rounding per operation:
+ *   KF_VIEW_NORMALS  (unsigned char)((255.f * (n.c + 1.f)) / 2.f) for c = x, y, z: DataViewer.cpp:24-26 byte for byte (127, 127, 127 without a normal);
+ *   KF_VIEW_SHADED   one grey level, 0 without a hit: d = eye - v (eye: the pose's translation), s = (d.x*d.x + d.y*d.y) + d.z*d.z,
+ *                    c = ((n.x*d.x + n.y*d.y) + n.z*d.z) / sqrtf(s) clamped to [0, 1] (NaN -> 0), g = (unsigned char)(32.f + 223.f * c);
+ *   KF_VIEW_COLOR    b, g, r of interpolateColor at the vertex (src/cuda/raycastingVolume.cu:91-92): KF_MAP_RAYCAST_RGB's bytes, kept whether or
+ *                    not the gradient succeeded, 0 without a crossing.  KF_ERR_STATE on a context without a colour plane.
+ * kf_render_view: a free viewpoint -- the march of kf_raycast_volume (raycastKernel, src/cuda/raycastingVolume.cu:121-156: same vertices, normals
+ *   and colours, bit for bit) for `view_cam`, any size from 1 to 4096 each way, from `pose` (NULL: the device-resident pose).  dev_v / dev_n: optional
+ *   caller-owned float4 maps of view_cam's size that receive what kf_raycast_volume would have written; either may be NULL.  It is a bystander to
+ *   tracking: the model maps, KF_MAP_RAYCAST_RGB, kf_get_raycast_form's record, a pending kf_prefetch_frame and the stage timers are left as they
+ *   are.  KF_ERR_ARG: bad mode, bad camera, NULL context or increment.  KF_ERR_STATE: a z-slab context that does not own the whole volume (it sees
+ *   only its own layers).
+ * kf_view_model_maps: the tracking camera's view without a march -- the same bytes from level 0 of the context's CURRENT model maps,
+ *   KF_MAP_RAYCAST_RGB and the device-resident pose.  Allowed on z-slab contexts: after kf_set_model_maps_rays every member holds the merged maps.
+ * kf_view_size: the size of the last view (KF_ERR_STATE before one).  kf_view_device: the image in HBM, valid in stream order until the next view
+ *   (NULL before one).  kf_read_view: blocking copy of cols * rows * 4 bytes. */
+enum { KF_VIEW_NORMALS = 0, KF_VIEW_SHADED = 1, KF_VIEW_COLOR = 2 };
+int kf_render_view(kf_ctx* ctx, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* raycast_params,
+                   float near_plane, float far_plane, float* dev_v, float* dev_n);
+int kf_view_model_maps(kf_ctx* ctx, int mode);
+int kf_view_size(kf_ctx* ctx, uint32_t* cols, uint32_t* rows);
+const uint8_t* kf_view_device(kf_ctx* ctx);
+int kf_read_view(kf_ctx* ctx, uint8_t* dst, size_t dst_bytes);
+
 /* CudaMap2D::clone(CPU) / copyDataFrom on the singleton's maps (debug + parity; blocking) */
 int kf_download_map(kf_ctx* ctx, int map_id, uint32_t level, void* dst, size_t dst_bytes);
 int kf_upload_map(kf_ctx* ctx, int map_id, uint32_t level, const void* src, size_t src_bytes);

@@ -114,7 +114,10 @@ int kf_group_frame_members_color(kf_group* g, const uint16_t* const* dev_mm, con
  * frames fused / lost with member 0's; a disagreement returns KF_GROUP_ERR_STATE (in-process members only: a RCCL_RANK
  * group compares nothing across processes). */
 int kf_group_track_result(kf_group* g, kf_track_result* out, int check_lockstep);
-/* borrowed: for read-backs (maps, volume, stats).  The group owns the context and its stream; do not destroy it or change its stream. */
+/* borrowed: for read-backs (maps, volume, stats).  The group owns the context and its stream; do not destroy it or change its stream.
+ * Viewer frames (hybkf.h): after step 9 every member holds the merged model maps, so kf_view_model_maps on any member -- member 0 by
+ * convention -- gives the whole volume's picture from the tracking camera.  A FREE viewpoint over a group is out of scope: kf_render_view
+ * refuses a member that does not own the whole volume (KF_ERR_STATE), because it sees only its own layers. */
 int kf_group_member(kf_group* g, uint32_t i, kf_ctx** out);
 /* kf_marching_cubes on every member (each extracts its own layers); a colour group extracts with colour */
 int kf_group_marching_cubes(kf_group* g, float threshold);

@@ -1,0 +1,72 @@
+#!/usr/bin/env python3
+"""Pictures of a scanned model from an orbit of viewpoints: fuse Scene S, then render N poses on a circle around the volume's centre with
+kf_render_view at a chosen size and mode, and write one picture per pose into a directory.
+  usage: tools/render_orbit.py OUT_DIR [--n 12] [--size 640x480] [--mode normals|shaded|color] [--res 256] [--volume 3.0] [--frames 12]
+PNG through PIL where it is installed, binary PPM otherwise (no hit: black)."""
+import argparse, math, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+from hybkinectfu_amd import lib as K, scene as S
+
+ap = argparse.ArgumentParser()
+ap.add_argument("out_dir")
+ap.add_argument("--n", type=int, default=12)
+ap.add_argument("--size", default="640x480")
+ap.add_argument("--mode", default="shaded", choices=("normals", "shaded", "color"))
+ap.add_argument("--res", type=int, default=256)
+ap.add_argument("--volume", type=float, default=3.0)
+ap.add_argument("--frames", type=int, default=12)
+args = ap.parse_args()
+cols, rows = (int(v) for v in args.size.lower().split("x"))
+mode = dict(normals=K.VIEW_NORMALS, shaded=K.VIEW_SHADED, color=K.VIEW_COLOR)[args.mode]
+P, cam, size, res = S.STOCK, S.vga_camera(), args.volume, args.res
+trunc = max(P["integrate_sdf_trunc"], 5 * size / res)
+color = mode == K.VIEW_COLOR
+
+ctx = K.Context(K.camera(*cam), res, size, P["volume_max_weight"], levels=3, has_color=color)
+for k in range(args.frames):
+    pose = S.trajectory_pose(k, size).astype(np.float32)
+    mm = S.render_depth_mm(pose, cam, size)
+    ctx.upload_depth_mm(mm)
+    if color:                                                   # a picture to fuse: the depth as a colour ramp
+        g = (mm // 8 % 256).astype(np.uint8)
+        ctx.upload_rgb(np.stack([g, 255 - g, (g // 2 + 64).astype(np.uint8)], axis=-1))
+    ctx.preprocess(P["depth_trunc_min"], P["depth_trunc_max"], P["filter_sigma_pixel"], P["filter_sigma_depth"])
+    ctx.integrate(pose, trunc, P["integrate_depth_trunc"], has_color=color, angle_weight=color)
+
+
+def look(eye, target):
+    """camera -> world: z towards the target, y down the image (world +y), float32"""
+    z = np.asarray(target, np.float64) - np.asarray(eye, np.float64)
+    z /= np.linalg.norm(z)
+    x = np.cross((0.0, 1.0, 0.0), z)
+    x /= np.linalg.norm(x)
+    p = np.eye(4)
+    p[:3, 0], p[:3, 1], p[:3, 2], p[:3, 3] = x, np.cross(z, x), z, eye
+    return p.astype(np.float32)
+
+
+def save(path, bgra):
+    rgb = np.ascontiguousarray(bgra[..., 2::-1]) * (bgra[..., 3:4] > 0)
+    try:
+        from PIL import Image
+        Image.fromarray(rgb, "RGB").save(path + ".png")
+        return path + ".png"
+    except ImportError:
+        with open(path + ".ppm", "wb") as f:
+            f.write(b"P6\n%d %d\n255\n" % (rgb.shape[1], rgb.shape[0]))
+            f.write(rgb.tobytes())
+        return path + ".ppm"
+
+
+os.makedirs(args.out_dir, exist_ok=True)
+view_cam = K.camera(cols, rows, (cols - 1) / 2.0, (rows - 1) / 2.0, 525.0 * cols / 640.0, 525.0 * cols / 640.0)
+centre = np.array([0.5 * size, 0.5 * size, 0.5 * size])
+# the orbit starts at the scanning camera's side (-z) and swings a third of a turn to either side of it: what the scan saw and where it ends
+for i in range(args.n):
+    a = math.radians(-60.0 + 120.0 * i / max(args.n - 1, 1))
+    eye = centre + 0.75 * size * np.array([math.sin(a), -0.15, -math.cos(a)])
+    ctx.render_view(mode, look(eye, centre), view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
+    img = ctx.read_view()
+    print("%s  hits %d" % (save(os.path.join(args.out_dir, "orbit_%03d" % i), img), int((img[..., 3] == 255).sum())))
+ctx.close()
