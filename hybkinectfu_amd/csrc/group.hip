@@ -116,6 +116,15 @@ struct kf_group {
   uint64_t* ta_min = nullptr;
   float* cand_sum = nullptr;
   int grid = 0;
+  // merged views (kf_group_render_view): buffers of the group's own, so a view never touches a frame's; they hold view_cap_px pixels (g->words
+  // words per candidate pixel), grow on demand and mirror the frame's set -- per member ta / spec / cand, on RCCL ta_own, on LOCAL the two group buffers
+  uint64_t* view_ta[KF_GROUP_MAX_MEMBERS] = {};
+  uint64_t* view_ta_own[KF_GROUP_MAX_MEMBERS] = {};
+  float* view_spec[KF_GROUP_MAX_MEMBERS] = {};
+  float* view_cand[KF_GROUP_MAX_MEMBERS] = {};
+  uint64_t* view_ta_min = nullptr;
+  float* view_cand_sum = nullptr;
+  size_t view_cap_px = 0;
   bool failed = false;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // merge timers: a pool of at most KF_GROUP_MAX_TIMED_FRAMES, ev_used of them recorded since the last read
@@ -186,13 +195,15 @@ void release(kf_group* g) {
     hipSetDevice(g->dev[i]);
     if (g->comm[i]) ncclCommDestroy(g->comm[i]);
     if (g->m[i]) kf_destroy(g->m[i]);            // (a member on the group stream returns to its own stream first)
-    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i], g->rgb[i]};
+    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i], g->rgb[i], g->view_ta[i], g->view_ta_own[i], g->view_spec[i], g->view_cand[i]};
     for (void* b : bufs) if (b) hipFree(b);
   }
   if (g->n) hipSetDevice(g->dev[0]);
   for (auto& e : g->ev) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
   if (g->ta_min) hipFree(g->ta_min);
   if (g->cand_sum) hipFree(g->cand_sum);
+  if (g->view_ta_min) hipFree(g->view_ta_min);
+  if (g->view_cand_sum) hipFree(g->view_cand_sum);
   if (g->stream) { hipStreamSynchronize(g->stream); hipStreamDestroy(g->stream); }
 }
 
@@ -241,13 +252,13 @@ int build(kf_group* g, const uint8_t* unique_id) {
   return 0;
 }
 
-int reduce_local(kf_group* g, bool words) {
-  const size_t npx = (size_t)g->base.depth_camera.cols * g->base.depth_camera.rows;
+// words: the MIN over `elems` 64-bit crossing words, else the integer SUM over `elems` 32-bit candidate words; src: one buffer per member
+int reduce_local(kf_group* g, bool words, size_t elems, const void* const* src, void* dst) {
   GroupReduceArgs a;
   memset(&a, 0, sizeof(a));
-  for (uint32_t i = 0; i < g->n; ++i) a.src[i] = words ? (const void*)g->ta[i] : (const void*)g->cand[i];
-  a.dst = words ? (void*)g->ta_min : (void*)g->cand_sum;
-  const size_t elems = words ? npx : g->words * npx, per16 = words ? 2 : 4;
+  for (uint32_t i = 0; i < g->n; ++i) a.src[i] = src[i];
+  a.dst = dst;
+  const size_t per16 = words ? 2 : 4;
   a.n16 = (unsigned)(elems / per16);
   a.tail = (unsigned)(elems % per16);
   const unsigned need = (a.n16 + KF_GROUP_BLOCK - 1) / KF_GROUP_BLOCK;
@@ -275,10 +286,10 @@ int merge(kf_group* g) {
   const size_t npx = (size_t)cam->cols * cam->rows;
   int st = 0;
   if (g->backend == KF_GROUP_LOCAL) {
-    if ((st = reduce_local(g, true))) return st;
+    if ((st = reduce_local(g, true, npx, (const void* const*)g->ta, g->ta_min))) return st;
     for (uint32_t i = 0; i < n; ++i)
       if ((st = member_normals(g, i, g->ta_min, g->ta[i]))) return st;
-    if ((st = reduce_local(g, false))) return st;
+    if ((st = reduce_local(g, false, g->words * npx, (const void* const*)g->cand, g->cand_sum))) return st;
     for (uint32_t i = 0; i < n; ++i)
       if ((st = member_maps(g, i, g->ta_min, g->cand_sum))) return st;
     return 0;
@@ -361,6 +372,77 @@ int frame(kf_group* g, const uint16_t* const* dev_mm, const uint16_t* host_mm, u
     ++g->ev_used;
   }
   return 0;
+}
+
+// ---- merged views ---------------------------------------------------------------------------------------------------------------------------
+bool view_cam_ok(const kf_camera_params* cam) {      // kf_render_view's limits
+  return cam && cam->cols >= 1 && cam->cols <= 4096 && cam->rows >= 1 && cam->rows <= 4096 && cam->fx != 0.f && cam->fy != 0.f &&
+         cam->fx == cam->fx && cam->fy == cam->fy && cam->cx == cam->cx && cam->cy == cam->cy;
+}
+
+// the view buffers for npx pixels: growing frees the old ones (hipFree waits for the work that still uses them)
+int view_reserve(kf_group* g, size_t npx) {
+  if (npx <= g->view_cap_px) return 0;
+  int st = 0;
+  g->view_cap_px = 0;
+  for (uint32_t i = 0; i < g->n; ++i) {
+    if ((st = (int)hipSetDevice(g->dev[i]))) return st;
+    void** bufs[] = {(void**)&g->view_ta[i], (void**)&g->view_ta_own[i], (void**)&g->view_spec[i], (void**)&g->view_cand[i]};
+    for (void** b : bufs) if (*b) { hipFree(*b); *b = nullptr; }
+    if ((st = group_alloc((void**)&g->view_ta[i], npx * 8))) return st;
+    if ((st = group_alloc((void**)&g->view_spec[i], npx * 4 * g->words))) return st;
+    if ((st = group_alloc((void**)&g->view_cand[i], npx * 4 * g->words))) return st;
+    if (g->backend != KF_GROUP_LOCAL && (st = group_alloc((void**)&g->view_ta_own[i], npx * 8))) return st;
+  }
+  if (g->backend == KF_GROUP_LOCAL) {
+    if ((st = (int)hipSetDevice(g->dev[0]))) return st;
+    if (g->view_ta_min) { hipFree(g->view_ta_min); g->view_ta_min = nullptr; }
+    if (g->view_cand_sum) { hipFree(g->view_cand_sum); g->view_cand_sum = nullptr; }
+    if ((st = group_alloc((void**)&g->view_ta_min, npx * 8))) return st;
+    if ((st = group_alloc((void**)&g->view_cand_sum, npx * 4 * g->words))) return st;
+  }
+  g->view_cap_px = npx;
+  return 0;
+}
+
+// the five steps of kf_group_render_view; the arguments have passed kf_group_view_validate
+int view(kf_group* g, int mode, const kf_mat44* pose, const kf_camera_params* cam, float near_plane, float far_plane, float* dev_v, float* dev_n) {
+  const int color = mode == KF_VIEW_COLOR ? 1 : 0;
+  const uint32_t n = g->n, words = color ? 4 : 3;                 // (words <= g->words: KF_VIEW_COLOR only on a colour group)
+  const size_t npx = (size_t)cam->cols * cam->rows;
+  const kf_raycast_params* rp = &g->p.raycast;
+  const bool local = g->backend == KF_GROUP_LOCAL;
+  int st = 0;
+  if ((st = view_reserve(g, npx))) return st;
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((st = hipSetDevice(g->dev[i]))) return st;
+    if ((st = kf_view_slab_cross(g->m[i], color, pose, cam, rp, near_plane, far_plane, g->view_ta[i], local ? g->view_ta[i] : g->view_ta_own[i], g->view_spec[i]))) return st;
+  }
+  if (local) {
+    if ((st = reduce_local(g, true, npx, (const void* const*)g->view_ta, g->view_ta_min))) return st;
+  } else {
+    if ((st = nccl_status(ncclGroupStart()))) return st;
+    for (uint32_t i = 0; i < n && !st; ++i)
+      st = nccl_status(ncclAllReduce(g->view_ta[i], g->view_ta[i], npx, ncclUint64, ncclMin, g->comm[i], member_stream(g, i)));
+    const int st_end = nccl_status(ncclGroupEnd());
+    if (st || st_end) return st ? st : st_end;
+  }
+  for (uint32_t i = 0; i < n; ++i) {
+    if ((st = hipSetDevice(g->dev[i]))) return st;
+    if ((st = kf_view_slab_normals(g->m[i], color, pose, cam, rp, near_plane, far_plane, local ? g->view_ta_min : g->view_ta[i],
+                                   local ? g->view_ta[i] : g->view_ta_own[i], g->view_spec[i], g->view_cand[i]))) return st;
+  }
+  if (local) {
+    if ((st = reduce_local(g, false, words * npx, (const void* const*)g->view_cand, g->view_cand_sum))) return st;
+  } else {
+    if ((st = nccl_status(ncclGroupStart()))) return st;
+    for (uint32_t i = 0; i < n && !st; ++i)
+      st = nccl_status(ncclAllReduce(g->view_cand[i], g->view_cand[i], words * npx, ncclInt32, ncclSum, g->comm[i], member_stream(g, i)));
+    const int st_end = nccl_status(ncclGroupEnd());
+    if (st || st_end) return st ? st : st_end;
+  }
+  if ((st = hipSetDevice(g->dev[0]))) return st;
+  return kf_view_from_rays(g->m[0], mode, pose, cam, local ? g->view_ta_min : g->view_ta[0], local ? g->view_cand_sum : g->view_cand[0], words, dev_v, dev_n);
 }
 }  // namespace
 
@@ -517,6 +599,40 @@ int kf_group_member(kf_group* g, uint32_t i, kf_ctx** out) {
 void* kf_group_stream(kf_group* g, uint32_t i) {
   if (!g || i >= g->n) return nullptr;
   return (void*)member_stream(g, i);
+}
+
+int kf_group_view_validate(int color_group, int mode, const kf_camera_params* view_cam) {
+  if (mode != KF_VIEW_NORMALS && mode != KF_VIEW_SHADED && mode != KF_VIEW_COLOR) return KF_GROUP_ERR_ARG;
+  if (!view_cam_ok(view_cam)) return KF_GROUP_ERR_ARG;
+  if (mode == KF_VIEW_COLOR && !color_group) return KF_GROUP_ERR_STATE;
+  return 0;
+}
+
+int kf_group_render_view(kf_group* g, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, float near_plane, float far_plane,
+                         float* dev_v, float* dev_n) {
+  if (!g) return KF_GROUP_ERR_ARG;
+  const int st = kf_group_view_validate(g->color ? 1 : 0, mode, view_cam);
+  if (st) return st;                                         // (nothing is enqueued, the group stays usable)
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  DeviceGuard guard;
+  return fail(g, view(g, mode, pose, view_cam, near_plane, far_plane, dev_v, dev_n));
+}
+
+int kf_group_view_size(kf_group* g, uint32_t* cols, uint32_t* rows) {
+  if (!g) return KF_GROUP_ERR_ARG;
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  return kf_view_size(g->m[0], cols, rows);                  // (KF_ERR_STATE before a view)
+}
+
+const uint8_t* kf_group_view_device(kf_group* g) { return (g && !g->failed) ? kf_view_device(g->m[0]) : nullptr; }
+
+int kf_group_read_view(kf_group* g, uint8_t* dst, size_t dst_bytes) {
+  if (!g || !dst) return KF_GROUP_ERR_ARG;
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  DeviceGuard guard;
+  int st = (int)hipSetDevice(g->dev[0]);
+  if (!st) st = kf_read_view(g->m[0], dst, dst_bytes);
+  return (st == KF_GROUP_ERR_ARG || st == KF_GROUP_ERR_STATE) ? st : fail(g, st);      // (a buffer too small, no view yet: refusals, the group stays usable)
 }
 
 int kf_group_marching_cubes(kf_group* g, float threshold) {

@@ -358,9 +358,14 @@ __device__ __forceinline__ void rc_tile_bounds(const RaycastArgs& a, const unsig
 // VIEW (compile time; kf_render_view): 0, or 1 + KF_VIEW_* -- the epilogue turns the lane's vertex, normal and colour into one display word in registers
 // (view_pixel.h) and stores it to view_img; the float4 maps only where the caller gave buffers (a.out_v / a.out_n may be null), no colour map, no
 // crossing words, no pyramid, no work counters.  a.cam is then the CALLER's camera: the grid, the tile bounds and the pixel index all follow it.
+// VIEW == RC_VIEW_CROSS (compile time; kf_view_slab_cross): the z-slab march with speculation -- out_ta, own_ta and out_spec are all given, 3 or (SPEC_COLOR)
+// 4 speculative words per pixel -- for the CALLER's camera, as a member's step of a merged view: the crossing words are the only stores; no model
+// maps, no out_t / out_rgb, no pyramid, no work counters.
+#define RC_VIEW_CROSS (-1)
 template <bool SPEC_COLOR, int VIEW = 0>
 __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, int tile_y, unsigned* s_tables, unsigned* view_img = nullptr) {
   const KfVolume& v = a.vol;
+  constexpr bool CROSS = VIEW == RC_VIEW_CROSS;
   // Packed bit tables live in LDS so that the empty-space walk costs LDS reads instead of dependent L2 round trips: one bit
   // per 32^3-voxel macro cell and per 128^3-voxel super cell of the whole volume (KfVolume::macrobits, kept current by the
   // fusion pass with atomicOr: copied as they are), and -- when it fits -- one bit per stored 8^3 brick (KfVolume::negbits).
@@ -452,18 +457,18 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
         const float alpha = t_cross - a.inc * ftdt / (ftdt - ft);
         const float3 vtx = kf_add(org, kf_scale(dir, alpha));
         bool want = true;
-        if (a.out_ta) {
+        if (CROSS || a.out_ta) {
           out_alpha = alpha;
           int gzv = kf_f2i(kf_div(vtx.z * (float)v.res, rS));
           gzv = max(0, min(gzv, v.res - 1));
-          want = a.out_spec != nullptr && __float_as_uint(alpha) != 0u && gzv >= v.own_z0 && gzv < v.own_z1;
+          want = (CROSS || a.out_spec != nullptr) && __float_as_uint(alpha) != 0u && gzv >= v.own_z0 && gzv < v.own_z1;
           // the colour at the vertex (:91-92), before and independently of the gradient: it stays whether or not a normal is found
           if (SPEC_COLOR && want) { uchar4 c = make_uchar4(0, 0, 0, 0); kf_interpolate_color(v, vtx, c); out_c = c; }
         } else if (a.has_color) { uchar4 c = make_uchar4(0, 0, 0, 0); kf_interpolate_color(v, vtx, c); out_c = c; }
         float3 grad;
         if (want && gradient_for_point_either<RC_GRAD_BATCH, RC_GRAD_ROUNDS>(a.shared_grad, ((tile_x + tile_y + wave) & 1) != 0, v, last_pos, vtx, rS, rcell, grad)) {
           out_n = make_float4(grad.x, grad.y, grad.z, 0.f);
-          if (!a.out_ta) { out_v = make_float4(vtx.x, vtx.y, vtx.z, 1.0f); out_alpha = alpha; }
+          if (!CROSS && !a.out_ta) { out_v = make_float4(vtx.x, vtx.y, vtx.z, 1.0f); out_alpha = alpha; }
         }
       }
     } else if (t_cross < inf) out_v = make_float4(t_cross, 0.f, 0.f, 1.f);
@@ -475,22 +480,22 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
     out_n = make_float4((float)n_samp, (float)(n_macro & 0xFFFF), (float)(n_macro >> 16), 0.f);
   }
 #endif
-  if (VIEW) {
+  if (VIEW > 0) {
     if (a.out_v) a.out_v[pix] = out_v;
     if (a.out_n) a.out_n[pix] = out_n;
-    view_img[pix] = kf_view_pixel<(VIEW ? VIEW - 1 : 0)>(out_v, out_n, out_c, org);     // the eye is the pose's translation: the ray origin
+    view_img[pix] = kf_view_pixel<(VIEW > 0 ? VIEW - 1 : 0)>(out_v, out_n, out_c, org);     // the eye is the pose's translation: the ray origin
   } else
-  if (a.out_ta) {
+  if (CROSS || a.out_ta) {
     const unsigned long long word = ((unsigned long long)__float_as_uint(t_cross) << 32) | (unsigned long long)(t_cross < inf ? __float_as_uint(out_alpha) : 0u);
     a.out_ta[pix] = word;
     if (SPEC_COLOR) {
       a.own_ta[pix] = word; a.out_spec[4 * pix] = out_n.x; a.out_spec[4 * pix + 1] = out_n.y; a.out_spec[4 * pix + 2] = out_n.z;
       a.out_spec[4 * pix + 3] = __uint_as_float(rc_color_word(out_c));
     } else
-    if (a.out_spec) { a.own_ta[pix] = word; a.out_spec[3 * pix] = out_n.x; a.out_spec[3 * pix + 1] = out_n.y; a.out_spec[3 * pix + 2] = out_n.z; }
+    if (CROSS || a.out_spec) { a.own_ta[pix] = word; a.out_spec[3 * pix] = out_n.x; a.out_spec[3 * pix + 1] = out_n.y; a.out_spec[3 * pix + 2] = out_n.z; }
   }
   else { a.out_v[pix] = out_v; a.out_n[pix] = out_n; }
-  if (!VIEW && a.work) {
+  if (VIEW == 0 && a.work) {
     // what the REFERENCE's march reads for this ray (raycastingVolume.cu:65-119): one voxel per sample from t_min up to the
     // crossing (or t_max); a crossing is evaluated with 2 + 6 trilinear look-ups of 8 voxels each
     const float t_stop = t_cross < inf ? t_cross : ref_tmax;
@@ -502,14 +507,14 @@ __device__ __forceinline__ void raycast_tile(const RaycastArgs& a, int tile_x, i
       atomicAdd(&a.work->rc_hits[sh * 16], (unsigned long long)hits);
     }
   }
-  if (!VIEW && a.out_t) a.out_t[pix] = t_cross;
-  if (!VIEW && a.has_color) a.out_rgb[pix] = out_c;
+  if (VIEW == 0 && a.out_t) a.out_t[pix] = t_cross;
+  if (VIEW == 0 && a.has_color) a.out_rgb[pix] = out_c;
   };
   if (live) march_pixel();
   // Levels 1 and 2 of the model maps' pyramids, which the NEXT frame's tracker reads first (ICP.cpp:57-60): a 32x16 tile holds whole 2x2 and
   // 4x4 blocks, so the workgroup that produced the texels averages them itself -- through the LDS the bit tables occupied until its last wave
   // left the march -- and the tracker's pyramid launch (a pass over four maps, ~8 us) has nothing left to do.
-  if (!VIEW && a.pyr.v1) {                                                   // uniform
+  if (VIEW == 0 && a.pyr.v1) {                                                 // uniform
     __syncthreads();                                                         // every wave is done with the tables
     float4* s_v = reinterpret_cast<float4*>(s_tables);
     float4* s_n = s_v + 32 * 16, *s1_v = s_n + 32 * 16, *s1_n = s1_v + 16 * 8;
@@ -534,6 +539,13 @@ template <int MODE>
 __global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast_view(RaycastArgs a, unsigned* img) {
   extern __shared__ unsigned s_dyn[];
   raycast_tile<false, MODE + 1>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn, img);
+}
+
+// kf_view_slab_cross: the z-slab march for the caller's camera (RC_VIEW_CROSS); COLOR: 4 speculative words per pixel
+template <bool COLOR>
+__global__ void __launch_bounds__(RAYCAST_THREADS) k_raycast_view_cross(RaycastArgs a) {
+  extern __shared__ unsigned s_dyn[];
+  raycast_tile<COLOR, RC_VIEW_CROSS>(a, (int)blockIdx.x, (int)blockIdx.y, s_dyn);
 }
 
 // The raycast with the NEXT frame's depth conversion + gate + bilateral filter riding along (kf_prefetch_frame, fused form).  The raycast
@@ -844,9 +856,10 @@ __global__ void __launch_bounds__(256) k_slab_ray_normals(SlabNormalArgs a) { sl
 __global__ void __launch_bounds__(256) k_slab_ray_normals_color(SlabNormalArgs a) { slab_ray_normals_body<true>(a); }
 static int slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_raycast_params* rp, const kf_camera_params* cam,
                             float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand,
-                            bool color = false) {
+                            bool color = false, bool view = false) {
   if (!c || !rp || !cam || !dev_ta_min || !dev_cand) return KF_ERR_ARG;
-  if ((int)cam->cols != c->cols || (int)cam->rows != c->rows) return KF_ERR_ARG;
+  // (the kernels follow a.cam alone -- the pixel, its ray and the buffers' index -- so a view's camera needs only a grid of its own size)
+  if (view ? !view_cam_ok(cam) : ((int)cam->cols != c->cols || (int)cam->rows != c->rows)) return KF_ERR_ARG;
   if (color && !c->vol.color) return KF_ERR_STATE;
   SlabNormalArgs a;
   a.vol = c->vol; a.ta = (const unsigned long long*)dev_ta_min; a.cand = dev_cand;
@@ -855,8 +868,9 @@ static int slab_ray_normals(kf_ctx* c, const kf_mat44* transform, const kf_rayca
   a.inc = rp->ray_increment; a.near_plane = near_plane; a.far_plane = far_plane;
   a.shared_grad = rc_shared_grad_for(c->vol);
   kf_pose_arg(c, transform, a.pose, a.pose_val);
-  if (color) hipLaunchKernelGGL(k_slab_ray_normals_color, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
-  else hipLaunchKernelGGL(k_slab_ray_normals, dim3(kf_div_up(c->cols, 32), kf_div_up(c->rows, 8)), dim3(256), 0, c->stream, a);
+  const dim3 grid(kf_div_up(a.cam.cols, 32), kf_div_up(a.cam.rows, 8));
+  if (color) hipLaunchKernelGGL(k_slab_ray_normals_color, grid, dim3(256), 0, c->stream, a);
+  else hipLaunchKernelGGL(k_slab_ray_normals, grid, dim3(256), 0, c->stream, a);
   return (int)hipGetLastError();
 }
 // dev_ta_own and dev_spec (4 words per pixel) may both be NULL: then every owned vertex is evaluated here
@@ -925,6 +939,75 @@ extern "C" int kf_set_model_maps_rays(kf_ctx* c, const kf_mat44* transform, cons
 }
 extern "C" int kf_set_model_maps_rays_color(kf_ctx* c, const kf_mat44* transform, const kf_camera_params* cam, const uint64_t* dev_ta_min, const float* dev_cand) {
   return set_model_maps_rays(c, transform, cam, dev_ta_min, dev_cand, true);
+}
+
+// ---- a merged view over z-slabs: the three per-member steps (what kf_group_render_view enqueues) ----------------------------------------------------
+// The ray-form merge above for the CALLER's camera, ending in display bytes instead of model maps: kf_view_slab_cross on every member, the MIN
+// all-reduce, kf_view_slab_normals on every member, the integer SUM all-reduce, kf_view_from_rays on one.  All three are bystanders exactly as
+// kf_render_view is: the model maps and model_pyr_ok, raycast_rgb, kf_get_raycast_form's record, a pending kf_prefetch_frame note (no riders), the
+// stage timers and the work counters are left alone.  A whole-volume context owns every layer and is accepted too.
+extern "C" int kf_view_slab_cross(kf_ctx* c, int color, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* rp,
+                                  float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec) {
+  if (!c || !rp || !dev_ta || !dev_ta_own || !dev_spec) return KF_ERR_ARG;
+  if (!view_cam_ok(view_cam)) return KF_ERR_ARG;
+  { const int st = slab_halo_check(c, rp); if (st) return st; }
+  if (color && !c->vol.color) return KF_ERR_STATE;
+  RaycastOut out = {}; out.output = KF_RC_OUT_TA_SPEC; out.color = color != 0;       // (not the model maps: raycast_args arms no pyramid)
+  out.ta = (unsigned long long*)dev_ta; out.own_ta = (unsigned long long*)dev_ta_own; out.spec = dev_spec;
+  RaycastArgs a; kf_raycast_form form; size_t lds;
+  { const int st = raycast_args(c, 0, pose, rp, view_cam, near_plane, far_plane, out, a, form, lds); if (st) return st; }
+  a.out_v = nullptr; a.out_n = nullptr; a.out_rgb = nullptr; a.work = nullptr;
+  const dim3 grid(kf_div_up((int)view_cam->cols, 32), kf_div_up((int)view_cam->rows, 16)), block(RAYCAST_THREADS);
+  if (color) hipLaunchKernelGGL(k_raycast_view_cross<true>, grid, block, lds, c->stream, a);
+  else hipLaunchKernelGGL(k_raycast_view_cross<false>, grid, block, lds, c->stream, a);
+  return (int)hipGetLastError();
+}
+extern "C" int kf_view_slab_normals(kf_ctx* c, int color, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* rp,
+                                    float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec,
+                                    float* dev_cand) {
+  if ((dev_ta_own == nullptr) != (dev_spec == nullptr)) return KF_ERR_ARG;
+  return slab_ray_normals(c, pose, rp, view_cam, near_plane, far_plane, dev_ta_min, dev_ta_own, dev_spec, dev_cand, color != 0, true);
+}
+// one pixel per lane: what slab_rays_unpack_body does for the model maps -- the vertex org + dir * alpha where the candidate normal has a set bit, the
+// colour from the fourth word whatever the normal -- pushed through the pixel function; the eye is the pose's translation, the ray's origin
+struct ViewRaysArgs { const unsigned long long* ta; const float* cand; unsigned* img; float4* v; float4* n; KfCam cam; const float* pose; KfMat pose_val; };
+template <int MODE, int W>
+__global__ void __launch_bounds__(256) k_view_from_rays(ViewRaysArgs a) {
+  const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+  if (i >= a.cam.cols * a.cam.rows) return;
+  const int y = i / a.cam.cols, x = i - y * a.cam.cols;
+  const float3 cd = kf3(a.cand[W * i], a.cand[W * i + 1], a.cand[W * i + 2]);
+  const uchar4 col = W == 4 ? rc_word_color(__float_as_uint(a.cand[W * i + 3])) : make_uchar4(0, 0, 0, 0);
+  float3 org, dir, cam_dir;
+  rc_pixel_ray(a.cam, a.pose ? a.pose : a.pose_val.m, x, y, org, dir, cam_dir);
+  float4 v = make_float4(0.f, 0.f, 0.f, 0.f), n = v;
+  if ((__float_as_uint(cd.x) | __float_as_uint(cd.y) | __float_as_uint(cd.z)) != 0u) {
+    const float3 vtx = kf_add(org, kf_scale(dir, __uint_as_float((unsigned)a.ta[i])));
+    v = make_float4(vtx.x, vtx.y, vtx.z, 1.0f);
+    n = make_float4(cd.x, cd.y, cd.z, 0.f);
+  }
+  if (a.v) a.v[i] = v;
+  if (a.n) a.n[i] = n;
+  a.img[i] = kf_view_pixel<MODE>(v, n, col, org);
+}
+extern "C" int kf_view_from_rays(kf_ctx* c, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, const uint64_t* dev_ta_min,
+                                 const float* dev_cand, uint32_t words, float* dev_v, float* dev_n) {
+  if (!c || !dev_ta_min || !dev_cand) return KF_ERR_ARG;
+  if (mode != KF_VIEW_NORMALS && mode != KF_VIEW_SHADED && mode != KF_VIEW_COLOR) return KF_ERR_ARG;
+  if (!view_cam_ok(view_cam)) return KF_ERR_ARG;
+  if ((words != 3 && words != 4) || (mode == KF_VIEW_COLOR && words != 4)) return KF_ERR_ARG;
+  ViewRaysArgs a;
+  { const int st = kf_view_reserve(c, view_cam->cols, view_cam->rows, &a.img); if (st) return st; }
+  a.ta = (const unsigned long long*)dev_ta_min; a.cand = dev_cand; a.v = (float4*)dev_v; a.n = (float4*)dev_n;
+  a.cam = kf_to_cam(view_cam);
+  kf_pose_arg(c, pose, a.pose, a.pose_val);
+  const dim3 grid(kf_div_up(a.cam.cols * a.cam.rows, 256)), block(256);
+  if (mode == KF_VIEW_COLOR) hipLaunchKernelGGL((k_view_from_rays<KF_VIEW_COLOR, 4>), grid, block, 0, c->stream, a);
+  else if (mode == KF_VIEW_NORMALS && words == 3) hipLaunchKernelGGL((k_view_from_rays<KF_VIEW_NORMALS, 3>), grid, block, 0, c->stream, a);
+  else if (mode == KF_VIEW_NORMALS) hipLaunchKernelGGL((k_view_from_rays<KF_VIEW_NORMALS, 4>), grid, block, 0, c->stream, a);
+  else if (words == 3) hipLaunchKernelGGL((k_view_from_rays<KF_VIEW_SHADED, 3>), grid, block, 0, c->stream, a);
+  else hipLaunchKernelGGL((k_view_from_rays<KF_VIEW_SHADED, 4>), grid, block, 0, c->stream, a);
+  return (int)hipGetLastError();
 }
 
 extern "C" int kf_set_model_maps_device(kf_ctx* c, const float* dev_v, const float* dev_n) {

@@ -27,6 +27,7 @@ SYMBOLS = [
     "kf_group_triangle_count", "kf_group_read_triangles", "kf_group_merge_timing", "kf_group_read_merge_ms", "kf_group_synchronize",
     "kf_group_stream",
     "kf_group_create_color", "kf_group_validate_color", "kf_group_frame_color", "kf_group_frame_members_color",
+    "kf_group_view_validate", "kf_group_render_view", "kf_group_view_size", "kf_group_view_device", "kf_group_read_view",
 ]
 
 
@@ -48,6 +49,7 @@ def load():
         _lib = C.CDLL(LIB_PATH)
         _lib.kf_group_error_string.restype = C.c_char_p
         _lib.kf_group_stream.restype = C.c_void_p
+        _lib.kf_group_view_device.restype = C.c_void_p
     return _lib
 
 
@@ -104,6 +106,11 @@ def validate_color_status(cfg, params, backend, cuts, devices=None, halo=0, uid=
                                           backend, len(cuts) - 1, cuts_a, devs_a, halo, uid_a, rank, world)
 
 
+def view_validate_status(color_group, mode, cam):
+    """kf_group_view_validate: the refusals of kf_group_render_view alone (no HIP call); cam: lib.camera or None"""
+    return load().kf_group_view_validate(int(bool(color_group)), int(mode), C.byref(cam) if cam is not None else None)
+
+
 def create_status(cfg, params, backend, cuts, devices=None, halo=0, uid=None, rank=0, world=1):
     """kf_group_create's status alone (the group, if made, is destroyed at once): the validation tests"""
     lib = load()
@@ -157,6 +164,23 @@ class Group:
             v = K.Context.borrow(m, kcam, res, size, levels)
             v.owned = (self.cuts[i], self.cuts[i + 1])
             self._members.append(v)
+
+    @classmethod
+    def borrow(cls, handle, kcam, res, size, levels=3):
+        """Wrap a kf_group owned by someone else (HybKinectfuSlabs: hkf_slabs_group): same methods, close() leaves it alone"""
+        self = cls.__new__(cls)
+        self.lib = load()
+        self.cam, self.res, self.size, self.levels = kcam, int(res), float(size), int(levels)
+        self.h = handle if isinstance(handle, C.c_void_p) else C.c_void_p(handle)
+        self.borrowed = True
+        n, hl = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_group_members(self.h, C.byref(n), C.byref(hl)), "kf_group_members")
+        self.n, self.halo, self._members = n.value, hl.value, []
+        for i in range(self.n):
+            m = C.c_void_p()
+            _chk(self.lib.kf_group_member(self.h, i, C.byref(m)), "kf_group_member")
+            self._members.append(K.Context.borrow(m, kcam, res, size, levels))
+        return self
 
     @classmethod
     def local(cls, kcam, res, size, cuts, device=0, **kw):
@@ -224,6 +248,31 @@ class Group:
             _chk(self.lib.kf_group_read_triangles(self.h, out.ctypes.data_as(C.c_void_p), 0, n.value), "kf_group_read_triangles")
         return out
 
+    # ---- merged views ----
+    def render_view(self, mode, pose, cam, near, far, dev_v=None, dev_n=None):
+        """the whole volume from `cam` (lib.camera, any size) and `pose` (None: the device-resident pose) into member 0's BGRA view image; the
+        group's own increment; dev_v / dev_n: optional device addresses of float4 maps on member 0's device.  Asynchronous; a bystander to frames"""
+        tp = C.byref(K.Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_group_render_view(self.h, int(mode), tp, C.byref(cam) if cam is not None else None, C.c_float(near), C.c_float(far),
+                                           C.c_void_p(dev_v), C.c_void_p(dev_n)), "kf_group_render_view")
+
+    def view_size(self):
+        """(cols, rows) of the last view"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_group_view_size(self.h, C.byref(a), C.byref(b)), "kf_group_view_size")
+        return a.value, b.value
+
+    def view_device(self):
+        """device address of the last view's image on member 0's device, valid in stream order; None before a view"""
+        return self.lib.kf_group_view_device(self.h)
+
+    def read_view(self):
+        """the last view as a (rows, cols, 4) uint8 array (b, g, r, a); blocking"""
+        cols, rows = self.view_size()
+        out = np.empty((rows, cols, 4), np.uint8)
+        _chk(self.lib.kf_group_read_view(self.h, out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes)), "kf_group_read_view")
+        return out
+
     def merge_timing(self, on=True):
         _chk(self.lib.kf_group_merge_timing(self.h, int(bool(on))), "kf_group_merge_timing")
 
@@ -243,7 +292,8 @@ class Group:
         if self.h:
             for v in self._members:
                 v.h = None
-            self.lib.kf_group_destroy(self.h)
+            if not getattr(self, "borrowed", False):
+                self.lib.kf_group_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -97,6 +97,18 @@ bool HybKinectfuSlabs::viewModelMaps(int mode, std::vector<uint8_t>& bgra) {
   return check(kf_read_view(ctx, bgra.data(), bgra.size()));
 }
 
+bool HybKinectfuSlabs::renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra) {
+  if (!_inited) return false;
+  const AppParams* p = AppParams::instance();
+  kf_mat44 kp; const kf_mat44* tp = nullptr;
+  if (pose) { memcpy(kp.m, pose->entries, sizeof(kp.m)); tp = &kp; }
+  if (!check(kf_group_render_view(_group, mode, tp, &cam, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, nullptr, nullptr))) return false;
+  uint32_t cols = 0, rows = 0;
+  if (!check(kf_group_view_size(_group, &cols, &rows))) return false;
+  bgra.resize((size_t)cols * rows * 4);
+  return check(kf_group_read_view(_group, bgra.data(), bgra.size()));
+}
+
 void HybKinectfuSlabs::generateMesh() {                        // MeshGeneratorMarchingcube::generateMesh, src/MeshGeneratorMarchingcube.cpp:23-29
   if (!_inited) return;
   const AppParams* p = AppParams::instance();

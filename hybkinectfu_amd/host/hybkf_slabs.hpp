@@ -40,8 +40,12 @@ public:
   unsigned triangleCount();
   const MeshData& mesh() const { return _mesh.mesh(); }
   // HybKinectfu::viewModelMaps through member 0: after a frame's merge every member holds the whole volume's model maps.  cols * rows * 4 bytes
-  // (b, g, r, a); mode = KF_VIEW_*, KF_VIEW_COLOR on a colour group only.  Blocking.  (No renderView: a member sees only its own layers.)
+  // (b, g, r, a); mode = KF_VIEW_*, KF_VIEW_COLOR on a colour group only.  Blocking.
   bool viewModelMaps(int mode, std::vector<uint8_t>& bgra);
+  // HybKinectfu::renderView over the group (kf_group_render_view: every member marches the view's rays through its own layers, the merge gives the
+  // whole volume's picture): any camera, from `pose` (nullptr: the current camera pose, device-resident on every member); the increment and the
+  // planes come from AppParams, as processNewFrame uses them; it leaves tracking state alone.  Blocking (the read-back).
+  bool renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra);
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

@@ -96,5 +96,16 @@ int hkf_slabs_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
   memcpy(out, img.data(), img.size());
   return 0;
 }
+// HybKinectfuSlabs::renderView, with hkf_app_render_view's arguments and return values (pose16 NULL: the current camera pose)
+int hkf_slabs_render_view(int mode, const float* pose16, unsigned cols, unsigned rows, float cx, float cy, float fx, float fy, uint8_t* out, size_t out_cap) {
+  if (!g_slabs) return -1;
+  Mat44 m; if (pose16) memcpy(m.entries, pose16, 64);
+  const kf_camera_params cam = {cols, rows, cx, cy, fx, fy};
+  std::vector<uint8_t> img;
+  if (!g_slabs->renderView(pose16 ? &m : nullptr, cam, mode, img)) return -2;
+  if (!out || out_cap < img.size()) return -3;
+  memcpy(out, img.data(), img.size());
+  return 0;
+}
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

@@ -103,6 +103,71 @@ class App:
         self.h.hkf_app_shutdown()
 
 
+SLABS_LIB = os.path.join(K.PKG_DIR, "libhybkf_slabs.so")
+_s = None
+
+
+def load_slabs():
+    global _s
+    if _s is None:
+        load()
+        if not os.path.exists(SLABS_LIB):
+            raise RuntimeError("libhybkf_slabs.so is missing: run __graft_entry__.build()")
+        _s = C.CDLL(SLABS_LIB)
+        _s.hkf_slabs_group.restype = C.c_void_p
+    return _s
+
+
+class SlabsApp:
+    """HybKinectfuSlabs through hkf_slabs_*: the application over a slab group (one per process).  backend / cuts: hybkf_group.h"""
+
+    def __init__(self, res, size, cam, cuts, backend=0, max_triangles=0, sdf_trunc=0.0, integrate_dist=0.0, trunc_max=0.0, device=0, halo=0):
+        self.h = load_slabs()
+        cuts_a = (C.c_uint32 * len(cuts))(*cuts)
+        st = self.h.hkf_slabs_init(res, C.c_float(size), cam[0], cam[1], C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
+                                   max_triangles, C.c_float(sdf_trunc), C.c_float(integrate_dist), C.c_float(trunc_max), device, backend,
+                                   len(cuts) - 1, cuts_a, None, halo)
+        if st:
+            raise K.KfError("hkf_slabs_init failed: %d" % st)
+        self.cam = cam
+
+    def process_frame(self, mm, frame_id):
+        mm = np.ascontiguousarray(mm, np.uint16)
+        r = self.h.hkf_slabs_process_frame(mm.ctypes.data_as(C.c_void_p), 0, frame_id)
+        if r < 0:
+            raise K.KfError("processNewFrame failed: %d" % r)
+        return bool(r)
+
+    def pose(self):
+        out = np.zeros(16, np.float32)
+        tracked = self.h.hkf_slabs_get_pose(out.ctypes.data_as(C.c_void_p))
+        return bool(tracked), out.reshape(4, 4)
+
+    def group_handle(self):
+        return C.c_void_p(self.h.hkf_slabs_group())
+
+    def render_view(self, mode, pose, cam):
+        """HybKinectfuSlabs::renderView: App.render_view over the group -- the whole volume's picture from any camera"""
+        out = np.empty((cam[1], cam[0], 4), np.uint8)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16) if pose is not None else None
+        r = self.h.hkf_slabs_render_view(int(mode), p.ctypes.data_as(C.c_void_p) if p is not None else None, int(cam[0]), int(cam[1]),
+                                         C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
+                                         out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("renderView failed: %d (%d)" % (r, self.h.hkf_slabs_last_error()))
+        return out
+
+    def view_model_maps(self, mode):
+        out = np.empty((self.cam[1], self.cam[0], 4), np.uint8)
+        r = self.h.hkf_slabs_view_model_maps(int(mode), out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("viewModelMaps failed: %d" % r)
+        return out
+
+    def close(self):
+        self.h.hkf_slabs_shutdown()
+
+
 # ---- GPU-free helpers of the dataset / trajectory code -------------------------------------------------------------------------
 def dataset_read(directory, cols, rows, n, with_color=False):
     h = load()

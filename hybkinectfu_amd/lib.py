@@ -114,6 +114,7 @@ SYMBOLS = [
     "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
     "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
     "kf_render_view", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
+    "kf_view_slab_cross", "kf_view_slab_normals", "kf_view_from_rays",
 ]
 
 
@@ -414,6 +415,27 @@ class Context:
         out = np.empty((rows, cols, 4), np.uint8)
         _chk(self.lib.kf_read_view(self.h, _p(out), C.c_size_t(out.nbytes)), "kf_read_view")
         return out
+
+    # the per-member steps of a merged view over z-slabs (group.Group.render_view runs them with the two all-reduces between)
+    def view_slab_cross(self, color, pose, cam, inc, near, far, dev_ta, dev_ta_own, dev_spec):
+        """raycast_slab_cross_spec (color: ..._spec_color, 4 words per pixel) for `cam`, any size; a bystander like render_view (kf_view_slab_cross)"""
+        rp = RaycastParams(inc)
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_view_slab_cross(self.h, int(bool(color)), tp, C.byref(cam), C.byref(rp), C.c_float(near), C.c_float(far), C.c_void_p(dev_ta),
+                                         C.c_void_p(dev_ta_own), C.c_void_p(dev_spec)), "kf_view_slab_cross")
+
+    def view_slab_normals(self, color, pose, cam, inc, near, far, dev_ta_min, dev_ta_own, dev_spec, dev_cand):
+        """slab_ray_normals_spec / _color for `cam`; dev_ta_own and dev_spec both None: every owned vertex is evaluated (kf_view_slab_normals)"""
+        rp = RaycastParams(inc)
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_view_slab_normals(self.h, int(bool(color)), tp, C.byref(cam), C.byref(rp), C.c_float(near), C.c_float(far), C.c_void_p(dev_ta_min),
+                                           C.c_void_p(dev_ta_own), C.c_void_p(dev_spec), C.c_void_p(dev_cand)), "kf_view_slab_normals")
+
+    def view_from_rays(self, mode, pose, cam, dev_ta_min, dev_cand, words=3, dev_v=None, dev_n=None):
+        """the merged crossing words and candidates (`words` per pixel) into the context's BGRA view image, optionally the float4 maps (kf_view_from_rays)"""
+        tp = C.byref(Mat44.of(pose)) if pose is not None else None
+        _chk(self.lib.kf_view_from_rays(self.h, int(mode), tp, C.byref(cam), C.c_void_p(dev_ta_min), C.c_void_p(dev_cand), int(words),
+                                        C.c_void_p(dev_v), C.c_void_p(dev_n)), "kf_view_from_rays")
 
     def raycast_form(self):
         """what the last raycast launch took (kf_get_raycast_form): a dict of the kf_raycast_form fields"""

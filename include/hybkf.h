@@ -359,7 +359,7 @@ int kf_weld_release(kf_ctx* ctx);
  *   caller-owned float4 maps of view_cam's size that receive what kf_raycast_volume would have written; either may be NULL.  It is a bystander to
  *   tracking: the model maps, KF_MAP_RAYCAST_RGB, kf_get_raycast_form's record, a pending kf_prefetch_frame and the stage timers are left as they
  *   are.  KF_ERR_ARG: bad mode, bad camera, NULL context or increment.  KF_ERR_STATE: a z-slab context that does not own the whole volume (it sees
- *   only its own layers).
+ *   only its own layers: the free viewpoint over z-slabs is the merged view below, which kf_group_render_view of hybkf_group.h runs).
  * kf_view_model_maps: the tracking camera's view without a march -- the same bytes from level 0 of the context's CURRENT model maps,
  *   KF_MAP_RAYCAST_RGB and the device-resident pose.  Allowed on z-slab contexts: after kf_set_model_maps_rays every member holds the merged maps.
  * kf_view_size: the size of the last view (KF_ERR_STATE before one).  kf_view_device: the image in HBM, valid in stream order until the next view
@@ -371,6 +371,28 @@ int kf_view_model_maps(kf_ctx* ctx, int mode);
 int kf_view_size(kf_ctx* ctx, uint32_t* cols, uint32_t* rows);
 const uint8_t* kf_view_device(kf_ctx* ctx);
 int kf_read_view(kf_ctx* ctx, uint8_t* dst, size_t dst_bytes);
+/* A MERGED VIEW over z-slabs: the ray-form merge (kf_raycast_volume_slab_cross_spec ... kf_set_model_maps_rays above) for the CALLER's camera, ending
+ * in display bytes.  The three per-member steps; the caller runs the two all-reduces between them (kf_group_render_view does all five).  All take
+ * view_cam with kf_render_view's limits (1 .. 4096 each way, any size whatever the context's), `pose` (NULL: the device-resident pose), are asynchronous
+ * on the context's stream, are accepted on z-slab contexts and on a whole-volume context (which owns every layer), and are bystanders to tracking
+ * exactly as kf_render_view is: the model maps, KF_MAP_RAYCAST_RGB, kf_get_raycast_form's record, a pending kf_prefetch_frame, the stage timers and
+ * the work counters are left as they are.  Buffers are caller-owned device memory of view_cam's pixel count.
+ *   kf_view_slab_cross    the march of kf_raycast_volume_slab_cross_spec (color != 0: of ..._spec_color, dev_spec 4 words per pixel) for view_cam: the
+ *                         same words, second copy and speculation, bit for bit, whenever view_cam is the context's camera.  KF_ERR_ARG: a halo thinner
+ *                         than ceil(ray_increment / voxel) + 2 layers, a bad camera, a NULL buffer.  KF_ERR_STATE: color without a colour plane.
+ *   kf_view_slab_normals  kf_slab_ray_normals_spec / kf_slab_ray_normals_color (color != 0: dev_spec, dev_cand 4 words per pixel) for view_cam.
+ *                         dev_ta_own and dev_spec may both be NULL: then every owned vertex is evaluated.
+ *   kf_view_from_rays     vertices from alpha, normals and (words = 4) colours from the summed candidates, through the pixel function above into the
+ *                         context's view image: kf_view_size / kf_view_device / kf_read_view follow as after any other view.  The eye is the pose's
+ *                         translation.  The colour bytes are kept whether or not a normal was found; byte 3 is 255 only where the candidate normal has
+ *                         a set bit.  dev_v / dev_n: optional float4 maps that receive what kf_raycast_volume would have written on the whole volume.
+ *                         Every pixel of the image and of the maps is written.  words: 3 or 4; KF_VIEW_COLOR needs 4 (KF_ERR_ARG otherwise). */
+int kf_view_slab_cross(kf_ctx* ctx, int color, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* raycast_params,
+                       float near_plane, float far_plane, uint64_t* dev_ta, uint64_t* dev_ta_own, float* dev_spec);
+int kf_view_slab_normals(kf_ctx* ctx, int color, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* raycast_params,
+                         float near_plane, float far_plane, const uint64_t* dev_ta_min, const uint64_t* dev_ta_own, const float* dev_spec, float* dev_cand);
+int kf_view_from_rays(kf_ctx* ctx, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, const uint64_t* dev_ta_min, const float* dev_cand,
+                      uint32_t words, float* dev_v, float* dev_n);
 
 /* CudaMap2D::clone(CPU) / copyDataFrom on the singleton's maps (debug + parity; blocking) */
 int kf_download_map(kf_ctx* ctx, int map_id, uint32_t level, void* dst, size_t dst_bytes);

@@ -116,9 +116,31 @@ int kf_group_frame_members_color(kf_group* g, const uint16_t* const* dev_mm, con
 int kf_group_track_result(kf_group* g, kf_track_result* out, int check_lockstep);
 /* borrowed: for read-backs (maps, volume, stats).  The group owns the context and its stream; do not destroy it or change its stream.
  * Viewer frames (hybkf.h): after step 9 every member holds the merged model maps, so kf_view_model_maps on any member -- member 0 by
- * convention -- gives the whole volume's picture from the tracking camera.  A FREE viewpoint over a group is out of scope: kf_render_view
- * refuses a member that does not own the whole volume (KF_ERR_STATE), because it sees only its own layers. */
+ * convention -- gives the whole volume's picture from the tracking camera.  A FREE viewpoint over a group is kf_group_render_view below:
+ * kf_render_view itself refuses a member that does not own the whole volume (KF_ERR_STATE), because it sees only its own layers. */
 int kf_group_member(kf_group* g, uint32_t i, kf_ctx** out);
+/* A merged view: the whole volume from any camera and pose, 4 display bytes per pixel (hybkf.h: KF_VIEW_*, the same bytes as kf_render_view on a
+ * whole-volume context).  kf_group_render_view enqueues, on the members' streams (asynchronous):
+ *   1. kf_view_slab_cross on every member   2. MIN all-reduce of the crossing words   3. kf_view_slab_normals on every member
+ *   4. integer SUM all-reduce of the candidates   5. kf_view_from_rays on member 0 -- the first member this process holds
+ * with the group's own ray increment (so the halo the group was created with suffices) and the caller's planes.  The candidates have 4 words per
+ * pixel only for KF_VIEW_COLOR: the other two modes run the colourless forms on a colour group too.  pose NULL: the device-resident pose (the
+ * same bits on every member); a given pose is used as it is by every member.  dev_v / dev_n: optional float4 maps of view_cam's size on member
+ * 0's device (kf_view_from_rays).  KF_GROUP_RCCL_RANK: the call is collective -- every rank issues it with the same arguments, and only those
+ * are checked.  The view's buffers are the group's own (a view never touches a frame's), grow on demand and are freed by kf_group_destroy.
+ * It is a bystander to kf_group_frame*: poses, launch forms, kf_get_raycast_form's records, model maps and volumes are the same with and
+ * without views between frames, and the merge timers do not count it.
+ * kf_group_view_validate: the refusals, without any HIP call -- KF_GROUP_ERR_ARG for a mode outside KF_VIEW_* or a camera outside kf_render_view's
+ * limits, KF_GROUP_ERR_STATE for KF_VIEW_COLOR with color_group == 0.  After such a refusal nothing is enqueued, no collective is issued and the
+ * group stays usable; a member call or a collective that fails mid-sequence puts the group into the failed state, as in a frame.
+ * kf_group_view_size / kf_group_view_device / kf_group_read_view (blocking): member 0's kf_view_size / kf_view_device / kf_read_view after a
+ * merged view; KF_GROUP_ERR_STATE (NULL) before one. */
+int kf_group_view_validate(int color_group, int mode, const kf_camera_params* view_cam);
+int kf_group_render_view(kf_group* g, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, float near_plane, float far_plane,
+                         float* dev_v, float* dev_n);
+int kf_group_view_size(kf_group* g, uint32_t* cols, uint32_t* rows);
+const uint8_t* kf_group_view_device(kf_group* g);
+int kf_group_read_view(kf_group* g, uint8_t* dst, size_t dst_bytes);
 /* kf_marching_cubes on every member (each extracts its own layers); a colour group extracts with colour */
 int kf_group_marching_cubes(kf_group* g, float threshold);
 int kf_group_triangle_count(kf_group* g, uint32_t* count);                                     /* sum over the members, blocking */

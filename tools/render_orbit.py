@@ -1,12 +1,15 @@
 #!/usr/bin/env python3
 """Pictures of a scanned model from an orbit of viewpoints: fuse Scene S, then render N poses on a circle around the volume's centre with
 kf_render_view at a chosen size and mode, and write one picture per pose into a directory.
-  usage: tools/render_orbit.py OUT_DIR [--n 12] [--size 640x480] [--mode normals|shaded|color] [--res 256] [--volume 3.0] [--frames 12]
+  usage: tools/render_orbit.py OUT_DIR [--n 12] [--size 640x480] [--mode normals|shaded|color] [--res 256] [--volume 3.0] [--frames 12] [--slabs N]
+--slabs N: the same orbit through a LOCAL slab group of N members (kf_group_render_view: every member marches its own layers, the merge gives
+the whole volume's picture -- the same bytes).
 PNG through PIL where it is installed, binary PPM otherwise (no hit: black)."""
 import argparse, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from hybkinectfu_amd import lib as K, scene as S
+from hybkinectfu_amd import group as G, pipeline as PL
 
 ap = argparse.ArgumentParser()
 ap.add_argument("out_dir")
@@ -16,6 +19,7 @@ ap.add_argument("--mode", default="shaded", choices=("normals", "shaded", "color
 ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--volume", type=float, default=3.0)
 ap.add_argument("--frames", type=int, default=12)
+ap.add_argument("--slabs", type=int, default=0, help="render through a LOCAL slab group of N members")
 args = ap.parse_args()
 cols, rows = (int(v) for v in args.size.lower().split("x"))
 mode = dict(normals=K.VIEW_NORMALS, shaded=K.VIEW_SHADED, color=K.VIEW_COLOR)[args.mode]
@@ -23,16 +27,34 @@ P, cam, size, res = S.STOCK, S.vga_camera(), args.volume, args.res
 trunc = max(P["integrate_sdf_trunc"], 5 * size / res)
 color = mode == K.VIEW_COLOR
 
-ctx = K.Context(K.camera(*cam), res, size, P["volume_max_weight"], levels=3, has_color=color)
-for k in range(args.frames):
-    pose = S.trajectory_pose(k, size).astype(np.float32)
-    mm = S.render_depth_mm(pose, cam, size)
-    ctx.upload_depth_mm(mm)
-    if color:                                                   # a picture to fuse: the depth as a colour ramp
-        g = (mm // 8 % 256).astype(np.uint8)
-        ctx.upload_rgb(np.stack([g, 255 - g, (g // 2 + 64).astype(np.uint8)], axis=-1))
-    ctx.preprocess(P["depth_trunc_min"], P["depth_trunc_max"], P["filter_sigma_pixel"], P["filter_sigma_depth"])
-    ctx.integrate(pose, trunc, P["integrate_depth_trunc"], has_color=color, angle_weight=color)
+
+def ramp(mm):                                                   # a picture to fuse: the depth as a colour ramp
+    g = (mm // 8 % 256).astype(np.uint8)
+    return np.stack([g, 255 - g, (g // 2 + 64).astype(np.uint8)], axis=-1)
+
+
+group = ctx = None
+if args.slabs:
+    # the group tracks its frames itself (the same trajectory, from HybKinectfu::init's pose)
+    params = G.stock_params()
+    params.integrate = K.IntegrateParams(trunc, P["integrate_depth_trunc"])
+    params.raycast = K.RaycastParams(P["raycast_increment_factor"] * trunc)
+    group = G.Group.local(K.camera(*cam), res, size, [0] + [r[1] for r in PL.slab_ranges(res, args.slabs)], params=params, has_color=color)
+    group.set_pose(S.pose0(size))
+    for k in range(args.frames):
+        mm = S.render_depth_mm(S.trajectory_pose(k, size), cam, size)
+        group.frame(mm, k, rgb=ramp(mm) if color else None)
+    group.sync()
+else:
+    ctx = K.Context(K.camera(*cam), res, size, P["volume_max_weight"], levels=3, has_color=color)
+    for k in range(args.frames):
+        pose = S.trajectory_pose(k, size).astype(np.float32)
+        mm = S.render_depth_mm(pose, cam, size)
+        ctx.upload_depth_mm(mm)
+        if color:
+            ctx.upload_rgb(ramp(mm))
+        ctx.preprocess(P["depth_trunc_min"], P["depth_trunc_max"], P["filter_sigma_pixel"], P["filter_sigma_depth"])
+        ctx.integrate(pose, trunc, P["integrate_depth_trunc"], has_color=color, angle_weight=color)
 
 
 def look(eye, target):
@@ -66,7 +88,11 @@ centre = np.array([0.5 * size, 0.5 * size, 0.5 * size])
 for i in range(args.n):
     a = math.radians(-60.0 + 120.0 * i / max(args.n - 1, 1))
     eye = centre + 0.75 * size * np.array([math.sin(a), -0.15, -math.cos(a)])
-    ctx.render_view(mode, look(eye, centre), view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
-    img = ctx.read_view()
+    if group:
+        group.render_view(mode, look(eye, centre), view_cam, 0.05, 4.0 * size)
+        img = group.read_view()
+    else:
+        ctx.render_view(mode, look(eye, centre), view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
+        img = ctx.read_view()
     print("%s  hits %d" % (save(os.path.join(args.out_dir, "orbit_%03d" % i), img), int((img[..., 3] == 255).sum())))
-ctx.close()
+(group or ctx).close()
