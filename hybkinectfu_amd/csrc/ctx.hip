@@ -253,6 +253,7 @@ extern "C" int kf_reset_volume(kf_ctx* c) {
   KF_CHECK(hipMemsetAsync(c->counters, 0, sizeof(KfCounters), c->stream));
   ++c->vol_flags_serial; c->pend_live = 0;
   c->wgt0_base = 0; c->wgt0_valid = 1;                       // nothing observed; the shards were zeroed with the counters
+  c->origin_vox[0] = c->origin_vox[1] = c->origin_vox[2] = 0; // the window is back on the first cube (kf_shift_volume)
   return 0;
 }
 

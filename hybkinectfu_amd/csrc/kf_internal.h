@@ -240,6 +240,9 @@ struct kf_ctx {
   double ev_ms[8]; unsigned ev_count[8];
   // viewer frames (view.hip; kf_render_view, kf_view_model_maps): the context-owned BGRA image of the last view, grown on demand
   unsigned* view_img; size_t view_cap_px; uint32_t view_cols, view_rows;   // view_cols == 0: no view yet
+  // the moving volume (shift.hip; kf_shift_volume, kf_volume_origin): voxel (0, 0, 0) of the window in the voxels of the first cube -- the sum of all shifts
+  // since kf_create / kf_reset_volume.  Host bookkeeping only: no kernel reads it.
+  int32_t origin_vox[3];
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,

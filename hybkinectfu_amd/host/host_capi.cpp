@@ -115,6 +115,11 @@ int hkf_app_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
   if (!g_app->viewModelMaps(mode, img)) return -2;
   return copy_view(img, out, out_cap);
 }
+// the moving volume: HybKinectfu::shiftVolume / volumeOrigin, and AppParams::_volume_params.fRecentreDist (call AFTER hkf_app_init, which restores the
+// defaults; 0 = off).  hkf_app_shift_volume: 1 shifted, 0 refused, -1 without an application
+int hkf_app_shift_volume(int dx, int dy, int dz) { if (!g_app) return -1; return g_app->shiftVolume(dx, dy, dz) ? 1 : 0; }
+int hkf_app_volume_origin(int out3[3]) { if (!g_app) return -1; g_app->volumeOrigin(out3); return 0; }
+int hkf_app_set_recentre(float dist) { if (!g_app) return -1; AppParams::instance()->_volume_params.fRecentreDist = dist; return 0; }
 int hkf_app_generate_mesh() { if (!g_mesh) return -1; g_mesh->generateMesh(); return (int)g_mesh->triangleCount(); }
 int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
   if (!g_mesh) return -1;

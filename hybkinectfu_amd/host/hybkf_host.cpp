@@ -18,7 +18,7 @@ void AppParams::setDefaults(unsigned res, float size) {
   _depth_prepocess_params = {4.0f, 0.3f, 0.03f, 2.0f};                  // max, min, sigma depth, sigma pixel
   _icp_params = {3, 0.1f, 0.1f, 0.3f, 0.3f};
   _sdf_tracker_params = {6, 0.3f, 0.3f};
-  _volume_params = {res, size, 128.0f};
+  _volume_params = {res, size, 128.0f, 0.0f};
   _integrate_params = {0.05f, 2.0f};
   _raycast_params.fRayIncrement = 0.7f * _integrate_params.fSdfTruncation;  // AppParamsProducer.cpp:113-117
   _marchingcube_params.uMaxTriangles = 6500000;
@@ -347,7 +347,8 @@ bool HybKinectfu::processNewFrame(const DepthFrameData& depth_frame, const Color
     if (dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, nullptr, &rp, &p->_depth_camera_params,
                                     p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc))) return false;
     _last_tracked = _camera_pose_finder->waitPose(); _pending = false;
-    if (_last_tracked && _camera_pose_recorder) _camera_pose_recorder->recordCameraPose(_camera_pose_finder->getCameraPose(), depth_frame.timeStamp());
+    if (_last_tracked && _camera_pose_recorder) _camera_pose_recorder->recordCameraPose(worldPose(_camera_pose_finder->getCameraPose()), depth_frame.timeStamp());
+    if (_last_tracked && p->_volume_params.fRecentreDist > 0.f) return recentre();
     return true;
   }
   bool camera_tracking_success = _camera_pose_finder->findCameraPose(depth_frame, rgb_frame);
@@ -355,7 +356,7 @@ bool HybKinectfu::processNewFrame(const DepthFrameData& depth_frame, const Color
   Mat44 cur_camera_pose = _camera_pose_finder->getCameraPose();
   kf_mat44 kp = to_kf(cur_camera_pose);
   if (camera_tracking_success) {
-    if (_camera_pose_recorder) _camera_pose_recorder->recordCameraPose(cur_camera_pose, depth_frame.timeStamp());     // :129-132
+    if (_camera_pose_recorder) _camera_pose_recorder->recordCameraPose(worldPose(cur_camera_pose), depth_frame.timeStamp());     // :129-132
     kf_integrate_params ip = {p->_integrate_params.fSdfTruncation, p->_integrate_params.fMaxIntegrateDist};
     if (dm->check(kf_integrate_volume(ctx, p->_switch_params.useRGBData, p->_switch_params.colorAngleWeight, &kp, &ip,
                                       &p->_depth_camera_params, &p->_rgb_camera_params))) return false;
@@ -363,7 +364,52 @@ bool HybKinectfu::processNewFrame(const DepthFrameData& depth_frame, const Color
   kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
   if (dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, &kp, &rp, &p->_depth_camera_params,
                                   p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc))) return false;
+  if (camera_tracking_success && p->_volume_params.fRecentreDist > 0.f) return recentre();
   return true;
+}
+// ---- the moving volume ------------------------------------------------------------------------------------------------------------------
+static float volume_cell() {                                   // KfVolume::cell: the fp32 quotient (tsdfVolume.h:44-46)
+  const AppParams* p = AppParams::instance();
+  return p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+}
+void HybKinectfu::volumeOrigin(int out[3]) {
+  int32_t o[3] = {0, 0, 0};
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (dm->ctx()) dm->check(kf_volume_origin(dm->ctx(), o));
+  for (int k = 0; k < 3; ++k) out[k] = (int)o[k];
+}
+Mat44 HybKinectfu::worldPose(const Mat44& pose) {
+  int o[3]; volumeOrigin(o);
+  const int32_t o32[3] = {o[0], o[1], o[2]};
+  Mat44 w = pose;
+  hkf_world_pose(w.entries, o32, volume_cell());
+  return w;
+}
+bool HybKinectfu::shiftVolume(int dx, int dy, int dz) {
+  if (!_inited) return false;
+  const AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (dm->check(kf_shift_volume(dm->ctx(), dx, dy, dz))) return false;
+  if (dx == 0 && dy == 0 && dz == 0) return true;
+  const float cell = volume_cell();
+  Mat44 moved = _camera_pose_finder->getCameraPose();           // the same expression as k_shift_pose
+  moved.entries[3] = moved.entries[3] - (float)dx * cell;
+  moved.entries[7] = moved.entries[7] - (float)dy * cell;
+  moved.entries[11] = moved.entries[11] - (float)dz * cell;
+  const bool resident = _camera_pose_finder->deviceResident();
+  if (resident) _camera_pose_finder->adoptCameraPose(moved); else _camera_pose_finder->setCameraPose(moved);
+  const kf_mat44 kp = to_kf(moved);
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
+  return 0 == dm->check(kf_raycast_volume(dm->ctx(), p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
+                                          p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
+}
+bool HybKinectfu::recentre() {
+  const AppParams* p = AppParams::instance();
+  int32_t d[3];
+  hkf_recentre_shift(_camera_pose_finder->getCameraPose().entries, p->_volume_params.fVolumeMeterSize, p->_volume_params.nResolution,
+                     p->_volume_params.fRecentreDist, d);
+  if (d[0] == 0 && d[1] == 0 && d[2] == 0) return true;
+  return shiftVolume(d[0], d[1], d[2]);
 }
 // what DataViewer shows, without the maps crossing to the host (HybKinectfu.cpp:145-158): 4 bytes per pixel come back
 static bool read_view(CudaDeviceDataMan* dm, std::vector<uint8_t>& bgra) {
@@ -587,6 +633,12 @@ bool MeshGeneratorMarchingcube::saveMesh(const std::string& filename) {   // :61
   if (!_device_weld || !weldOnDevice()) {
     if (!copyTrianglesToCPU()) return false;
     weldMesh();
+  }
+  {                                                              // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
+    int32_t o[3] = {0, 0, 0};
+    CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+    if (dm->ctx() && kf_volume_origin(dm->ctx(), o) == 0)
+      hkf_world_positions(_meshes.vertices.data(), _meshes.vertices.size() / 3, o, volume_cell());
   }
   // the reference returns 0 here even on success (:95); we report whether the file was written
   return _meshes.saveToFile(filename);

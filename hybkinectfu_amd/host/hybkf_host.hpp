@@ -18,7 +18,9 @@ struct SDFTrackerParams { unsigned maxIterNums; float fDistShake, fAngleShake; }
 typedef kf_camera_params CameraParams;                       // {cols, rows, cx, cy, fx, fy}, 24 bytes
 struct RayCasterParams { float fRayIncrement; };
 struct DepthPrepocessParams { float fMaxTrunc, fMinTrunc, fSigmaDepth, fSigmaPixel; };
-struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; };
+// fRecentreDist (not in the reference): the moving volume's policy.  0 (default): off, the cube stays where init put it.  > 0: after a tracked
+// processNewFrame whose focus point lies farther than this (metres, any axis) from the volume's centre, the window is shifted towards it by whole bricks
+struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; };
 struct MarchingcubeParams { unsigned uMaxTriangles; };
 struct IntegrateParams { float fSdfTruncation, fMaxIntegrateDist; };
 struct SwitchParams { bool recordRGBD, recordTrajectory, useRGBData, colorAngleWeight, useDatasetRGBD, useTrajFromFile, useSdfTracker; };
@@ -88,6 +90,8 @@ public:
   virtual bool findCameraPose(const DepthFrameData& depth_frame, const ColorFrameData& color_frame);
   Mat44 getCameraPose() const { return _pose; }
   void setCameraPose(const Mat44& transform);
+  // the host's copy only, for a pose the device already holds (HybKinectfu::shiftVolume: kf_shift_volume moved the device-resident pose itself)
+  void adoptCameraPose(const Mat44& transform) { _pose = transform; }
   // false (default): the Gauss-Newton loop runs on the device (kf_icp_track / kf_sdf_track), one read-back per frame;
   // true: the reference's own host loop -- one kernel wrapper + 27-float read-back + host 6x6 solve per iteration.
   void setHostLoop(bool on) { _host_loop = on; }
@@ -169,6 +173,17 @@ private:
   Mat44 _refer_transform;
 };
 
+// ---- the moving volume's host arithmetic (recentre.cpp; no reference counterpart, no device, C linkage: the CPU tests call them) -----------------
+extern "C" {
+// How far to shift for `pose` (row-major camera -> world in the window's coordinates): the focus point t + R (0, 0, size_m / 2) against the centre
+// (size_m / 2 each way).  If any component of (focus - centre) exceeds `dist` in magnitude, out[i] = trunc((focus - centre)[i] / (8 cell)) * 8 voxels
+// (truncation toward zero, cell = size_m / res), else zeros; dist <= 0 or a pose that is not finite gives zeros.  fp32, one rounding per operation.
+void hkf_recentre_shift(const float pose[16], float size_m, uint32_t res, float dist, int32_t out[3]);
+// volume coordinates -> world coordinates: + (float)origin_vox * cell on the pose's translation / on n xyz positions.  A zero origin leaves every bit.
+void hkf_world_pose(float pose[16], const int32_t origin_vox[3], float cell);
+void hkf_world_positions(float* xyz, size_t n, const int32_t origin_vox[3], float cell);
+}
+
 // ---- src/TrajectoryRecorder.{h,cpp}: TUM-format trajectory writer ---------------------------------------------------------------------------------
 class TrajectoryRecorder {
 public:
@@ -231,7 +246,18 @@ public:
   // tracking state alone.  viewModelMaps: the tracking camera's view from the current model maps, no march.  Blocking (the read-back).
   bool renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra);
   bool viewModelMaps(int mode, std::vector<uint8_t>& bgra);
+  // The moving volume (no reference counterpart).  shiftVolume: kf_shift_volume by (dx, dy, dz) voxels, multiples of 8, then the raycast with the
+  // moved pose and the stock parameters, so the model maps show the new window before the next frame is tracked.  A finder that keeps its pose on
+  // the host gets the translated pose through setCameraPose -- the same fp32 expression as on the device.  false: not initialised, or the shift
+  // was refused (a component that is no multiple of 8, a z-slab context).  volumeOrigin: the sum of all shifts, in voxels.
+  // With AppParams::_volume_params.fRecentreDist > 0 processNewFrame recentres by itself after a tracked frame (hkf_recentre_shift on the pose it
+  // has just waited for); enqueueFrame never does: it holds no host pose to decide on.  The recorded trajectory and saved meshes are in WORLD
+  // coordinates (volume coordinates + origin * cell); with a zero origin they are what they always were, byte for byte.
+  bool shiftVolume(int dx, int dy, int dz);
+  void volumeOrigin(int out[3]);
 private:
+  bool recentre();
+  Mat44 worldPose(const Mat44& pose);
   void copyFrameToGPU(const DepthFrameData& depth_frame, const ColorFrameData& color_frame);
   CameraPoseFinder* _camera_pose_finder;
   TrajectoryRecorder* _camera_pose_recorder = nullptr;       // switch recordTrajectory (HybKinectfu.cpp:47-50,129-132)

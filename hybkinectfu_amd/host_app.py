@@ -99,6 +99,26 @@ class App:
             raise K.KfError("viewModelMaps failed: %d" % r)
         return out
 
+    def shift_volume(self, dx, dy, dz):
+        """HybKinectfu::shiftVolume: the window moves by (dx, dy, dz) voxels (multiples of 8), the model maps are raycast anew; False: refused"""
+        r = self.h.hkf_app_shift_volume(int(dx), int(dy), int(dz))
+        if r < 0:
+            raise K.KfError("hkf_app_shift_volume: no application")
+        return bool(r)
+
+    def volume_origin(self):
+        """HybKinectfu::volumeOrigin: the sum of all shifts, in voxels"""
+        o = (C.c_int * 3)()
+        if self.h.hkf_app_volume_origin(o) != 0:
+            raise K.KfError("hkf_app_volume_origin: no application")
+        return tuple(int(x) for x in o)
+
+    def set_recentre(self, dist):
+        """AppParams::_volume_params.fRecentreDist: process_frame recentres the window after a tracked frame whose focus point lies farther
+        than `dist` metres from the volume's centre (0: off, the default)"""
+        if self.h.hkf_app_set_recentre(C.c_float(dist)) != 0:
+            raise K.KfError("hkf_app_set_recentre: no application")
+
     def close(self):
         self.h.hkf_app_shutdown()
 
@@ -262,3 +282,12 @@ def mesh_save(which, filename):
 
 def app_mesh():
     return _mesh_read(1)
+
+
+def recentre_shift(pose, size, res, dist):
+    """hkf_recentre_shift: the shift (voxels, multiples of 8) HybKinectfu::processNewFrame applies for `pose` with fRecentreDist = dist; GPU-free"""
+    h = load()
+    p = np.ascontiguousarray(pose, np.float32).reshape(16)
+    out = (C.c_int32 * 3)()
+    h.hkf_recentre_shift(p.ctypes.data_as(C.c_void_p), C.c_float(size), C.c_uint32(res), C.c_float(dist), out)
+    return tuple(int(x) for x in out)

@@ -115,6 +115,7 @@ SYMBOLS = [
     "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
     "kf_render_view", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
     "kf_view_slab_cross", "kf_view_slab_normals", "kf_view_from_rays",
+    "kf_shift_volume", "kf_volume_origin",
 ]
 
 
@@ -142,6 +143,8 @@ def load():
         _lib.kf_version.restype = C.c_char_p
         _lib.kf_stream.restype = C.c_void_p
         _lib.kf_view_device.restype = C.c_void_p
+        _lib.kf_shift_volume.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.kf_volume_origin.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     return _lib
 
 
@@ -590,6 +593,17 @@ class Context:
 
     def reset_volume(self):
         _chk(self.lib.kf_reset_volume(self.h), "kf_reset_volume")
+
+    def shift_volume(self, dx, dy, dz):
+        """the window moves by (dx, dy, dz) voxels, multiples of 8: contents, deferred weights and the device-resident pose move with it, in place
+        and asynchronously; the model maps are stale until the next raycast (kf_shift_volume)"""
+        _chk(self.lib.kf_shift_volume(self.h, int(dx), int(dy), int(dz)), "kf_shift_volume")
+
+    def volume_origin(self):
+        """(x, y, z): the sum of all shifts since the context was created / reset, in voxels (kf_volume_origin)"""
+        o = (C.c_int32 * 3)()
+        _chk(self.lib.kf_volume_origin(self.h, o), "kf_volume_origin")
+        return tuple(int(x) for x in o)
 
     def stats(self, observed=True):
         """observed=False: kf_get_fusion_counters -- the update counters only (weight_gt0 = 0), no sweep, no effect on the observed-voxel count's bookkeeping"""

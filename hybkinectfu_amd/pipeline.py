@@ -72,6 +72,17 @@ class SingleGpuPipeline:
         c.integrate(None, P["integrate_sdf_trunc"], self.integ_dist, has_color=self.color, angle_weight=self.color)
         c.raycast(None, self.inc, P["depth_trunc_min"], self.trunc_max, has_color=self.color)
 
+    def shift_volume(self, dx, dy, dz):
+        """The moving volume: slide the window by (dx, dy, dz) voxels (multiples of 8) between two frames, then raycast with the moved
+        device-resident pose so that the model maps show the new window before the next frame is tracked.  Nothing synchronises."""
+        c = self.ctx
+        c.shift_volume(dx, dy, dz)
+        if dx or dy or dz:
+            c.raycast(None, self.inc, P["depth_trunc_min"], self.trunc_max, has_color=self.color)
+
+    def volume_origin(self):
+        return self.ctx.volume_origin()
+
     def sync(self):
         self.ctx.sync()
 

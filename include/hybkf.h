@@ -426,6 +426,24 @@ int kf_resize_slab(kf_ctx* ctx, uint32_t z_begin, uint32_t z_end, uint32_t halo)
 int kf_count_layer_work(kf_ctx* ctx, int frames);
 int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /* blocking */
 
+/* The moving volume (no reference counterpart: the reference's cube stays where HybKinectfu::init put it, src/HybKinectfu.cpp:51-54).
+ * kf_shift_volume: the window moves by +d voxels, each component a multiple of 8 (whole bricks).  Afterwards voxel (x, y, z) holds what voxel
+ *   (x + dx, y + dy, z + dz) held before wherever that lies inside the volume -- (tsdf, weight), colour and the brick's deferred-weight state
+ *   (kf_set_defer stays in force) --, and everything else reads as after kf_reset_volume.  |d| >= resolution on an axis leaves an empty volume;
+ *   d = (0, 0, 0) returns 0 without enqueuing anything.  The device-resident pose moves with the contents, on the device:
+ *   t <- t - (float)d * cell (cell = size_m / resolution, the fp32 quotient) and its inverse is recomputed; the tracked / lost verdict stays.
+ *   In place (no second volume), asynchronous on the context's stream, no allocation and no synchronisation: it may sit between two frames
+ *   of a streamed run.  Brick flags, skip tables and the observed-voxel count follow as after kf_upload_volume.
+ *   THE MODEL MAPS ARE STALE AFTERWARDS: they are not translated.  Call kf_raycast_volume(transform = NULL) before the next kf_icp_track /
+ *   kf_sdf_track; then "shifted here" equals "uploaded there" bit for bit.
+ *   KF_ERR_ARG, with nothing touched and nothing enqueued: a component that is no multiple of 8; any non-zero shift on a z-slab context
+ *   (one that does not store the whole volume: a z shift needs a layer exchange between the members -- slab groups cannot shift yet);
+ *   a sum of shifts beyond 32 bits.
+ * kf_volume_origin: the sum of all shifts since kf_create / kf_reset_volume, in voxels: where voxel (0, 0, 0) of the window lies in the first
+ *   cube.  World position = volume position + origin * cell.  Host bookkeeping: never blocks.  Zero on a context that never shifts. */
+int kf_shift_volume(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz);
+int kf_volume_origin(kf_ctx* ctx, int32_t origin_vox[3]);
+
 /* test hook: counts fp32 quotients where the kernels' split exact-division helper differs from the compiler's `/` (must be 0) */
 int kf_selftest_div(kf_ctx* ctx, unsigned n, unsigned seed, int mode, unsigned* mismatches);
 
