@@ -123,6 +123,7 @@ extern "C" int kf_destroy(kf_ctx* c) {
                   c->tile_max_depth, c->view_img, c->triangles, c->mc_block_counts, c->mc_list, c->mc_nbr_bits, c->mc_partials, c->mc_codes, c->mc_surv, c->mc_block_bits, c->mc_recs, c->mc_d1_list};
   for (void* p : ptrs) if (p) hipFree(p);
   kf_weld_free(c);
+  kf_world_soup_free(c);
   if (c->up_stream) { hipStreamSynchronize(c->up_stream); hipStreamDestroy(c->up_stream); }
   for (int i = 0; i < KF_UP_SLOTS; ++i) {
     if (c->up_host[i]) hipHostFree(c->up_host[i]);
@@ -254,6 +255,7 @@ extern "C" int kf_reset_volume(kf_ctx* c) {
   ++c->vol_flags_serial; c->pend_live = 0;
   c->wgt0_base = 0; c->wgt0_valid = 1;                       // nothing observed; the shards were zeroed with the counters
   c->origin_vox[0] = c->origin_vox[1] = c->origin_vox[2] = 0; // the window is back on the first cube (kf_shift_volume)
+  if (c->soup) KF_CHECK(hipMemsetAsync(c->soup_cnt, 0, 4 * sizeof(unsigned), c->stream));   // ... and the world soup describes a world that is gone
   return 0;
 }
 

@@ -222,6 +222,12 @@ struct kf_ctx {
   unsigned* mc_block_counts; size_t mc_blocks_cap;
   unsigned* mc_list; unsigned* mc_nbr_bits; unsigned* mc_partials;   // extraction scratch, allocated by the first kf_marching_cubes
   unsigned short* mc_codes; unsigned char* mc_surv; unsigned* mc_block_bits; uint2* mc_recs; unsigned* mc_d1_list;   // voxel classes, sieve bits, cell records, brick list (mcubes.hip), same scratch
+  uint32_t mc_recs_cap;          // cells mc_recs holds: the larger of the triangle buffer's and the world soup's capacity when the scratch was allocated / the soup reserved
+  int region_noop;               // the last kf_marching_cubes_region had an empty box (kf_region_work reports zeros)
+  // the world soup (mcubes.hip; kf_world_soup_reserve ...): a second triangle buffer, in WORLD coordinates, for surface whose window has moved on.
+  // soup_cnt: [0] triangles held, [2] [3] a 64-bit count of the triangles that did not fit since the last clear.  Absent until reserved.
+  kf_triangle* soup; uint32_t soup_cap; unsigned* soup_cnt;
+  int stream_on, stream_color; float stream_thr;   // kf_set_stream_out: kf_shift_volume extracts what is about to leave into the world soup
   struct KfWeld* weld;           // scratch and indexed mesh of kf_weld_mesh (weld.hip), allocated by the first weld
   unsigned long long* layer_work; int layer_work_frames;   // per-brick-layer update counts of the next `layer_work_frames` integrate calls (kf_count_layer_work)
   int defer_override;            // kf_set_defer: -1 follow the environment (default), 0 never defer, 1 defer
@@ -648,3 +654,6 @@ int kf_tail_cull_discard(kf_ctx* ctx);   // a cull that ran as the tail of a tra
 void kf_weld_free(kf_ctx* ctx);          // (weld.hip) what kf_weld_release frees, for kf_destroy: the caller has synchronised the stream
 int kf_view_reserve(kf_ctx* ctx, uint32_t cols, uint32_t rows, unsigned** img);   // (view.hip) the view image for a cols x rows view about to be enqueued; it becomes "the last view"
 int kf_upload_wait_for(kf_ctx* ctx, const uint16_t* dev_mm);   // dev_mm is about to be read on the context's stream: wait for its staged copy, if it is one
+// (mcubes.hip) kf_marching_cubes_region past its argument checks: what kf_shift_volume's stream-out enqueues for each departing box
+int kf_mc_region_enqueue(kf_ctx* ctx, int has_color, float thr, const int32_t lo[3], const int32_t hi[3], int flags);
+void kf_world_soup_free(kf_ctx* ctx);    // (mcubes.hip) for kf_destroy: the caller has synchronised the stream

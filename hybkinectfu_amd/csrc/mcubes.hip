@@ -25,13 +25,19 @@ __constant__ unsigned long long c_tri_words[256] = {
 
 struct McArgs {
   KfVolume vol;
-  int z0, z1;                    // cell layers processed (owned slab)
+  int z0, z1;                    // cell layers processed (owned slab; the box of a region extraction)
+  // The cells are numbered in (z, y, x) order inside the box [xa, xa + wx) x [y0, y0 + wy) x [z0, z1): the whole volume (0, res, 0, res) for
+  // kf_marching_cubes, the caller's box for kf_marching_cubes_region -- there with the x range widened to whole bricks (xa, wx multiples of 8), so
+  // that eight consecutive cells always share one sieve byte; [x0, x1) is the x range that really counts (mc_xmask).
+  int xa, wx, y0, wy, x0, x1;
   int has_color;
   float thr;
   unsigned* block_counts;        // [n_blocks + 1]
   unsigned n_blocks;
   kf_triangle* tris; unsigned max_tris;
-  KfCounters* cnt;
+  const unsigned* n_held;        // triangles the destination already holds (the triangle buffer's count, or the world soup's)
+  int world; float3 woff;        // KF_MC_WORLD: every position + woff, woff = (float)origin_vox * cell
+  int spread;                    // k_mc_count deals the listed blocks out evenly instead of MC_BATCH at a time (a region's short list: 64 blocks to one workgroup is a serial walk)
   int count_work;                // measurement passes: count the blocks that pass the neighbourhood test (kf_stage_timers bit 16)
   unsigned* nbr_bits;            // one bit per stored brick: some brick of its 3x3x3 neighbourhood holds a negative voxel
   unsigned* list;                // blocks that may hold surface, in no particular order (their output position comes from the scan)
@@ -48,6 +54,14 @@ struct McArgs {
   unsigned recs_cap;
 };
 #define MC_CHUNK KF_SCAN_CHUNK     // block counts scanned by one workgroup (scan.h)
+__device__ __forceinline__ size_t mc_n_cells(const McArgs& a) { return (size_t)(a.z1 - a.z0) * (size_t)a.wy * (size_t)a.wx; }
+// the cells cx .. cx + 7 (cx a multiple of 8 inside [xa, xa + wx)) that lie in [x0, x1), as a mask over their sieve byte
+__device__ __forceinline__ unsigned mc_xmask(const McArgs& a, int cx) {
+  unsigned m = 0xFFu;
+  if (cx < a.x0) m &= 0xFFu << (a.x0 - cx);
+  if (cx + 8 > a.x1) m &= 0xFFu >> (cx + 8 - a.x1);
+  return m & 0xFFu;
+}
 
 __device__ __forceinline__ float sel8(const float d[8], int k) {
   float r = d[0];
@@ -266,15 +280,15 @@ __global__ void __launch_bounds__(256) k_mc_sift(McArgs a) {
       }
     }
     a.surv[(size_t)slot * 64u + lane] = (unsigned char)mask8;
-    // the 256-cell block these eight cells lie in (R is a multiple of 8) -> its bit.  The eight rows of one z share a word (two at
+    // the 256-cell block these eight cells lie in (wx is a multiple of 8) -> its bit.  The eight rows of one z share a word (two at
     // 2048^3): the first lane of each run of equal words ORs the run's bits together and issues the one atomic.
     unsigned word = 0xFFFFFFFFu, bit = 0u;
     {
       const int bx = (int)(slot % (unsigned)nb), by = (int)((slot / (unsigned)nb) % (unsigned)nb), bz = (int)(slot / ((unsigned)nb * nb)) + v.bz0;
       const int y = by * 8 + (int)(lane & 7u), z = bz * 8 + (int)(lane >> 3);
-      if (z >= a.z0 && z < a.z1) {
-        const unsigned blk = (unsigned)((((size_t)(z - a.z0) * R + y) * R + (size_t)bx * 8u) >> 8);
-        word = blk >> 5; bit = mask8 ? 1u << (blk & 31u) : 0u;
+      if (z >= a.z0 && z < a.z1 && y >= a.y0 && y < a.y0 + a.wy && bx * 8 >= a.xa && bx * 8 < a.xa + a.wx) {
+        const unsigned blk = (unsigned)((((size_t)(z - a.z0) * a.wy + (y - a.y0)) * a.wx + (size_t)(bx * 8 - a.xa)) >> 8);
+        word = blk >> 5; bit = (mask8 & mc_xmask(a, bx * 8)) ? 1u << (blk & 31u) : 0u;
       }
     }
     const unsigned prev_word = (unsigned)__shfl_up((int)word, 1, 8);
@@ -289,7 +303,7 @@ __global__ void __launch_bounds__(256) k_mc_sift(McArgs a) {
 }
 __device__ __forceinline__ bool mc_survives(const McArgs& a, int x, int y, int z) {
   const size_t slot = kf_brick_slot(a.vol, x >> 3, y >> 3, z >> 3);
-  return (a.surv[slot * 64u + (size_t)(((z & 7) << 3) | (y & 7))] >> (x & 7)) & 1u;
+  return x >= a.x0 && x < a.x1 && ((a.surv[slot * 64u + (size_t)(((z & 7) << 3) | (y & 7))] >> (x & 7)) & 1u);
 }
 
 // ---- which blocks need visiting ------------------------------------------------------------------------------------------------
@@ -387,13 +401,19 @@ __global__ void __launch_bounds__(256) k_mc_list(McArgs a) {
 // cell (x, y, z) of lane `tid` in the 256-cell block `blk`: the block's first cell is decoded once (wave-uniform), the lane's offset
 // is added with carries -- three 64-bit divisions per LANE here cost as much as the cell's whole evaluation
 __device__ __forceinline__ bool mc_cell_of(const McArgs& a, unsigned blk, unsigned tid, size_t n_cells, int& x, int& y, int& z) {
-  const unsigned R = (unsigned)a.vol.res;
+  const unsigned R = (unsigned)a.wx, Ry = (unsigned)a.wy;
   const size_t f = (size_t)blk * 256;
   if (f + tid >= n_cells) return false;
   const unsigned row = (unsigned)(f / R);                           // uniform
-  unsigned cx = (unsigned)(f - (size_t)row * R) + tid, cy = row % R, cz = row / R;
-  while (cx >= R) { cx -= R; if (++cy == R) { cy = 0; ++cz; } }      // at most 256 / R turns (none when R is a multiple of 256)
-  x = (int)cx; y = (int)cy; z = a.z0 + (int)cz;
+  unsigned cx = (unsigned)(f - (size_t)row * R) + tid, cy = row % Ry, cz = row / Ry;
+  if (R >= 64u) {
+    while (cx >= R) { cx -= R; if (++cy == Ry) { cy = 0; ++cz; } }   // at most 256 / R turns (none when R is a multiple of 256)
+  } else if (cx >= R) {                                              // the short rows of a thin box: up to 32 turns, so divide instead
+    const unsigned q = cx / R;
+    cx -= q * R; cy += q;
+    if (cy >= Ry) { const unsigned qy = cy / Ry; cy -= qy * Ry; cz += qy; }
+  }
+  x = a.xa + (int)cx; y = a.y0 + (int)cy; z = a.z0 + (int)cz;
   return true;
 }
 
@@ -411,12 +431,13 @@ __device__ __forceinline__ bool mc_cell_of(const McArgs& a, unsigned blk, unsign
 __global__ void __launch_bounds__(256) MC_COUNT_ATTR k_mc_count(McArgs a) {
   __shared__ unsigned s_cnt[MC_BATCH], s_qstart[MC_BATCH], s_bstart[MC_BATCH], s_wave[4];
   __shared__ unsigned short s_q[MC_BATCH * 256];
-  const int R = a.vol.res;
-  const size_t n_cells = (size_t)(a.z1 - a.z0) * R * R;
+  const size_t n_cells = mc_n_cells(a);
   const unsigned n_list = *a.n_list;
   const unsigned lane = threadIdx.x & 63u;
-  for (unsigned base = blockIdx.x * MC_BATCH; base < n_list; base += gridDim.x * MC_BATCH) {
-    const unsigned nbat = n_list - base < MC_BATCH ? n_list - base : MC_BATCH;
+  unsigned batch = MC_BATCH;                                                     // blocks per turn (uniform); any value in 1 .. MC_BATCH works below
+  if (a.spread) { batch = (n_list + gridDim.x - 1u) / gridDim.x; batch = batch < 1u ? 1u : (batch > MC_BATCH ? MC_BATCH : batch); }
+  for (unsigned base = blockIdx.x * batch; base < n_list; base += gridDim.x * batch) {
+    const unsigned nbat = n_list - base < batch ? n_list - base : batch;
     // the batch's sieve bytes: pass p, lane (b_local, k) -> byte k (cells 8k .. 8k+7) of block p * 8 + b_local; all loads first
     unsigned sv[MC_BATCH / 8];
 #pragma unroll
@@ -425,7 +446,7 @@ __global__ void __launch_bounds__(256) MC_COUNT_ATTR k_mc_count(McArgs a) {
       sv[p] = 0;
       int cx, cy, cz;
       if (b < nbat && mc_cell_of(a, a.list[base + b], 8u * k, n_cells, cx, cy, cz))
-        sv[p] = a.surv[(size_t)kf_brick_slot(a.vol, cx >> 3, cy >> 3, cz >> 3) * 64u + (size_t)(((cz & 7) << 3) | (cy & 7))];
+        sv[p] = a.surv[(size_t)kf_brick_slot(a.vol, cx >> 3, cy >> 3, cz >> 3) * 64u + (size_t)(((cz & 7) << 3) | (cy & 7))] & mc_xmask(a, cx);
     }
     if (threadIdx.x < MC_BATCH) s_cnt[threadIdx.x] = 0;
     unsigned nq = 0;
@@ -481,6 +502,11 @@ __device__ __forceinline__ void mc_write_triangles(const McArgs& a, const CellEv
     tri.v0 = edge_vertex(a, e, (unsigned)((e.word >> (12 * t)) & 0xF));
     tri.v1 = edge_vertex(a, e, (unsigned)((e.word >> (12 * t + 4)) & 0xF));
     tri.v2 = edge_vertex(a, e, (unsigned)((e.word >> (12 * t + 8)) & 0xF));
+    if (a.world) {
+      tri.v0.pos[0] += a.woff.x; tri.v0.pos[1] += a.woff.y; tri.v0.pos[2] += a.woff.z;
+      tri.v1.pos[0] += a.woff.x; tri.v1.pos[1] += a.woff.y; tri.v1.pos[2] += a.woff.z;
+      tri.v2.pos[0] += a.woff.x; tri.v2.pos[1] += a.woff.y; tri.v2.pos[2] += a.woff.z;
+    }
     a.tris[dst] = tri;
   }
 }
@@ -490,9 +516,8 @@ __device__ __forceinline__ void mc_write_triangles(const McArgs& a, const CellEv
 __global__ void __launch_bounds__(256) k_mc_emit_recs(McArgs a) {
   if (*a.recs_overflow) return;
   const unsigned n_recs = *a.n_recs;
-  const int R = a.vol.res;
-  const size_t n_cells = (size_t)(a.z1 - a.z0) * R * R;
-  const unsigned held = a.cnt->n_triangles;
+  const size_t n_cells = mc_n_cells(a);
+  const unsigned held = *a.n_held;
   for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n_recs; i += gridDim.x * 256u) {
     const uint2 r = a.recs[i];
     int cx, cy, cz;
@@ -509,8 +534,7 @@ __global__ void __launch_bounds__(256) k_mc_emit(McArgs a) {
   __shared__ unsigned s_wave[4], s_wc[4];
   __shared__ unsigned char s_q[256];
   if (!*a.recs_overflow) return;
-  const int R = a.vol.res;
-  const size_t n_cells = (size_t)(a.z1 - a.z0) * R * R;
+  const size_t n_cells = mc_n_cells(a);
   const unsigned n_list = *a.n_list;
   for (unsigned li = blockIdx.x; li < n_list; li += gridDim.x) {
     const unsigned blk = a.list[li];
@@ -534,15 +558,159 @@ __global__ void __launch_bounds__(256) k_mc_emit(McArgs a) {
     }
     unsigned total;
     const unsigned off0 = kf_block_excl_scan((unsigned)n, s_wave, total);
-    mc_write_triangles(a, e, n, a.cnt->n_triangles + my_base + off0);
+    mc_write_triangles(a, e, n, *a.n_held + my_base + off0);
   }
 }
 
-__global__ void k_mc_finish(KfCounters* cnt, unsigned max_tris) {
+// the destination's count after an extraction: what it held + the scan's total, clamped at its capacity (marchingcube.cu:29-31); `dropped` (the
+// world soup's; null for the triangle buffer) sums what did not fit
+// work (a region extraction's; null otherwise): what kf_region_work reports -- the lengths of the class pass's brick list and of the block list
+__global__ void k_mc_finish(unsigned* n_tris, const unsigned* scan_total, unsigned max_tris, unsigned long long* dropped, const unsigned* n_d1, const unsigned* n_list,
+                            unsigned* work) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
-    unsigned long long t = (unsigned long long)cnt->n_triangles + cnt->scan_total;
-    cnt->n_triangles = (unsigned)(t > max_tris ? max_tris : t);
+    unsigned long long t = (unsigned long long)*n_tris + *scan_total;
+    if (dropped && t > max_tris) *dropped += t - max_tris;
+    *n_tris = (unsigned)(t > max_tris ? max_tris : t);
+    if (work) { work[0] = *n_d1; work[1] = *n_list; }
   }
+}
+// the exclusive prefix of a short array of block counts by ONE workgroup, KF_SCAN_CHUNK values at a time: one launch where kf_scan_in_place takes three
+// (a thin box has a few thousand blocks; its extraction is a chain of short launches, and the chain's length is its cost)
+#define MC_SMALL_SCAN_CHUNKS 8u
+__global__ void __launch_bounds__(256) k_mc_scan_small(unsigned* counts, unsigned n, unsigned* total_out) {
+  __shared__ unsigned s_wave[4];
+  unsigned carry = 0;
+  for (unsigned base = 0; base < n; base += KF_SCAN_CHUNK) {
+    const unsigned i0 = base + threadIdx.x * 16u;
+    unsigned v[16]; unsigned local = 0;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { v[k] = (i0 + k < n) ? counts[i0 + k] : 0u; local += v[k]; }
+    unsigned total;
+    unsigned excl = carry + kf_block_excl_scan(local, s_wave, total);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) { if (i0 + k < n) counts[i0 + k] = excl; excl += v[k]; }
+    carry += total;
+  }
+  if (threadIdx.x == 0) { counts[n] = carry; *total_out = carry; }
+}
+// a region extraction's three clears in one launch: the block counts (n_blocks + 1), the block bits and the five counters at the head of mc_list
+__global__ void __launch_bounds__(256) k_mc_region_clear(unsigned* __restrict__ counts, unsigned n_counts, unsigned* __restrict__ bits, unsigned n_bits, unsigned* __restrict__ head) {
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  if (i < n_counts) counts[i] = 0u;
+  if (i < n_bits) bits[i] = 0u;
+  if (i < 5u) head[i] = 0u;
+}
+
+// ---- the bricks of a region extraction ----------------------------------------------------------------------------------------------
+// kf_marching_cubes_region reads the classes of the bricks its box touches, widened by one brick (a cell reads voxels -1 .. +1), and
+// sieves the bricks the box touches.  One lane per brick of the widened range decides what k_mc_dilate decides for every stored brick --
+// does a brick of its 3x3x3 neighbourhood hold a negative voxel -- and
+//   yes: lists the brick for k_mc_codes (a.d1_list) and, when the box touches it, for k_mc_sift (sift_list);
+//   no : writes its class row (and, inside the box, its sieve row) as zeros -- what the whole-volume extraction expects to find there, and
+//        nothing is trusted that an earlier extraction left: every row the region reads is written by the region call itself.
+struct McRegionBricks { int wlo[3], wn[3], blo[3], bhi[3]; };
+__global__ void __launch_bounds__(256) k_mc_region_bricks(McArgs a, McRegionBricks g, unsigned* __restrict__ sift_list, unsigned* n_sift) {
+  const KfVolume& v = a.vol;
+  const unsigned n = (unsigned)g.wn[0] * (unsigned)g.wn[1] * (unsigned)g.wn[2];
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  bool any = false, inbox = false;
+  unsigned slot = 0;
+  if (i < n) {
+    const int nb = v.nb;
+    const int bx = g.wlo[0] + (int)(i % (unsigned)g.wn[0]), by = g.wlo[1] + (int)((i / (unsigned)g.wn[0]) % (unsigned)g.wn[1]);
+    const int bz = g.wlo[2] + (int)(i / ((unsigned)g.wn[0] * (unsigned)g.wn[1]));
+    slot = kf_brick_slot(v, bx, by, bz);
+    inbox = bx >= g.blo[0] && bx < g.bhi[0] && by >= g.blo[1] && by < g.bhi[1] && bz >= g.blo[2] && bz < g.bhi[2];
+    for (int dz = -1; dz <= 1; ++dz) {
+      const int z = bz + dz;
+      if (z < v.bz0 || z >= v.bz1) continue;
+      for (int dy = -1; dy <= 1; ++dy) {
+        const int y = by + dy;
+        if (y < 0 || y >= nb) continue;
+        for (int dx = -1; dx <= 1; ++dx) {
+          const int x = bx + dx;
+          if (x < 0 || x >= nb) continue;
+          const size_t s2 = kf_brick_slot(v, x, y, z);
+          any = any || ((v.negbits[s2 >> 5] >> (s2 & 31u)) & 1u);
+        }
+      }
+    }
+    if (!any) {
+      uint4* cr = reinterpret_cast<uint4*>(a.codes + (size_t)slot * 64u);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) cr[k] = make_uint4(0u, 0u, 0u, 0u);
+      if (inbox) {
+        uint4* sr = reinterpret_cast<uint4*>(a.surv + (size_t)slot * 64u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) sr[k] = make_uint4(0u, 0u, 0u, 0u);
+      }
+    }
+  }
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned long long m = __ballot(any), ms = __ballot(any && inbox);
+  unsigned at = 0, ats = 0;
+  if (lane == 0) {
+    if (m) at = atomicAdd(a.n_d1, (unsigned)__popcll(m));
+    if (ms) ats = atomicAdd(n_sift, (unsigned)__popcll(ms));
+  }
+  at = (unsigned)__builtin_amdgcn_readfirstlane((int)at); ats = (unsigned)__builtin_amdgcn_readfirstlane((int)ats);
+  if (any) a.d1_list[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = slot;
+  if (any && inbox) sift_list[ats + (unsigned)__popcll(ms & ((1ull << lane) - 1ull))] = slot;
+}
+
+// extraction scratch: allocated by the first extraction, not by every context (per 4-KiB brick: 128 B of voxel classes + 64 B of sieve bits + 12 B of lists)
+// mc_list: [0] block list length, [1] records, [2] overflow, [3] class-pass bricks, [4] sieve bricks of a region, [5] [6] kf_region_work; then the block ids
+#define MC_LIST_HEAD 8
+static int mc_scratch(kf_ctx* c) {
+  if (c->mc_list) return 0;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  // all or nothing: the pointers are committed to the context only once every allocation has succeeded (at 2048^3 the scratch is
+  // ~3.3 GB next to 68.7 GB of voxels -- a failure must not leave a half-allocated set behind that the next call would trust)
+  size_t recs = c->max_triangles > c->soup_cap ? c->max_triangles : c->soup_cap;
+  if (recs == 0) recs = 1;
+  const size_t sizes[8] = {(c->mc_blocks_cap + MC_LIST_HEAD) * sizeof(unsigned),                        // list: the head, then the block ids
+                           (c->n_stored_bricks / 32 + 4) * sizeof(unsigned),                           // neighbourhood bits
+                           ((c->mc_blocks_cap + MC_CHUNK - 1) / MC_CHUNK + 1) * sizeof(unsigned),       // scan partials
+                           c->n_stored_bricks * 64 * sizeof(unsigned short),                            // voxel classes
+                           c->n_stored_bricks * 64,                                                    // sieve survivors
+                           2 * c->n_stored_bricks * sizeof(unsigned),                                  // brick list; behind it a region's sieve list
+                           (c->mc_blocks_cap / 32 + 2) * sizeof(unsigned),                             // block bits
+                           recs * sizeof(uint2)};                                                      // records: a recorded cell holds >= 1 triangle
+  void* got[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < 8; ++i) {
+    const hipError_t e = hipMalloc(&got[i], sizes[i]);
+    if (e != hipSuccess) { for (int j = 0; j < i; ++j) hipFree(got[j]); (void)hipGetLastError(); return (int)e; }
+  }
+  c->mc_list = (unsigned*)got[0]; c->mc_nbr_bits = (unsigned*)got[1]; c->mc_partials = (unsigned*)got[2]; c->mc_codes = (unsigned short*)got[3];
+  c->mc_surv = (unsigned char*)got[4]; c->mc_d1_list = (unsigned*)got[5]; c->mc_block_bits = (unsigned*)got[6]; c->mc_recs = (uint2*)got[7];
+  c->mc_recs_cap = (uint32_t)recs;
+  c->region_noop = 1;                                      // no region call on this scratch yet: kf_region_work reports zeros, not what hipMalloc left in the head
+  c->mc_zero_serial = c->vol_flags_serial - 1;
+  return 0;
+}
+static void mc_scratch_args(kf_ctx* c, McArgs& a) {
+  a.block_counts = c->mc_block_counts; a.count_work = c->count_work;
+  a.nbr_bits = c->mc_nbr_bits; a.n_list = c->mc_list; a.n_recs = c->mc_list + 1; a.recs_overflow = c->mc_list + 2; a.list = c->mc_list + MC_LIST_HEAD;
+  a.partials = c->mc_partials; a.codes = c->mc_codes; a.surv = c->mc_surv; a.block_bits = c->mc_block_bits;
+  a.recs = c->mc_recs; a.recs_cap = c->mc_recs_cap; a.d1_list = c->mc_d1_list; a.n_d1 = c->mc_list + 3;
+}
+// list -> count -> scan -> emit -> finish: the second half of an extraction, the same for the whole volume and for a box
+static void mc_count_and_emit(kf_ctx* c, const McArgs& a, unsigned* n_tris, unsigned long long* dropped, unsigned* work) {
+  // persistent workgroups walking the block list / the records, no more of them than a small box has blocks (k_mc_count takes MC_BATCH at a time)
+  const unsigned walk_all = (unsigned)c->num_cus * 8u, walk = a.n_blocks < walk_all ? a.n_blocks : walk_all;
+  const unsigned walk_count = a.spread ? walk : ((a.n_blocks + MC_BATCH - 1) / MC_BATCH < walk_all ? (a.n_blocks + MC_BATCH - 1) / MC_BATCH : walk_all);
+  const unsigned list_wgs = ((a.n_blocks + 31u) / 32u + 255u) / 256u;
+  const unsigned lgx = list_wgs < 65535u ? list_wgs : 65535u, lgy = (list_wgs + lgx - 1) / lgx;
+  hipLaunchKernelGGL(k_mc_list, dim3(lgx, lgy), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_mc_count, dim3(walk_count), dim3(256), 0, c->stream, a);
+  if (work && a.n_blocks <= MC_SMALL_SCAN_CHUNKS * KF_SCAN_CHUNK)
+    hipLaunchKernelGGL(k_mc_scan_small, dim3(1), dim3(256), 0, c->stream, a.block_counts, a.n_blocks, &c->counters->scan_total);
+  else
+    kf_scan_in_place(a.block_counts, a.n_blocks, a.partials, &c->counters->scan_total, c->stream);   // scan.h: reduce / partials / apply
+  hipLaunchKernelGGL(k_mc_emit_recs, dim3(walk), dim3(256), 0, c->stream, a);
+  hipLaunchKernelGGL(k_mc_emit, dim3(walk), dim3(256), 0, c->stream, a);              // returns at once unless the record list overflowed
+  hipLaunchKernelGGL(k_mc_finish, dim3(1), dim3(64), 0, c->stream, n_tris, (const unsigned*)&c->counters->scan_total, a.max_tris, dropped,
+                     (const unsigned*)a.n_d1, (const unsigned*)a.n_list, work);
 }
 
 extern "C" int kf_marching_cubes(kf_ctx* c, int has_color, float thr) {
@@ -551,35 +719,14 @@ extern "C" int kf_marching_cubes(kf_ctx* c, int has_color, float thr) {
   if (has_color && !c->vol.color) return KF_ERR_STATE;
   McArgs a;
   a.vol = c->vol; a.z0 = c->vol.own_z0; a.z1 = c->vol.own_z1; a.has_color = has_color; a.thr = thr;
+  a.xa = 0; a.wx = c->vol.res; a.y0 = 0; a.wy = c->vol.res; a.x0 = 0; a.x1 = c->vol.res;
+  a.world = 0; a.woff = make_float3(0.f, 0.f, 0.f); a.spread = 0;
   const size_t n_cells = (size_t)(a.z1 - a.z0) * c->vol.res * c->vol.res;
   a.n_blocks = (unsigned)((n_cells + 255) / 256);
   if (a.n_blocks > c->mc_blocks_cap) return KF_ERR_STATE;
-  if (!c->mc_list) {                                       // extraction scratch: allocated by the first extraction, not by every context
-    KF_CHECK(hipSetDevice(c->cfg.device));                 // (per 4-KiB brick: 128 B of voxel classes + 64 B of sieve bits + 8 B of row bits)
-    // all or nothing: the pointers are committed to the context only once every allocation has succeeded (at 2048^3 the scratch is
-    // ~3.3 GB next to 68.7 GB of voxels -- a failure must not leave a half-allocated set behind that the next call would trust)
-    const size_t sizes[8] = {(c->mc_blocks_cap + 4) * sizeof(unsigned),                                  // list: [0] length, [1] records, [2] overflow, [3] bricks; then the block ids
-                             (c->n_stored_bricks / 32 + 4) * sizeof(unsigned),                           // neighbourhood bits
-                             ((c->mc_blocks_cap + MC_CHUNK - 1) / MC_CHUNK + 1) * sizeof(unsigned),       // scan partials
-                             c->n_stored_bricks * 64 * sizeof(unsigned short),                            // voxel classes
-                             c->n_stored_bricks * 64,                                                    // sieve survivors
-                             c->n_stored_bricks * sizeof(unsigned),                                      // brick list
-                             (c->mc_blocks_cap / 32 + 2) * sizeof(unsigned),                             // block bits
-                             (size_t)c->max_triangles * sizeof(uint2)};                                  // records: a recorded cell holds >= 1 triangle
-    void* got[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    for (int i = 0; i < 8; ++i) {
-      const hipError_t e = hipMalloc(&got[i], sizes[i]);
-      if (e != hipSuccess) { for (int j = 0; j < i; ++j) hipFree(got[j]); (void)hipGetLastError(); return (int)e; }
-    }
-    c->mc_list = (unsigned*)got[0]; c->mc_nbr_bits = (unsigned*)got[1]; c->mc_partials = (unsigned*)got[2]; c->mc_codes = (unsigned short*)got[3];
-    c->mc_surv = (unsigned char*)got[4]; c->mc_d1_list = (unsigned*)got[5]; c->mc_block_bits = (unsigned*)got[6]; c->mc_recs = (uint2*)got[7];
-    c->mc_zero_serial = c->vol_flags_serial - 1;
-  }
-  a.block_counts = c->mc_block_counts; a.tris = c->triangles; a.max_tris = c->max_triangles; a.cnt = c->counters;
-  a.count_work = c->count_work;
-  a.nbr_bits = c->mc_nbr_bits; a.n_list = c->mc_list; a.n_recs = c->mc_list + 1; a.recs_overflow = c->mc_list + 2; a.list = c->mc_list + 4;
-  a.partials = c->mc_partials; a.codes = c->mc_codes; a.surv = c->mc_surv; a.block_bits = c->mc_block_bits;
-  a.recs = c->mc_recs; a.recs_cap = c->max_triangles; a.d1_list = c->mc_d1_list; a.n_d1 = c->mc_list + 3;
+  { const int st = mc_scratch(c); if (st) return st; }
+  mc_scratch_args(c, a);
+  a.tris = c->triangles; a.max_tris = c->max_triangles; a.n_held = &c->counters->n_triangles;
   kf_evt_begin(c, KF_STAGE_MCUBES);
   if (c->mc_zero_serial != c->vol_flags_serial) {          // bricks outside the has-negative neighbourhood set must read as class 0 / no survivor
     KF_CHECK(hipMemsetAsync(c->mc_codes, 0, c->n_stored_bricks * 64 * sizeof(unsigned short), c->stream));
@@ -594,19 +741,162 @@ extern "C" int kf_marching_cubes(kf_ctx* c, int has_color, float thr) {
     hipLaunchKernelGGL(k_mc_dilate_words, dim3((n_slots / 32 + 255) / 256), dim3(256), 0, c->stream, c->vol, c->mc_nbr_bits, n_slots / 32, a.d1_list, a.n_d1, c->count_work ? c->counters : nullptr);
   else
     hipLaunchKernelGGL(k_mc_dilate, dim3((n_slots + 255) / 256), dim3(256), 0, c->stream, c->vol, c->mc_nbr_bits, n_slots, a.d1_list, a.n_d1, c->count_work ? c->counters : nullptr);
-  const unsigned walk = (unsigned)c->num_cus * 8u;         // persistent workgroups walking the brick list / the block list / the records
+  const unsigned walk = (unsigned)c->num_cus * 8u;
   hipLaunchKernelGGL(k_mc_codes, dim3(walk), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(k_mc_sift, dim3(walk), dim3(256), 0, c->stream, a);
-  const unsigned list_wgs = ((a.n_blocks + 31u) / 32u + 255u) / 256u;
-  const unsigned lgx = list_wgs < 65535u ? list_wgs : 65535u, lgy = (list_wgs + lgx - 1) / lgx;
-  hipLaunchKernelGGL(k_mc_list, dim3(lgx, lgy), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(k_mc_count, dim3(walk), dim3(256), 0, c->stream, a);
-  kf_scan_in_place(a.block_counts, a.n_blocks, a.partials, &c->counters->scan_total, c->stream);   // scan.h: reduce / partials / apply
-  hipLaunchKernelGGL(k_mc_emit_recs, dim3(walk), dim3(256), 0, c->stream, a);
-  hipLaunchKernelGGL(k_mc_emit, dim3(walk), dim3(256), 0, c->stream, a);              // returns at once unless the record list overflowed
-  hipLaunchKernelGGL(k_mc_finish, dim3(1), dim3(64), 0, c->stream, c->counters, c->max_triangles);
+  mc_count_and_emit(c, a, &c->counters->n_triangles, nullptr, nullptr);
   kf_evt_end(c, KF_STAGE_MCUBES);
   return (int)hipGetLastError();
+}
+
+// ---- region extraction and the world soup ---------------------------------------------------------------------------------------------
+// (kf_internal.h) the region extraction behind kf_marching_cubes_region and kf_shift_volume's stream-out: the arguments are checked by the callers
+int kf_mc_region_enqueue(kf_ctx* c, int has_color, float thr, const int32_t lo_in[3], const int32_t hi_in[3], int flags) {
+  const KfVolume& v = c->vol;
+  const int R = v.res;
+  int lo[3], hi[3];
+  for (int k = 0; k < 3; ++k) {
+    lo[k] = lo_in[k] < 0 ? 0 : (lo_in[k] > R ? R : lo_in[k]);
+    hi[k] = hi_in[k] < 0 ? 0 : (hi_in[k] > R ? R : hi_in[k]);
+    if (lo[k] >= hi[k]) { c->region_noop = 1; return 0; }    // empty or inverted: nothing to do
+  }
+  const bool to_soup = (flags & KF_MC_TO_WORLD_SOUP) != 0;
+  McArgs a;
+  a.vol = v; a.has_color = has_color; a.thr = thr;
+  a.x0 = lo[0]; a.x1 = hi[0]; a.xa = lo[0] & ~7; a.wx = ((hi[0] + 7) & ~7) - a.xa;
+  a.y0 = lo[1]; a.wy = hi[1] - lo[1]; a.z0 = lo[2]; a.z1 = hi[2];
+  a.world = (flags & KF_MC_WORLD) ? 1 : 0; a.spread = 1;
+  a.woff = make_float3((float)c->origin_vox[0] * v.cell, (float)c->origin_vox[1] * v.cell, (float)c->origin_vox[2] * v.cell);
+  const size_t n_cells = (size_t)(a.z1 - a.z0) * (size_t)a.wy * (size_t)a.wx;
+  a.n_blocks = (unsigned)((n_cells + 255) / 256);
+  if (a.n_blocks > c->mc_blocks_cap) return KF_ERR_STATE;
+  { const int st = mc_scratch(c); if (st) return st; }
+  mc_scratch_args(c, a);
+  unsigned* n_tris; unsigned long long* dropped = nullptr;
+  if (to_soup) { a.tris = c->soup; a.max_tris = c->soup_cap; n_tris = c->soup_cnt; dropped = reinterpret_cast<unsigned long long*>(c->soup_cnt + 2); }
+  else { a.tris = c->triangles; a.max_tris = c->max_triangles; n_tris = &c->counters->n_triangles; }
+  a.n_held = n_tris;
+  McRegionBricks g;
+  unsigned n_w = 1;
+  for (int k = 0; k < 3; ++k) {
+    g.blo[k] = lo[k] >> 3; g.bhi[k] = ((hi[k] - 1) >> 3) + 1;
+    g.wlo[k] = g.blo[k] > 0 ? g.blo[k] - 1 : 0;
+    const int whi = g.bhi[k] < v.nb ? g.bhi[k] + 1 : v.nb;
+    g.wn[k] = whi - g.wlo[k];
+    n_w *= (unsigned)g.wn[k];
+  }
+  unsigned* sift_list = c->mc_d1_list + c->n_stored_bricks;
+  kf_evt_begin(c, KF_STAGE_MCUBES);
+  hipLaunchKernelGGL(k_mc_region_clear, dim3((a.n_blocks + 1 + 255) / 256), dim3(256), 0, c->stream, c->mc_block_counts, a.n_blocks + 1, c->mc_block_bits,
+                     a.n_blocks / 32 + 1, c->mc_list);
+  hipLaunchKernelGGL(k_mc_region_bricks, dim3((n_w + 255) / 256), dim3(256), 0, c->stream, a, g, sift_list, c->mc_list + 4);
+  // the persistent walkers, no more of them than the widened range has bricks (four per workgroup)
+  const unsigned walk_all = (unsigned)c->num_cus * 8u, walk = (n_w + 3) / 4 < walk_all ? (n_w + 3) / 4 : walk_all;
+  hipLaunchKernelGGL(k_mc_codes, dim3(walk), dim3(256), 0, c->stream, a);
+  McArgs s = a; s.d1_list = sift_list; s.n_d1 = c->mc_list + 4;
+  hipLaunchKernelGGL(k_mc_sift, dim3(walk), dim3(256), 0, c->stream, s);
+  mc_count_and_emit(c, a, n_tris, dropped, c->mc_list + 5);
+  kf_evt_end(c, KF_STAGE_MCUBES);
+  c->region_noop = 0;
+  return (int)hipGetLastError();
+}
+
+extern "C" int kf_marching_cubes_region(kf_ctx* c, int has_color, float thr, const int32_t lo[3], const int32_t hi[3], int flags) {
+  if (!c || !lo || !hi) return KF_ERR_ARG;
+  if (flags & ~(KF_MC_WORLD | KF_MC_TO_WORLD_SOUP)) return KF_ERR_ARG;
+  if ((flags & KF_MC_TO_WORLD_SOUP) && !(flags & KF_MC_WORLD)) return KF_ERR_ARG;       // the world soup holds world coordinates only
+  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;                     // a z-slab context, as for kf_shift_volume
+  if (has_color && !c->vol.color) return KF_ERR_STATE;
+  if (flags & KF_MC_TO_WORLD_SOUP) { if (!c->soup) return KF_ERR_STATE; }
+  else if (!c->triangles || c->max_triangles == 0) return KF_ERR_STATE;
+  return kf_mc_region_enqueue(c, has_color, thr, lo, hi, flags);
+}
+
+extern "C" int kf_region_work(kf_ctx* c, uint64_t out[2]) {
+  if (!c || !out) return KF_ERR_ARG;
+  out[0] = out[1] = 0;
+  if (!c->mc_list || c->region_noop) return 0;
+  KF_CHECK(hipMemcpyAsync(c->host_pinned, c->mc_list + 5, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  KF_CHECK(hipStreamSynchronize(c->stream));
+  out[0] = ((unsigned*)c->host_pinned)[0]; out[1] = ((unsigned*)c->host_pinned)[1];
+  return 0;
+}
+
+void kf_world_soup_free(kf_ctx* c) {
+  if (c->soup) hipFree(c->soup);
+  if (c->soup_cnt) hipFree(c->soup_cnt);
+  c->soup = nullptr; c->soup_cnt = nullptr; c->soup_cap = 0; c->stream_on = 0;
+}
+extern "C" int kf_world_soup_reserve(kf_ctx* c, uint32_t max_triangles) {
+  if (!c) return KF_ERR_ARG;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  KF_CHECK(hipStreamSynchronize(c->stream));                 // whatever still writes the old soup
+  kf_world_soup_free(c);
+  if (max_triangles == 0) return 0;
+  kf_triangle* soup = nullptr; unsigned* cnt = nullptr; uint2* recs = nullptr;
+  const bool grow_recs = c->mc_list && max_triangles > c->mc_recs_cap;      // the record list holds a cell per triangle of the larger destination
+  hipError_t e = hipMalloc((void**)&soup, (size_t)max_triangles * sizeof(kf_triangle));
+  if (e == hipSuccess) e = hipMalloc((void**)&cnt, 4 * sizeof(unsigned));
+  if (e == hipSuccess && grow_recs) e = hipMalloc((void**)&recs, (size_t)max_triangles * sizeof(uint2));
+  if (e != hipSuccess) { if (soup) hipFree(soup); if (cnt) hipFree(cnt); (void)hipGetLastError(); return (int)e; }
+  if (grow_recs) { hipFree(c->mc_recs); c->mc_recs = recs; c->mc_recs_cap = max_triangles; }
+  c->soup = soup; c->soup_cnt = cnt; c->soup_cap = max_triangles;
+  KF_CHECK(hipMemsetAsync(c->soup_cnt, 0, 4 * sizeof(unsigned), c->stream));
+  return 0;
+}
+extern "C" int kf_clear_world_soup(kf_ctx* c) {
+  if (!c) return KF_ERR_ARG;
+  if (!c->soup) return KF_ERR_STATE;
+  KF_CHECK(hipMemsetAsync(c->soup_cnt, 0, 4 * sizeof(unsigned), c->stream));
+  return 0;
+}
+extern "C" int kf_world_soup_count(kf_ctx* c, uint32_t* count, uint32_t* dropped) {
+  if (!c || !count) return KF_ERR_ARG;
+  *count = 0; if (dropped) *dropped = 0;
+  if (!c->soup) return 0;
+  KF_CHECK(hipMemcpyAsync(c->host_pinned, c->soup_cnt, 4 * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+  KF_CHECK(hipStreamSynchronize(c->stream));
+  const unsigned* h = (const unsigned*)c->host_pinned;
+  *count = h[0];
+  if (dropped) { const unsigned long long d = (unsigned long long)h[2] | ((unsigned long long)h[3] << 32); *dropped = d > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)d; }
+  return 0;
+}
+extern "C" int kf_read_world_soup(kf_ctx* c, kf_triangle* dst, uint32_t first, uint32_t count) {
+  if (!c || !dst) return KF_ERR_ARG;
+  if ((uint64_t)first + count > c->soup_cap) return KF_ERR_ARG;
+  if (count == 0) return 0;
+  KF_CHECK(hipMemcpyAsync(dst, c->soup + first, (size_t)count * sizeof(kf_triangle), hipMemcpyDeviceToHost, c->stream));
+  KF_CHECK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+// the world soup behind what the triangle buffer holds, clamped at the buffer's capacity: 18 words per triangle, a lane per word
+__global__ void __launch_bounds__(256) k_soup_append(const kf_triangle* __restrict__ soup, const unsigned* __restrict__ n_soup, kf_triangle* __restrict__ tris,
+                                                    const unsigned* __restrict__ n_tris, unsigned max_tris) {
+  const unsigned held = *n_tris, room = max_tris - held, n = *n_soup < room ? *n_soup : room;
+  const size_t words = (size_t)n * 18u;
+  const unsigned* src = reinterpret_cast<const unsigned*>(soup);
+  unsigned* dst = reinterpret_cast<unsigned*>(tris + held);
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < words; i += (size_t)gridDim.x * 256u) dst[i] = src[i];
+}
+__global__ void k_soup_append_finish(const unsigned* n_soup, unsigned* n_tris, unsigned max_tris) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) { const unsigned long long t = (unsigned long long)*n_tris + *n_soup; *n_tris = (unsigned)(t > max_tris ? max_tris : t); }
+}
+extern "C" int kf_append_world_soup(kf_ctx* c) {
+  if (!c) return KF_ERR_ARG;
+  if (!c->soup || !c->triangles || c->max_triangles == 0) return KF_ERR_STATE;
+  hipLaunchKernelGGL(k_soup_append, dim3((unsigned)c->num_cus * 8u), dim3(256), 0, c->stream, (const kf_triangle*)c->soup, (const unsigned*)c->soup_cnt, c->triangles,
+                     (const unsigned*)&c->counters->n_triangles, c->max_triangles);
+  hipLaunchKernelGGL(k_soup_append_finish, dim3(1), dim3(64), 0, c->stream, (const unsigned*)c->soup_cnt, &c->counters->n_triangles, c->max_triangles);
+  return (int)hipGetLastError();
+}
+extern "C" int kf_set_stream_out(kf_ctx* c, int on, int has_color, float thr) {
+  if (!c) return KF_ERR_ARG;
+  if (!on) { c->stream_on = 0; return 0; }
+  if (!c->soup) return KF_ERR_STATE;
+  if (has_color && !c->vol.color) return KF_ERR_STATE;
+  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;
+  c->stream_on = 1; c->stream_color = has_color ? 1 : 0; c->stream_thr = thr;
+  return 0;
 }
 
 extern "C" int kf_clear_triangles(kf_ctx* c) {

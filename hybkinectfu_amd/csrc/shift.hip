@@ -61,6 +61,31 @@ __global__ void k_shift_pose(KfTrackState* st, int dx, int dy, int dz, float cel
   for (int i = 0; i < 16; ++i) { st->cur[0][i] = st->pose[i]; st->last_inv[i] = st->pose_inv[i]; }
 }
 
+// Stream-out (kf_set_stream_out): the cells whose 27 voxels include a voxel that is about to leave, as up to three disjoint boxes -- the x strip
+// in full, the y strip without the x strip, the z strip without both.  Along one axis with d > 0 voxels < d leave: cells [0, d + 1); with d < 0
+// cells [res + d - 1, res).  The same few lines as hkf_departing_boxes of the host library (this library does not link it).
+static int departing_boxes(const int32_t d[3], int res, int32_t lo[3][3], int32_t hi[3][3]) {
+  int32_t slo[3], shi[3], klo[3], khi[3];                  // per axis: the strip, and what is left of the axis without it
+  for (int k = 0; k < 3; ++k) {
+    const int64_t dd = d[k];
+    if (dd > 0) { slo[k] = 0; shi[k] = (int32_t)(dd + 1 > res ? res : dd + 1); klo[k] = shi[k]; khi[k] = res; }
+    else if (dd < 0) { shi[k] = res; slo[k] = (int32_t)(res + dd - 1 < 0 ? 0 : res + dd - 1); klo[k] = 0; khi[k] = slo[k]; }
+    else { slo[k] = shi[k] = 0; klo[k] = 0; khi[k] = res; }
+  }
+  int n = 0;
+  for (int k = 0; k < 3; ++k) {
+    if (slo[k] >= shi[k]) continue;
+    bool empty = false;
+    for (int j = 0; j < 3; ++j) {
+      lo[n][j] = j < k ? klo[j] : (j == k ? slo[j] : 0);
+      hi[n][j] = j < k ? khi[j] : (j == k ? shi[j] : res);
+      if (lo[n][j] >= hi[n][j]) empty = true;
+    }
+    if (!empty) ++n;
+  }
+  return n;
+}
+
 extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
   if (!c) return KF_ERR_ARG;
   if ((dx % KF_BRICK) || (dy % KF_BRICK) || (dz % KF_BRICK)) return KF_ERR_ARG;
@@ -74,6 +99,14 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
   // the bookkeeping of a wholesale change, in kf_resize_slab's order
   { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
   { const int fs = kf_flush_pending(c); if (fs) return fs; }      // the words become 0, 1 or KF_PEND_SAT: they describe voxels that move verbatim
+  if (c->stream_on && c->soup) {                                  // before anything moves: the surface that can never be extracted again -> the world soup
+    int32_t lo[3][3], hi[3][3];
+    const int nbox = departing_boxes(d, v.res, lo, hi);
+    for (int b = 0; b < nbox; ++b) {
+      const int rs = kf_mc_region_enqueue(c, c->stream_color, c->stream_thr, lo[b], hi[b], KF_MC_WORLD | KF_MC_TO_WORLD_SOUP);
+      if (rs) return rs;
+    }
+  }
   ++c->vol_flags_serial;
   c->wgt0_valid = 0;
   c->model_pyr_ok = 0;                                            // the model maps show the old window: the caller raycasts before the next kf_*_track

@@ -120,6 +120,11 @@ int hkf_app_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
 int hkf_app_shift_volume(int dx, int dy, int dz) { if (!g_app) return -1; return g_app->shiftVolume(dx, dy, dz) ? 1 : 0; }
 int hkf_app_volume_origin(int out3[3]) { if (!g_app) return -1; g_app->volumeOrigin(out3); return 0; }
 int hkf_app_set_recentre(float dist) { if (!g_app) return -1; AppParams::instance()->_volume_params.fRecentreDist = dist; return 0; }
+// AppParams::_volume_params.nStreamMeshTriangles (call AFTER hkf_app_init, which restores the defaults; 0 = off): HybKinectfu::setStreamMesh.
+// hkf_app_set_stream_mesh: 0 ok, -1 without an application, -2 refused (CudaDeviceDataMan::lastError has the status).  hkf_app_world_soup_count: the
+// triangles streamed out so far, -1 without an application
+int hkf_app_set_stream_mesh(unsigned max_triangles) { if (!g_app) return -1; return g_app->setStreamMesh(max_triangles) ? 0 : -2; }
+int hkf_app_world_soup_count() { if (!g_app) return -1; return (int)g_app->worldSoupCount(); }
 int hkf_app_generate_mesh() { if (!g_mesh) return -1; g_mesh->generateMesh(); return (int)g_mesh->triangleCount(); }
 int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
   if (!g_mesh) return -1;

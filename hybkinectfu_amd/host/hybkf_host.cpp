@@ -18,7 +18,7 @@ void AppParams::setDefaults(unsigned res, float size) {
   _depth_prepocess_params = {4.0f, 0.3f, 0.03f, 2.0f};                  // max, min, sigma depth, sigma pixel
   _icp_params = {3, 0.1f, 0.1f, 0.3f, 0.3f};
   _sdf_tracker_params = {6, 0.3f, 0.3f};
-  _volume_params = {res, size, 128.0f, 0.0f};
+  _volume_params = {res, size, 128.0f, 0.0f, 0u};
   _integrate_params = {0.05f, 2.0f};
   _raycast_params.fRayIncrement = 0.7f * _integrate_params.fSdfTruncation;  // AppParamsProducer.cpp:113-117
   _marchingcube_params.uMaxTriangles = 6500000;
@@ -294,6 +294,7 @@ bool HybKinectfu::init() {                                     // :28-61
                               -AppParams::instance()->_depth_prepocess_params.fMinTrunc);
   if (!_camera_pose_finder->init(camera_pose0)) return false;
   _inited = true;
+  if (AppParams::instance()->_volume_params.nStreamMeshTriangles > 0 && !setStreamMesh(AppParams::instance()->_volume_params.nStreamMeshTriangles)) _inited = false;
   return _inited;
 }
 
@@ -402,6 +403,25 @@ bool HybKinectfu::shiftVolume(int dx, int dy, int dz) {
   kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
   return 0 == dm->check(kf_raycast_volume(dm->ctx(), p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
                                           p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
+}
+static float mesh_threshold() {                                // MeshGeneratorMarchingcube.cpp:23-29
+  const AppParams* p = AppParams::instance();
+  return 300 * p->_volume_params.fVolumeMeterSize / p->_volume_params.nResolution;
+}
+bool HybKinectfu::setStreamMesh(unsigned max_triangles) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  p->_volume_params.nStreamMeshTriangles = max_triangles;
+  if (dm->check(kf_world_soup_reserve(dm->ctx(), max_triangles))) { p->_volume_params.nStreamMeshTriangles = 0; return false; }
+  if (max_triangles == 0) return true;
+  if (dm->check(kf_set_stream_out(dm->ctx(), 1, p->_switch_params.useRGBData, mesh_threshold()))) { p->_volume_params.nStreamMeshTriangles = 0; return false; }
+  return true;
+}
+unsigned HybKinectfu::worldSoupCount() {
+  uint32_t n = 0; CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (dm->ctx()) dm->check(kf_world_soup_count(dm->ctx(), &n, nullptr));
+  return n;
 }
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();
@@ -578,6 +598,13 @@ bool MeshData::saveToFile(const std::string& filename) const {  // MeshIO.h:50-7
 void MeshGeneratorMarchingcube::generateMesh() {                // :23-29
   const AppParams* p = AppParams::instance();
   CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  _world = false;
+  if (p->_volume_params.nStreamMeshTriangles > 0) {           // streaming: [world soup, the current window], everything in world coordinates
+    const int32_t lo[3] = {0, 0, 0}, hi[3] = {(int32_t)p->_volume_params.nResolution, (int32_t)p->_volume_params.nResolution, (int32_t)p->_volume_params.nResolution};
+    if (dm->check(kf_clear_triangles(dm->ctx())) || dm->check(kf_append_world_soup(dm->ctx()))) return;
+    _world = 0 == dm->check(kf_marching_cubes_region(dm->ctx(), p->_switch_params.useRGBData, mesh_threshold(), lo, hi, KF_MC_WORLD));
+    return;
+  }
   dm->check(kf_marching_cubes(dm->ctx(), p->_switch_params.useRGBData, 300 * p->_volume_params.fVolumeMeterSize / p->_volume_params.nResolution));
 }
 unsigned MeshGeneratorMarchingcube::triangleCount() {
@@ -634,7 +661,7 @@ bool MeshGeneratorMarchingcube::saveMesh(const std::string& filename) {   // :61
     if (!copyTrianglesToCPU()) return false;
     weldMesh();
   }
-  {                                                              // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
+  if (!_world) {                                                 // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
     int32_t o[3] = {0, 0, 0};
     CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
     if (dm->ctx() && kf_volume_origin(dm->ctx(), o) == 0)

@@ -20,7 +20,10 @@ struct RayCasterParams { float fRayIncrement; };
 struct DepthPrepocessParams { float fMaxTrunc, fMinTrunc, fSigmaDepth, fSigmaPixel; };
 // fRecentreDist (not in the reference): the moving volume's policy.  0 (default): off, the cube stays where init put it.  > 0: after a tracked
 // processNewFrame whose focus point lies farther than this (metres, any axis) from the volume's centre, the window is shifted towards it by whole bricks
-struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; };
+// nStreamMeshTriangles (not in the reference): 0 (default): off.  > 0: HybKinectfu::init reserves a world soup of that many triangles and switches
+// stream-out on (kf_set_stream_out with the mesh generator's colour switch and threshold): every shift first extracts the surface that is about to
+// leave, and MeshGeneratorMarchingcube::generateMesh hands out [world soup, current window], all in world coordinates
+struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; unsigned nStreamMeshTriangles; };
 struct MarchingcubeParams { unsigned uMaxTriangles; };
 struct IntegrateParams { float fSdfTruncation, fMaxIntegrateDist; };
 struct SwitchParams { bool recordRGBD, recordTrajectory, useRGBData, colorAngleWeight, useDatasetRGBD, useTrajFromFile, useSdfTracker; };
@@ -182,6 +185,10 @@ void hkf_recentre_shift(const float pose[16], float size_m, uint32_t res, float 
 // volume coordinates -> world coordinates: + (float)origin_vox * cell on the pose's translation / on n xyz positions.  A zero origin leaves every bit.
 void hkf_world_pose(float pose[16], const int32_t origin_vox[3], float cell);
 void hkf_world_positions(float* xyz, size_t n, const int32_t origin_vox[3], float cell);
+// The cells that a shift by d voxels makes unextractable for good (their 27 voxels include one that leaves), as up to three disjoint half-open boxes
+// lo[b] <= (x, y, z) < hi[b] in the order the stream-out emits them: the x strip in full, the y strip without it, the z strip without both.
+// Returns the number of (non-empty) boxes written; 0 for a zero shift.
+int hkf_departing_boxes(const int32_t d[3], uint32_t res, int32_t lo[3][3], int32_t hi[3][3]);
 }
 
 // ---- src/TrajectoryRecorder.{h,cpp}: TUM-format trajectory writer ---------------------------------------------------------------------------------
@@ -255,6 +262,10 @@ public:
   // coordinates (volume coordinates + origin * cell); with a zero origin they are what they always were, byte for byte.
   bool shiftVolume(int dx, int dy, int dz);
   void volumeOrigin(int out[3]);
+  // Streaming the departing surface (AppParams::_volume_params.nStreamMeshTriangles; init calls this when it is > 0): reserves the world soup and
+  // switches stream-out on; 0 frees the soup and switches it off.  worldSoupCount: the triangles the soup holds (blocking).
+  bool setStreamMesh(unsigned max_triangles);
+  unsigned worldSoupCount();
 private:
   bool recentre();
   Mat44 worldPose(const Mat44& pose);
@@ -305,4 +316,5 @@ protected:
   bool weldOnDevice();                                                       // :61-86 without the 72 bytes per triangle crossing to the host
   MeshData _meshes;
   bool _device_weld = false;
+  bool _world = false;            // the triangles of the last generateMesh are in world coordinates already (streaming on): saveMesh adds no origin
 };

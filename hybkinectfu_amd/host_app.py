@@ -119,6 +119,20 @@ class App:
         if self.h.hkf_app_set_recentre(C.c_float(dist)) != 0:
             raise K.KfError("hkf_app_set_recentre: no application")
 
+    def set_stream_mesh(self, max_triangles):
+        """AppParams::_volume_params.nStreamMeshTriangles: reserve a world soup of that many triangles and stream the departing surface into it at
+        every shift; generate_mesh then hands out [world soup, current window] in world coordinates (0: off, the default)"""
+        r = self.h.hkf_app_set_stream_mesh(C.c_uint(int(max_triangles)))
+        if r != 0:
+            raise K.KfError("hkf_app_set_stream_mesh failed: %d" % r)
+
+    def world_soup_count(self):
+        """HybKinectfu::worldSoupCount: triangles streamed out so far"""
+        r = self.h.hkf_app_world_soup_count()
+        if r < 0:
+            raise K.KfError("hkf_app_world_soup_count: no application")
+        return r
+
     def close(self):
         self.h.hkf_app_shutdown()
 
@@ -282,6 +296,17 @@ def mesh_save(which, filename):
 
 def app_mesh():
     return _mesh_read(1)
+
+
+def departing_boxes(d, res):
+    """hkf_departing_boxes: the disjoint cell boxes [(lo, hi), ...] (x, y, z; half-open) that a shift by d voxels makes unextractable, in the order
+    the stream-out emits them; GPU-free"""
+    h = load()
+    dd = (C.c_int32 * 3)(*[int(x) for x in d])
+    lo, hi = ((C.c_int32 * 3) * 3)(), ((C.c_int32 * 3) * 3)()
+    h.hkf_departing_boxes.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
+    n = h.hkf_departing_boxes(dd, C.c_uint32(res), lo, hi)
+    return [(tuple(int(x) for x in lo[b]), tuple(int(x) for x in hi[b])) for b in range(n)]
 
 
 def recentre_shift(pose, size, res, dist):

@@ -90,6 +90,8 @@ RC_OUT_MAPS, RC_OUT_T, RC_OUT_TA, RC_OUT_TA_SPEC = 0, 1, 2, 3          # kf_rayc
 VERTEX_DTYPE = np.dtype([("pos", "<f4", (3,)), ("color", "<f4", (3,))])
 TRI_DTYPE = np.dtype([("v", VERTEX_DTYPE, (3,))])
 
+MC_WORLD, MC_TO_WORLD_SOUP = 1, 2                                     # kf_marching_cubes_region: flags
+
 MAP_RAW_DEPTH, MAP_TRUNCED_DEPTH, MAP_FILTERED_DEPTH = 0, 1, 2
 MAP_NEW_VERTICES, MAP_NEW_NORMALS, MAP_MODEL_VERTICES, MAP_MODEL_NORMALS = 3, 4, 5, 6
 MAP_RAW_RGB, MAP_RAYCAST_RGB = 7, 8
@@ -116,6 +118,8 @@ SYMBOLS = [
     "kf_render_view", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
     "kf_view_slab_cross", "kf_view_slab_normals", "kf_view_from_rays",
     "kf_shift_volume", "kf_volume_origin",
+    "kf_marching_cubes_region", "kf_region_work", "kf_world_soup_reserve", "kf_world_soup_count", "kf_read_world_soup", "kf_clear_world_soup",
+    "kf_append_world_soup", "kf_set_stream_out",
 ]
 
 
@@ -145,6 +149,14 @@ def load():
         _lib.kf_view_device.restype = C.c_void_p
         _lib.kf_shift_volume.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         _lib.kf_volume_origin.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        _lib.kf_marching_cubes_region.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
+        _lib.kf_region_work.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
+        _lib.kf_world_soup_reserve.argtypes = [C.c_void_p, C.c_uint32]
+        _lib.kf_world_soup_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.kf_read_world_soup.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32]
+        _lib.kf_clear_world_soup.argtypes = [C.c_void_p]
+        _lib.kf_append_world_soup.argtypes = [C.c_void_p]
+        _lib.kf_set_stream_out.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
     return _lib
 
 
@@ -598,6 +610,47 @@ class Context:
         """the window moves by (dx, dy, dz) voxels, multiples of 8: contents, deferred weights and the device-resident pose move with it, in place
         and asynchronously; the model maps are stale until the next raycast (kf_shift_volume)"""
         _chk(self.lib.kf_shift_volume(self.h, int(dx), int(dy), int(dz)), "kf_shift_volume")
+
+    def marching_cubes_region(self, thr, lo, hi, has_color=False, flags=0):
+        """kf_marching_cubes for the cells lo <= (x, y, z) < hi only, appended to the triangle buffer (flags: MC_WORLD world coordinates,
+        MC_TO_WORLD_SOUP into the world soup instead); its cost follows the box (kf_marching_cubes_region)"""
+        l, h = (C.c_int32 * 3)(*[int(x) for x in lo]), (C.c_int32 * 3)(*[int(x) for x in hi])
+        _chk(self.lib.kf_marching_cubes_region(self.h, int(has_color), thr, l, h, int(flags)), "kf_marching_cubes_region")
+
+    def region_work(self):
+        """(bricks whose voxels the class pass read, 256-cell blocks listed) of the last region extraction (kf_region_work)"""
+        out = (C.c_uint64 * 2)()
+        _chk(self.lib.kf_region_work(self.h, out), "kf_region_work")
+        return int(out[0]), int(out[1])
+
+    def world_soup_reserve(self, max_triangles):
+        """(re)allocate and clear the world soup; 0 frees it (kf_world_soup_reserve)"""
+        _chk(self.lib.kf_world_soup_reserve(self.h, int(max_triangles)), "kf_world_soup_reserve")
+
+    def world_soup_count(self):
+        """(triangles held, triangles that did not fit since the last clear)"""
+        n, d = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_world_soup_count(self.h, C.byref(n), C.byref(d)), "kf_world_soup_count")
+        return n.value, d.value
+
+    def world_soup(self):
+        """the world soup's triangles (lib.TRI_DTYPE), in world coordinates"""
+        n, _ = self.world_soup_count()
+        out = np.zeros(n, dtype=TRI_DTYPE)
+        if n:
+            _chk(self.lib.kf_read_world_soup(self.h, _p(out), 0, n), "kf_read_world_soup")
+        return out
+
+    def clear_world_soup(self):
+        _chk(self.lib.kf_clear_world_soup(self.h), "kf_clear_world_soup")
+
+    def append_world_soup(self):
+        """device to device: the world soup behind what the triangle buffer holds, clamped (kf_append_world_soup)"""
+        _chk(self.lib.kf_append_world_soup(self.h), "kf_append_world_soup")
+
+    def set_stream_out(self, on, thr=0.0, has_color=False):
+        """on: every shift_volume first extracts the surface that is about to leave into the world soup (kf_set_stream_out)"""
+        _chk(self.lib.kf_set_stream_out(self.h, int(bool(on)), int(has_color), thr), "kf_set_stream_out")
 
     def volume_origin(self):
         """(x, y, z): the sum of all shifts since the context was created / reset, in voxels (kf_volume_origin)"""

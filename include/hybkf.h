@@ -444,6 +444,42 @@ int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /*
 int kf_shift_volume(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz);
 int kf_volume_origin(kf_ctx* ctx, int32_t origin_vox[3]);
 
+/* Streaming the departing surface into a world mesh (no reference counterpart).  kf_shift_volume overwrites what leaves the window; these
+ * entry points keep its surface: a marching cubes limited to a box of cells, and a second, context-owned triangle buffer in WORLD coordinates
+ * (world position = volume position + origin * cell, see kf_volume_origin) that outlives the window the triangles were extracted under.
+ * kf_marching_cubes_region: exactly the triangles kf_marching_cubes emits for the cells lo <= (x, y, z) < hi (cells, half-open, any integers,
+ *   clamped to [0, resolution)) -- every float and colour byte the same, in the canonical order (z, y, x, k) restricted to the box --, appended
+ *   to what the destination holds and clamped at its capacity.  An empty or inverted box is a no-op that returns 0.  Its cost follows the box:
+ *   only the bricks the box touches, widened by one brick, are tested and classified, and the 256-cell blocks are numbered inside the box.
+ *   flags: KF_MC_WORLD -- every position component i becomes p + (float)origin[i] * cell (one fp32 multiply, one add: hkf_world_positions'
+ *   expression; a zero origin leaves every bit); KF_MC_TO_WORLD_SOUP -- the destination is the world soup instead of the triangle buffer
+ *   (KF_ERR_ARG without KF_MC_WORLD, KF_ERR_STATE without a reserved soup).  KF_ERR_ARG: NULL context or box, unknown flag bits, a z-slab
+ *   context (one that does not store the whole volume).  KF_ERR_STATE: has_color without a colour plane, no destination.  Asynchronous.
+ * kf_region_work: what the last kf_marching_cubes_region (or the last box of a streaming kf_shift_volume) visited -- out[0] = bricks whose voxels
+ *   its class pass read, out[1] = 256-cell blocks listed.  Zeros after a no-op.  Blocking.
+ * kf_world_soup_reserve: (re)allocates the world soup for max_triangles and clears it; 0 frees it (and switches stream-out off).  Blocking.
+ * kf_world_soup_count: triangles held, and (dropped, may be NULL) the triangles that did not fit, summed since the last clear (saturating).
+ *   Zeros without a soup.  Blocking.  kf_read_world_soup: as kf_read_triangles.  kf_clear_world_soup: both counts to zero (KF_ERR_STATE
+ *   without a soup); kf_reset_volume does the same.
+ * kf_append_world_soup: device to device, the world soup behind what the triangle buffer holds, clamped at max_triangles.  Asynchronous.
+ * kf_set_stream_out: on != 0 -- from now on kf_shift_volume first extracts, with these marching-cubes parameters, into the world soup every
+ *   cell whose 27 voxels include a voxel that is about to leave: along one axis with shift d > 0 the cells [0, d + 1), with d < 0 the cells
+ *   [resolution + d - 1, resolution); over several axes the union as disjoint boxes in this order -- the x strip in full, the y strip without
+ *   the x strip, the z strip without both --, each in canonical order.  Exactly these cells can never be extracted again (cell d becomes cell 0,
+ *   whose lookups need voxel -1; cell d + 1 keeps its 27 voxels and is left for later), so a run of shifts in one direction loses nothing and
+ *   emits nothing twice.  A window that comes back over old ground re-fuses it and streams it again: the soup then holds that surface twice.
+ *   The volume, the pose and every later frame are what they are without stream-out, bit for bit.  KF_ERR_STATE without a reserved soup or
+ *   with has_color on a context without a colour plane; KF_ERR_ARG on a z-slab context. */
+enum { KF_MC_WORLD = 1, KF_MC_TO_WORLD_SOUP = 2 };
+int kf_marching_cubes_region(kf_ctx* ctx, int has_color, float threshold_marchingcube, const int32_t lo[3], const int32_t hi[3], int flags);
+int kf_region_work(kf_ctx* ctx, uint64_t out[2]);
+int kf_world_soup_reserve(kf_ctx* ctx, uint32_t max_triangles);
+int kf_world_soup_count(kf_ctx* ctx, uint32_t* count, uint32_t* dropped);
+int kf_read_world_soup(kf_ctx* ctx, kf_triangle* dst, uint32_t first, uint32_t count);
+int kf_clear_world_soup(kf_ctx* ctx);
+int kf_append_world_soup(kf_ctx* ctx);
+int kf_set_stream_out(kf_ctx* ctx, int on, int has_color, float threshold_marchingcube);
+
 /* test hook: counts fp32 quotients where the kernels' split exact-division helper differs from the compiler's `/` (must be 0) */
 int kf_selftest_div(kf_ctx* ctx, unsigned n, unsigned seed, int mode, unsigned* mismatches);
 
