@@ -124,6 +124,7 @@ extern "C" int kf_destroy(kf_ctx* c) {
   for (void* p : ptrs) if (p) hipFree(p);
   kf_weld_free(c);
   kf_world_soup_free(c);
+  kf_brick_store_free(c);
   if (c->up_stream) { hipStreamSynchronize(c->up_stream); hipStreamDestroy(c->up_stream); }
   for (int i = 0; i < KF_UP_SLOTS; ++i) {
     if (c->up_host[i]) hipHostFree(c->up_host[i]);
@@ -256,6 +257,7 @@ extern "C" int kf_reset_volume(kf_ctx* c) {
   c->wgt0_base = 0; c->wgt0_valid = 1;                       // nothing observed; the shards were zeroed with the counters
   c->origin_vox[0] = c->origin_vox[1] = c->origin_vox[2] = 0; // the window is back on the first cube (kf_shift_volume)
   if (c->soup) KF_CHECK(hipMemsetAsync(c->soup_cnt, 0, 4 * sizeof(unsigned), c->stream));   // ... and the world soup describes a world that is gone
+  if (c->bstore.max_bricks) { const int bs = kf_brick_store_reset(c); if (bs) return bs; }      // ... so does the brick store
   return 0;
 }
 

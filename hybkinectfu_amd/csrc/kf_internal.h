@@ -138,6 +138,20 @@ __device__ __forceinline__ unsigned kf_new_voxels(bool count, bool u0, float w0,
   return count ? (unsigned)__popcll(a) + (unsigned)__popcll(b) : 0u;
 }
 
+// The brick store (brickstore.hip; kf_brick_store_reserve ...): a sparse archive of the bricks that have left the moving window, keyed by world brick
+// coordinate (brick_key.h).  Slot i holds one brick verbatim -- its 4 KiB of (tsdf, weight), its 2 KiB of colour on a context with a colour plane, its
+// deferred-weight word -- and its key; slots are handed out in order and never freed, so [0, cnt->held) are the entries.  tkey / tslot: an open-addressing
+// hash table (linear probing, `mask + 1` entries, a power of two >= 2 * max_bricks; KF_BRICK_KEY_EMPTY marks a free entry) from key to slot.  An entry is
+// claimed only once its brick has a slot, so the table never holds more than max_bricks keys and every probe ends at a free entry.
+struct KfBrickStoreCounts { unsigned held, pad_; unsigned long long dropped, restored; };
+struct KfBrickStore {
+  float2* tw; uchar4* color; unsigned long long* pend; unsigned long long* key;   // per slot (color: null without a colour plane)
+  unsigned long long* tkey; unsigned* tslot;                                       // per table entry
+  KfBrickStoreCounts* cnt;
+  unsigned max_bricks, mask;                                                       // max_bricks == 0: no store
+};
+#define KF_BRICK_NO_SLOT 0xFFFFFFFFu
+
 #define KF_UP_SLOTS 3                  // host-upload slots: the current frame and up to two staged ahead of it
 struct kf_ctx {
   kf_config cfg;
@@ -249,6 +263,7 @@ struct kf_ctx {
   // the moving volume (shift.hip; kf_shift_volume, kf_volume_origin): voxel (0, 0, 0) of the window in the voxels of the first cube -- the sum of all shifts
   // since kf_create / kf_reset_volume.  Host bookkeeping only: no kernel reads it.
   int32_t origin_vox[3];
+  KfBrickStore bstore;           // the brick store (brickstore.hip): absent (max_bricks == 0) until kf_brick_store_reserve
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,
@@ -657,3 +672,9 @@ int kf_upload_wait_for(kf_ctx* ctx, const uint16_t* dev_mm);   // dev_mm is abou
 // (mcubes.hip) kf_marching_cubes_region past its argument checks: what kf_shift_volume's stream-out enqueues for each departing box
 int kf_mc_region_enqueue(kf_ctx* ctx, int has_color, float thr, const int32_t lo[3], const int32_t hi[3], int flags);
 void kf_world_soup_free(kf_ctx* ctx);    // (mcubes.hip) for kf_destroy: the caller has synchronised the stream
+// (brickstore.hip) the brick store's part of kf_shift_volume, asynchronous on the context's stream: s = the shift in bricks (not clamped), origin_vox = the window's
+// origin the keys are formed with -- the old one for the eviction (before anything moves), the new one for the restore (after the move)
+int kf_brick_store_evict(kf_ctx* ctx, const int s[3], const int32_t origin_vox[3]);
+int kf_brick_store_restore(kf_ctx* ctx, const int s[3], const int32_t origin_vox[3]);
+int kf_brick_store_reset(kf_ctx* ctx);   // no entries, counts zero (kf_brick_store_clear, kf_reset_volume); asynchronous
+void kf_brick_store_free(kf_ctx* ctx);   // for kf_destroy and kf_brick_store_reserve: the caller has synchronised the stream

@@ -7,7 +7,11 @@
 // is overwritten (ascending for s > 0, descending for s < 0).  Inside one launch source and destination plane differ, so no workgroup reads
 // what another writes; stream order does the rest.  The pass that moves a brick also sees all of its voxels, so it rebuilds the brick's
 // flags, its has-negative bit and the skip tables on the way: no second sweep of the volume.
+//
+// With a brick store reserved (brickstore.hip) the observed bricks that leave are copied into the store before anything moves, and the bricks that
+// enter are looked up in it after the move: two more launches around the ones above, which stay as they are.
 #include "kf_internal.h"
+#include "brick_key.h"
 #include <stdint.h>
 
 // One workgroup iteration moves one brick of brick plane `plane` (perpendicular to `axis`: 0 x, 1 y, 2 z): 256 lanes x one float4 (two voxels),
@@ -95,6 +99,13 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
   const int32_t d[3] = {dx, dy, dz};
   int64_t org[3];
   for (int k = 0; k < 3; ++k) { org[k] = (int64_t)c->origin_vox[k] + d[k]; if (org[k] > INT32_MAX || org[k] < INT32_MIN) return KF_ERR_ARG; }
+  const bool store = c->bstore.max_bricks != 0;
+  if (store) {                                                    // every brick of the old and of the new window needs a key (brick_key.h): refused before anything is touched
+    for (int k = 0; k < 3; ++k) {
+      const int64_t b_old = c->origin_vox[k] / KF_BRICK, b_new = org[k] / KF_BRICK;
+      if (!kf_brick_key_in_range(b_old) || !kf_brick_key_in_range(b_old + v.nb - 1) || !kf_brick_key_in_range(b_new) || !kf_brick_key_in_range(b_new + v.nb - 1)) return KF_ERR_ARG;
+    }
+  }
   KF_CHECK(hipSetDevice(c->cfg.device));
   // the bookkeeping of a wholesale change, in kf_resize_slab's order
   { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
@@ -107,6 +118,8 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
       if (rs) return rs;
     }
   }
+  const int sb[3] = {d[0] / KF_BRICK, d[1] / KF_BRICK, d[2] / KF_BRICK};   // the shift in bricks, not clamped: the store's passes clamp their boxes themselves
+  if (store) { const int es = kf_brick_store_evict(c, sb, c->origin_vox); if (es) return es; }   // the flushed voxels and words of what leaves, keyed under the OLD origin
   ++c->vol_flags_serial;
   c->wgt0_valid = 0;
   c->model_pyr_ok = 0;                                            // the model maps show the old window: the caller raycasts before the next kf_*_track
@@ -125,6 +138,7 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
     else hipLaunchKernelGGL(k_shift_bricks<false>, grid, block, 0, c->stream, v, axis, plane, s[0], s[1], s[2]);
   }
   for (int k = 0; k < 3; ++k) c->origin_vox[k] = (int32_t)org[k];
+  if (store) { const int rs = kf_brick_store_restore(c, sb, c->origin_vox); if (rs) return rs; }   // what enters, looked up under the NEW origin
   return (int)hipGetLastError();
 }
 

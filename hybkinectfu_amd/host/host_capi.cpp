@@ -125,6 +125,17 @@ int hkf_app_set_recentre(float dist) { if (!g_app) return -1; AppParams::instanc
 // triangles streamed out so far, -1 without an application
 int hkf_app_set_stream_mesh(unsigned max_triangles) { if (!g_app) return -1; return g_app->setStreamMesh(max_triangles) ? 0 : -2; }
 int hkf_app_world_soup_count() { if (!g_app) return -1; return (int)g_app->worldSoupCount(); }
+// AppParams::_volume_params.nBrickStoreBricks (call AFTER hkf_app_init, which restores the defaults; 0 = off): HybKinectfu::setBrickStore.
+// hkf_app_set_brick_store: 0 ok, -1 without an application, -2 refused.  hkf_app_brick_store_count: out3 = bricks held, dropped, restored; -2 when the
+// read failed
+int hkf_app_set_brick_store(unsigned max_bricks) { if (!g_app) return -1; return g_app->setBrickStore(max_bricks) ? 0 : -2; }
+int hkf_app_brick_store_count(uint64_t out3[3]) {
+  if (!g_app || !out3) return -1;
+  unsigned held = 0; uint64_t dropped = 0, restored = 0;
+  if (!g_app->brickStoreCounts(held, dropped, restored)) return -2;
+  out3[0] = held; out3[1] = dropped; out3[2] = restored;
+  return 0;
+}
 int hkf_app_generate_mesh() { if (!g_mesh) return -1; g_mesh->generateMesh(); return (int)g_mesh->triangleCount(); }
 int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
   if (!g_mesh) return -1;

@@ -18,7 +18,7 @@ void AppParams::setDefaults(unsigned res, float size) {
   _depth_prepocess_params = {4.0f, 0.3f, 0.03f, 2.0f};                  // max, min, sigma depth, sigma pixel
   _icp_params = {3, 0.1f, 0.1f, 0.3f, 0.3f};
   _sdf_tracker_params = {6, 0.3f, 0.3f};
-  _volume_params = {res, size, 128.0f, 0.0f, 0u};
+  _volume_params = {res, size, 128.0f, 0.0f, 0u, 0u};
   _integrate_params = {0.05f, 2.0f};
   _raycast_params.fRayIncrement = 0.7f * _integrate_params.fSdfTruncation;  // AppParamsProducer.cpp:113-117
   _marchingcube_params.uMaxTriangles = 6500000;
@@ -295,6 +295,7 @@ bool HybKinectfu::init() {                                     // :28-61
   if (!_camera_pose_finder->init(camera_pose0)) return false;
   _inited = true;
   if (AppParams::instance()->_volume_params.nStreamMeshTriangles > 0 && !setStreamMesh(AppParams::instance()->_volume_params.nStreamMeshTriangles)) _inited = false;
+  if (_inited && AppParams::instance()->_volume_params.nBrickStoreBricks > 0 && !setBrickStore(AppParams::instance()->_volume_params.nBrickStoreBricks)) _inited = false;
   return _inited;
 }
 
@@ -422,6 +423,23 @@ unsigned HybKinectfu::worldSoupCount() {
   uint32_t n = 0; CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
   if (dm->ctx()) dm->check(kf_world_soup_count(dm->ctx(), &n, nullptr));
   return n;
+}
+bool HybKinectfu::setBrickStore(unsigned max_bricks) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  p->_volume_params.nBrickStoreBricks = max_bricks;
+  if (dm->check(kf_brick_store_reserve(dm->ctx(), max_bricks))) { p->_volume_params.nBrickStoreBricks = 0; return false; }
+  return true;
+}
+bool HybKinectfu::brickStoreCounts(unsigned& held, uint64_t& dropped, uint64_t& restored) {
+  held = 0; dropped = 0; restored = 0;
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  if (!dm->ctx()) return false;
+  uint32_t h = 0;
+  if (dm->check(kf_brick_store_count(dm->ctx(), &h, &dropped, &restored))) return false;
+  held = h;
+  return true;
 }
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();

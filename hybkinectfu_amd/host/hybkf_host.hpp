@@ -23,7 +23,9 @@ struct DepthPrepocessParams { float fMaxTrunc, fMinTrunc, fSigmaDepth, fSigmaPix
 // nStreamMeshTriangles (not in the reference): 0 (default): off.  > 0: HybKinectfu::init reserves a world soup of that many triangles and switches
 // stream-out on (kf_set_stream_out with the mesh generator's colour switch and threshold): every shift first extracts the surface that is about to
 // leave, and MeshGeneratorMarchingcube::generateMesh hands out [world soup, current window], all in world coordinates
-struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; unsigned nStreamMeshTriangles; };
+// nBrickStoreBricks (not in the reference): 0 (default): off.  > 0: HybKinectfu::init reserves a brick store of that many bricks
+// (kf_brick_store_reserve): every shift keeps the observed bricks that leave the window and restores the ones it finds when the window returns
+struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; unsigned nStreamMeshTriangles; unsigned nBrickStoreBricks; };
 struct MarchingcubeParams { unsigned uMaxTriangles; };
 struct IntegrateParams { float fSdfTruncation, fMaxIntegrateDist; };
 struct SwitchParams { bool recordRGBD, recordTrajectory, useRGBData, colorAngleWeight, useDatasetRGBD, useTrajFromFile, useSdfTracker; };
@@ -266,6 +268,10 @@ public:
   // switches stream-out on; 0 frees the soup and switches it off.  worldSoupCount: the triangles the soup holds (blocking).
   bool setStreamMesh(unsigned max_triangles);
   unsigned worldSoupCount();
+  // The brick store (AppParams::_volume_params.nBrickStoreBricks; init calls this when it is > 0): reserves a store of max_bricks bricks, so that a
+  // window that returns finds what it left; 0 frees it.  brickStoreCounts: bricks held, dropped for want of room, restored (blocking).
+  bool setBrickStore(unsigned max_bricks);
+  bool brickStoreCounts(unsigned& held, uint64_t& dropped, uint64_t& restored);
 private:
   bool recentre();
   Mat44 worldPose(const Mat44& pose);

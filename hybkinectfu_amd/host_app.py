@@ -133,6 +133,21 @@ class App:
             raise K.KfError("hkf_app_world_soup_count: no application")
         return r
 
+    def set_brick_store(self, max_bricks):
+        """AppParams::_volume_params.nBrickStoreBricks: reserve a brick store of that many bricks; every shift then keeps the observed bricks that
+        leave the window and restores what it finds when the window returns (0: off, the default)"""
+        r = self.h.hkf_app_set_brick_store(C.c_uint(int(max_bricks)))
+        if r != 0:
+            raise K.KfError("hkf_app_set_brick_store failed: %d" % r)
+
+    def brick_store_count(self):
+        """HybKinectfu::brickStoreCounts: (bricks held, bricks dropped for want of room, bricks restored)"""
+        out = (C.c_uint64 * 3)()
+        r = self.h.hkf_app_brick_store_count(out)
+        if r != 0:
+            raise K.KfError("hkf_app_brick_store_count failed: %d" % r)
+        return int(out[0]), int(out[1]), int(out[2])
+
     def close(self):
         self.h.hkf_app_shutdown()
 

@@ -120,6 +120,7 @@ SYMBOLS = [
     "kf_shift_volume", "kf_volume_origin",
     "kf_marching_cubes_region", "kf_region_work", "kf_world_soup_reserve", "kf_world_soup_count", "kf_read_world_soup", "kf_clear_world_soup",
     "kf_append_world_soup", "kf_set_stream_out",
+    "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store",
 ]
 
 
@@ -157,6 +158,10 @@ def load():
         _lib.kf_clear_world_soup.argtypes = [C.c_void_p]
         _lib.kf_append_world_soup.argtypes = [C.c_void_p]
         _lib.kf_set_stream_out.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float]
+        _lib.kf_brick_store_reserve.argtypes = [C.c_void_p, C.c_uint32]
+        _lib.kf_brick_store_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        _lib.kf_brick_store_clear.argtypes = [C.c_void_p]
+        _lib.kf_read_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return _lib
 
 
@@ -201,6 +206,7 @@ class Context:
         self.cam = depth_cam
         self.rgb_cam = rgb_cam if rgb_cam is not None else depth_cam
         self.res, self.size, self.levels = int(volume_res), float(volume_size), int(levels)
+        self.has_color = bool(has_color)
         z0, z1 = slab if slab is not None else (0, volume_res)
         cfg = Config(depth_cam, self.rgb_cam, VolumeParams(volume_res, volume_size, max_weight), levels, max_triangles,
                      int(has_color), device, z0, z1, halo)
@@ -651,6 +657,32 @@ class Context:
     def set_stream_out(self, on, thr=0.0, has_color=False):
         """on: every shift_volume first extracts the surface that is about to leave into the world soup (kf_set_stream_out)"""
         _chk(self.lib.kf_set_stream_out(self.h, int(bool(on)), int(has_color), thr), "kf_set_stream_out")
+
+    def brick_store_reserve(self, max_bricks):
+        """(re)allocate and clear the brick store: from now on shift_volume keeps every observed brick that leaves and restores every brick that
+        enters and is found; 0 frees it (kf_brick_store_reserve)"""
+        _chk(self.lib.kf_brick_store_reserve(self.h, int(max_bricks)), "kf_brick_store_reserve")
+
+    def brick_store_count(self):
+        """(bricks held, bricks dropped for want of room, bricks restored) since the last clear (kf_brick_store_count)"""
+        h, d, r = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        _chk(self.lib.kf_brick_store_count(self.h, C.byref(h), C.byref(d), C.byref(r)), "kf_brick_store_count")
+        return h.value, d.value, r.value
+
+    def brick_store_clear(self):
+        _chk(self.lib.kf_brick_store_clear(self.h), "kf_brick_store_clear")
+
+    def brick_store(self, color=None):
+        """(keys, tsdf, weight, color): everything the store holds -- keys[i] the world brick coordinate (x, y, z), tsdf[i] / weight[i] the brick as
+        (8, 8, 8) in (z, y, x) order with the true weights, color[i] as (8, 8, 8, 3), None without a colour plane (kf_read_brick_store)"""
+        color = getattr(self, "has_color", False) if color is None else color
+        n = self.brick_store_count()[0]
+        keys = np.zeros((n, 3), np.int32)
+        t, w = np.zeros((n, 8, 8, 8), np.float32), np.zeros((n, 8, 8, 8), np.float32)
+        c = np.zeros((n, 8, 8, 8, 3), np.uint8) if color else None
+        if n:
+            _chk(self.lib.kf_read_brick_store(self.h, 0, n, _p(keys), _p(t), _p(w), _p(c) if color else None), "kf_read_brick_store")
+        return keys, t, w, c
 
     def volume_origin(self):
         """(x, y, z): the sum of all shifts since the context was created / reset, in voxels (kf_volume_origin)"""

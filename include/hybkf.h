@@ -429,7 +429,8 @@ int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /*
 /* The moving volume (no reference counterpart: the reference's cube stays where HybKinectfu::init put it, src/HybKinectfu.cpp:51-54).
  * kf_shift_volume: the window moves by +d voxels, each component a multiple of 8 (whole bricks).  Afterwards voxel (x, y, z) holds what voxel
  *   (x + dx, y + dy, z + dz) held before wherever that lies inside the volume -- (tsdf, weight), colour and the brick's deferred-weight state
- *   (kf_set_defer stays in force) --, and everything else reads as after kf_reset_volume.  |d| >= resolution on an axis leaves an empty volume;
+ *   (kf_set_defer stays in force) --, and everything else reads as after kf_reset_volume unless the brick store holds the brick (below).
+ *   |d| >= resolution on an axis leaves an empty volume;
  *   d = (0, 0, 0) returns 0 without enqueuing anything.  The device-resident pose moves with the contents, on the device:
  *   t <- t - (float)d * cell (cell = size_m / resolution, the fp32 quotient) and its inverse is recomputed; the tracked / lost verdict stays.
  *   In place (no second volume), asynchronous on the context's stream, no allocation and no synchronisation: it may sit between two frames
@@ -438,7 +439,7 @@ int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /*
  *   kf_sdf_track; then "shifted here" equals "uploaded there" bit for bit.
  *   KF_ERR_ARG, with nothing touched and nothing enqueued: a component that is no multiple of 8; any non-zero shift on a z-slab context
  *   (one that does not store the whole volume: a z shift needs a layer exchange between the members -- slab groups cannot shift yet);
- *   a sum of shifts beyond 32 bits.
+ *   a sum of shifts beyond 32 bits; with a brick store, a brick of the old or the new window outside [-2^20, 2^20) (below).
  * kf_volume_origin: the sum of all shifts since kf_create / kf_reset_volume, in voxels: where voxel (0, 0, 0) of the window lies in the first
  *   cube.  World position = volume position + origin * cell.  Host bookkeeping: never blocks.  Zero on a context that never shifts. */
 int kf_shift_volume(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz);
@@ -467,7 +468,8 @@ int kf_volume_origin(kf_ctx* ctx, int32_t origin_vox[3]);
  *   [resolution + d - 1, resolution); over several axes the union as disjoint boxes in this order -- the x strip in full, the y strip without
  *   the x strip, the z strip without both --, each in canonical order.  Exactly these cells can never be extracted again (cell d becomes cell 0,
  *   whose lookups need voxel -1; cell d + 1 keeps its 27 voxels and is left for later), so a run of shifts in one direction loses nothing and
- *   emits nothing twice.  A window that comes back over old ground re-fuses it and streams it again: the soup then holds that surface twice.
+ *   emits nothing twice.  A window that comes back over old ground re-fuses it (or, with a brick store, gets it back: below) and streams it again
+ *   when it leaves again: the soup then holds that surface twice.
  *   The volume, the pose and every later frame are what they are without stream-out, bit for bit.  KF_ERR_STATE without a reserved soup or
  *   with has_color on a context without a colour plane; KF_ERR_ARG on a z-slab context. */
 enum { KF_MC_WORLD = 1, KF_MC_TO_WORLD_SOUP = 2 };
@@ -479,6 +481,38 @@ int kf_read_world_soup(kf_ctx* ctx, kf_triangle* dst, uint32_t first, uint32_t c
 int kf_clear_world_soup(kf_ctx* ctx);
 int kf_append_world_soup(kf_ctx* ctx);
 int kf_set_stream_out(kf_ctx* ctx, int on, int has_color, float threshold_marchingcube);
+
+/* The brick store: the moving volume keeps what leaves and restores it on return (no reference counterpart: the reference's cube never moves, so
+ * nothing ever leaves it).  A device-resident, sparse archive of bricks keyed by WORLD BRICK COORDINATE = origin / 8 + brick index (see
+ * kf_volume_origin; the origin is always a multiple of 8), each component in [-2^20, 2^20).  Absent until reserved: a context that never reserves
+ * one enqueues the launches and produces the bits it always did.
+ * kf_shift_volume with a store: after the deferred weights are flushed and the departing cells are streamed out (kf_set_stream_out), and before
+ *   anything moves, every brick that is about to leave (source brick q with q - d / 8 outside [0, resolution / 8) on some axis) and has a voxel of
+ *   weight > 0 is copied into the store: its 512 (tsdf, weight) pairs, its colour on a context with a colour plane, its deferred-weight word.  A key
+ *   the store already holds keeps its entry and is overwritten (the window's copy is the newer one); a new key takes the next free entry; when none
+ *   is free the brick is counted as dropped and a later look-up of its key misses.  A brick never observed takes no entry.  After the move every
+ *   brick that has entered (destination brick b with b + d / 8 outside) is looked up, read-only: on a hit the entry is copied back -- tsdf, weight,
+ *   colour and deferred-weight word, bit for bit -- and the brick's flags, its has-negative bit and the skip tables follow as for a moved brick, so
+ *   a shift away and back is lossless and "shifted here" still equals "uploaded there".  A restored brick stays in the store (nothing is ever
+ *   deleted); until it leaves again the window's copy is the only current one.  Still asynchronous, no allocation, no synchronisation: two more
+ *   launches.  KF_ERR_ARG, with nothing touched and nothing enqueued, when a brick of the old or of the new window would have a world brick
+ *   coordinate outside [-2^20, 2^20).  With stream-out on, a restored brick that leaves again is streamed again: the world soup is not de-duplicated.
+ * kf_brick_store_reserve: (re)allocates the store for max_bricks bricks (4 KiB each, + 2 KiB with a colour plane, + a hash table of the next power of
+ *   two >= 2 * max_bricks entries) and clears it; from then on every shift uses it.  0 frees it: shifts are what they were.  Blocking.  KF_ERR_ARG
+ *   on a z-slab context or a NULL context; KF_ERR_ALLOC when the memory is not there -- the store is then absent.
+ * kf_brick_store_count: bricks held, bricks dropped since the last clear, bricks restored since the last clear (cumulative).  Any pointer may be
+ *   NULL.  Zeros without a store.  Blocking.
+ * kf_brick_store_clear: no entries, all three counts zero (KF_ERR_STATE without a store); kf_reset_volume does the same, kf_destroy frees the store.
+ * kf_read_brick_store: entries [first, first + count) as a sparse map of what the window has left behind: keys[i][3] the world brick coordinate
+ *   (x, y, z); tsdf[i][512] and weight[i][512] in the in-brick order (z & 7) << 6 | (y & 7) << 3 | (x & 7) -- kf_download_volume's order restricted
+ *   to the brick --, the weights being the TRUE weights kf_download_volume would have reported just before the brick left (the stored
+ *   deferred-weight word applied); color[i][512][3] the colour bytes (untouched on a context without a colour plane).  Any pointer may be NULL.
+ *   The order of the entries is unspecified, and stable as long as no shift, clear or reserve happens in between.  KF_ERR_ARG when
+ *   first + count > held.  Blocking. */
+int kf_brick_store_reserve(kf_ctx* ctx, uint32_t max_bricks);
+int kf_brick_store_count(kf_ctx* ctx, uint32_t* held, uint64_t* dropped, uint64_t* restored);
+int kf_brick_store_clear(kf_ctx* ctx);
+int kf_read_brick_store(kf_ctx* ctx, uint32_t first, uint32_t count, int32_t* keys, float* tsdf, float* weight, uint8_t* color);
 
 /* test hook: counts fp32 quotients where the kernels' split exact-division helper differs from the compiler's `/` (must be 0) */
 int kf_selftest_div(kf_ctx* ctx, unsigned n, unsigned seed, int mode, unsigned* mismatches);
