@@ -13,6 +13,7 @@
 // nothing, so the table never holds a key without a slot and never fills up: a later look-up of a dropped key misses.  Nothing is ever deleted.
 #include "kf_internal.h"
 #include "brick_key.h"
+#include "brick_find.h"
 #include <stdint.h>
 
 // Up to three disjoint boxes of bricks (half-open), numbered one behind the other: iteration i < end[0] lies in box 0, i < end[1] in box 1, ...
@@ -27,18 +28,6 @@ __device__ __forceinline__ void box_brick(const KfBrickBoxes& b, unsigned i, int
   const int lz = k == 0 ? b.lo[0][2] : (k == 1 ? b.lo[1][2] : b.lo[2][2]);
   const unsigned ex = (unsigned)(hx - lx), ey = (unsigned)(hy - ly);
   bx = lx + (int)(j % ex); by = ly + (int)((j / ex) % ey); bz = lz + (int)(j / (ex * ey));
-}
-
-// read-only: the slot of `key`, or KF_BRICK_NO_SLOT.  The probe ends at the first free entry: entries are never freed, so a key that was ever
-// inserted sits before it.
-__device__ __forceinline__ unsigned store_find(const KfBrickStore& st, unsigned long long key) {
-  unsigned h = kf_brick_key_hash(key, st.mask);
-  for (unsigned p = 0; p <= st.mask; ++p, h = (h + 1u) & st.mask) {
-    const unsigned long long k = st.tkey[h];
-    if (k == key) { const unsigned slot = st.tslot[h]; return slot < st.max_bricks ? slot : KF_BRICK_NO_SLOT; }
-    if (k == KF_BRICK_KEY_EMPTY) break;
-  }
-  return KF_BRICK_NO_SLOT;
 }
 
 // one lane per departing brick: the slot the brick is written to, or KF_BRICK_NO_SLOT when the store is full (counted as dropped)

@@ -264,6 +264,9 @@ struct kf_ctx {
   // since kf_create / kf_reset_volume.  Host bookkeeping only: no kernel reads it.
   int32_t origin_vox[3];
   KfBrickStore bstore;           // the brick store (brickstore.hip): absent (max_bricks == 0) until kf_brick_store_reserve
+  // the virtual window of kf_marching_cubes_at (mapmesh.hip): one all-zero brick (4 KiB), then 16 bytes per brick slot -- where that brick's voxels and colours
+  // are read from.  Part of the extraction scratch: allocated by the first kf_marching_cubes_at, freed with the rest.
+  void* mc_vtab;
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,
@@ -672,6 +675,7 @@ int kf_upload_wait_for(kf_ctx* ctx, const uint16_t* dev_mm);   // dev_mm is abou
 // (mcubes.hip) kf_marching_cubes_region past its argument checks: what kf_shift_volume's stream-out enqueues for each departing box
 int kf_mc_region_enqueue(kf_ctx* ctx, int has_color, float thr, const int32_t lo[3], const int32_t hi[3], int flags);
 void kf_world_soup_free(kf_ctx* ctx);    // (mcubes.hip) for kf_destroy: the caller has synchronised the stream
+int kf_mc_scratch(kf_ctx* ctx);          // (mcubes.hip) the extraction scratch, allocated on first use; mapmesh.hip works on the same scratch
 // (brickstore.hip) the brick store's part of kf_shift_volume, asynchronous on the context's stream: s = the shift in bricks (not clamped), origin_vox = the window's
 // origin the keys are formed with -- the old one for the eviction (before anything moves), the new one for the restore (after the move)
 int kf_brick_store_evict(kf_ctx* ctx, const int s[3], const int32_t origin_vox[3]);

@@ -136,6 +136,8 @@ int hkf_app_brick_store_count(uint64_t out3[3]) {
   out3[0] = held; out3[1] = dropped; out3[2] = restored;
   return 0;
 }
+// MeshGeneratorMarchingcube::setMapMesh (call AFTER hkf_app_init, which restores the defaults): with a brick store reserved, generateMesh builds the map mesh
+int hkf_app_set_map_mesh(int on) { if (!g_mesh) return -1; g_mesh->setMapMesh(on != 0); return 0; }
 int hkf_app_generate_mesh() { if (!g_mesh) return -1; g_mesh->generateMesh(); return (int)g_mesh->triangleCount(); }
 int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_faces) {
   if (!g_mesh) return -1;

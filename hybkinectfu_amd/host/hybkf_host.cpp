@@ -18,7 +18,7 @@ void AppParams::setDefaults(unsigned res, float size) {
   _depth_prepocess_params = {4.0f, 0.3f, 0.03f, 2.0f};                  // max, min, sigma depth, sigma pixel
   _icp_params = {3, 0.1f, 0.1f, 0.3f, 0.3f};
   _sdf_tracker_params = {6, 0.3f, 0.3f};
-  _volume_params = {res, size, 128.0f, 0.0f, 0u, 0u};
+  _volume_params = {res, size, 128.0f, 0.0f, 0u, 0u, false};
   _integrate_params = {0.05f, 2.0f};
   _raycast_params.fRayIncrement = 0.7f * _integrate_params.fSdfTruncation;  // AppParamsProducer.cpp:113-117
   _marchingcube_params.uMaxTriangles = 6500000;
@@ -617,6 +617,14 @@ void MeshGeneratorMarchingcube::generateMesh() {                // :23-29
   const AppParams* p = AppParams::instance();
   CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
   _world = false;
+  if (p->_volume_params.bMapMesh && p->_volume_params.nBrickStoreBricks > 0) {   // the map: store and window on the world's tile lattice, world coordinates
+    uint64_t dropped = 0; uint32_t tiles = 0;
+    if (0 == kf_brick_store_count(dm->ctx(), nullptr, &dropped, nullptr) && dropped)
+      fprintf(stderr, "generateMesh: the brick store has dropped %llu bricks for want of room: the map mesh has holes there\n", (unsigned long long)dropped);
+    if (dm->check(kf_clear_triangles(dm->ctx()))) return;
+    _world = 0 == dm->check(kf_marching_cubes_map(dm->ctx(), p->_switch_params.useRGBData, mesh_threshold(), KF_MC_WORLD, &tiles));
+    return;
+  }
   if (p->_volume_params.nStreamMeshTriangles > 0) {           // streaming: [world soup, the current window], everything in world coordinates
     const int32_t lo[3] = {0, 0, 0}, hi[3] = {(int32_t)p->_volume_params.nResolution, (int32_t)p->_volume_params.nResolution, (int32_t)p->_volume_params.nResolution};
     if (dm->check(kf_clear_triangles(dm->ctx())) || dm->check(kf_append_world_soup(dm->ctx()))) return;
@@ -625,6 +633,7 @@ void MeshGeneratorMarchingcube::generateMesh() {                // :23-29
   }
   dm->check(kf_marching_cubes(dm->ctx(), p->_switch_params.useRGBData, 300 * p->_volume_params.fVolumeMeterSize / p->_volume_params.nResolution));
 }
+void MeshGeneratorMarchingcube::setMapMesh(bool on) { AppParams::instance()->_volume_params.bMapMesh = on; }
 unsigned MeshGeneratorMarchingcube::triangleCount() {
   uint32_t n = 0; CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
   dm->check(kf_triangle_count(dm->ctx(), &n));

@@ -25,7 +25,9 @@ struct DepthPrepocessParams { float fMaxTrunc, fMinTrunc, fSigmaDepth, fSigmaPix
 // leave, and MeshGeneratorMarchingcube::generateMesh hands out [world soup, current window], all in world coordinates
 // nBrickStoreBricks (not in the reference): 0 (default): off.  > 0: HybKinectfu::init reserves a brick store of that many bricks
 // (kf_brick_store_reserve): every shift keeps the observed bricks that leave the window and restores the ones it finds when the window returns
-struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; unsigned nStreamMeshTriangles; unsigned nBrickStoreBricks; };
+// bMapMesh (not in the reference): false (default): off.  true, with a brick store reserved: MeshGeneratorMarchingcube::generateMesh builds the MAP mesh --
+// kf_marching_cubes_map over store and window, world coordinates, no duplicates -- instead of [world soup, current window] (setMapMesh)
+struct tsdfVolumeParams { unsigned nResolution; float fVolumeMeterSize, fWeightMax; float fRecentreDist; unsigned nStreamMeshTriangles; unsigned nBrickStoreBricks; bool bMapMesh; };
 struct MarchingcubeParams { unsigned uMaxTriangles; };
 struct IntegrateParams { float fSdfTruncation, fMaxIntegrateDist; };
 struct SwitchParams { bool recordRGBD, recordTrajectory, useRGBData, colorAngleWeight, useDatasetRGBD, useTrajFromFile, useSdfTracker; };
@@ -317,10 +319,12 @@ public:
   // Off by default; if the device weld fails, saveMesh welds on the host as before.
   void setDeviceWeld(bool on) { _device_weld = on; }
   bool deviceWeld() const { return _device_weld; }
+  // AppParams::_volume_params.bMapMesh: with a brick store reserved, generateMesh clears the triangle buffer and meshes the whole map (kf_marching_cubes_map)
+  void setMapMesh(bool on);
 protected:
   bool copyTrianglesToCPU();
   bool weldOnDevice();                                                       // :61-86 without the 72 bytes per triangle crossing to the host
   MeshData _meshes;
   bool _device_weld = false;
-  bool _world = false;            // the triangles of the last generateMesh are in world coordinates already (streaming on): saveMesh adds no origin
+  bool _world = false;            // the triangles of the last generateMesh are in world coordinates already (streaming on, or the map mesh): saveMesh adds no origin
 };

@@ -140,6 +140,12 @@ class App:
         if r != 0:
             raise K.KfError("hkf_app_set_brick_store failed: %d" % r)
 
+    def set_map_mesh(self, on=True):
+        """MeshGeneratorMarchingcube::setMapMesh: with a brick store reserved, generate_mesh builds the map mesh -- store and window, world coordinates,
+        every cell once (kf_marching_cubes_map) -- instead of [world soup, current window].  Default off."""
+        if self.h.hkf_app_set_map_mesh(int(bool(on))) != 0:
+            raise K.KfError("hkf_app_set_map_mesh: no application")
+
     def brick_store_count(self):
         """HybKinectfu::brickStoreCounts: (bricks held, bricks dropped for want of room, bricks restored)"""
         out = (C.c_uint64 * 3)()

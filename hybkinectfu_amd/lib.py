@@ -120,7 +120,8 @@ SYMBOLS = [
     "kf_shift_volume", "kf_volume_origin",
     "kf_marching_cubes_region", "kf_region_work", "kf_world_soup_reserve", "kf_world_soup_count", "kf_read_world_soup", "kf_clear_world_soup",
     "kf_append_world_soup", "kf_set_stream_out",
-    "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store",
+    "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
+    "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
 ]
 
 
@@ -162,7 +163,25 @@ def load():
         _lib.kf_brick_store_count.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         _lib.kf_brick_store_clear.argtypes = [C.c_void_p]
         _lib.kf_read_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.kf_brick_store_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
+        _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
+        _lib.kf_map_tile_frames.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64]
+        _lib.kf_map_tile_frames.restype = C.c_int64
     return _lib
+
+
+def map_tiles(store_lo, store_hi, origin_vox, res):
+    """the frames (n, 3) kf_marching_cubes_map visits, in order, for a store box (bricks, half-open), a window origin and a resolution (kf_map_tile_frames)"""
+    lib = load()
+    a, b, o = ((C.c_int32 * 3)(*[int(x) for x in v]) for v in (store_lo, store_hi, origin_vox))
+    n = lib.kf_map_tile_frames(a, b, o, int(res), None, 0)
+    if n < 0:
+        raise KfError("kf_map_tile_frames: resolution %d" % res)
+    out = np.zeros((n, 3), np.int32)
+    if n:
+        lib.kf_map_tile_frames(a, b, o, int(res), out.ctypes.data_as(C.c_void_p), n)
+    return out
 
 
 class KfError(RuntimeError):
@@ -683,6 +702,26 @@ class Context:
         if n:
             _chk(self.lib.kf_read_brick_store(self.h, 0, n, _p(keys), _p(t), _p(w), _p(c) if color else None), "kf_read_brick_store")
         return keys, t, w, c
+
+    def brick_store_bounds(self):
+        """(lo, hi): the half-open box of the world brick coordinates the store holds; lo == hi for an empty or absent store (kf_brick_store_bounds)"""
+        lo, hi = (C.c_int32 * 3)(), (C.c_int32 * 3)()
+        _chk(self.lib.kf_brick_store_bounds(self.h, lo, hi), "kf_brick_store_bounds")
+        return tuple(int(x) for x in lo), tuple(int(x) for x in hi)
+
+    def marching_cubes_at(self, thr, frame_origin, lo, hi, has_color=False, flags=0):
+        """marching_cubes_region in a virtual window at frame_origin (voxels, multiples of 8): the triangles the region call would give after
+        shift_volume(frame_origin - origin), store included, without moving anything (kf_marching_cubes_at)"""
+        f = (C.c_int32 * 3)(*[int(x) for x in frame_origin])
+        l, h = (C.c_int32 * 3)(*[int(x) for x in lo]), (C.c_int32 * 3)(*[int(x) for x in hi])
+        _chk(self.lib.kf_marching_cubes_at(self.h, int(has_color), thr, f, l, h, int(flags)), "kf_marching_cubes_at")
+
+    def marching_cubes_map(self, thr, has_color=False, flags=MC_WORLD):
+        """one mesh of everything ever fused -- brick store and window -- in world coordinates, appended to the triangle buffer tile by tile of a
+        lattice fixed in the world; returns the number of tiles visited (kf_marching_cubes_map)"""
+        n = C.c_uint32()
+        _chk(self.lib.kf_marching_cubes_map(self.h, int(has_color), thr, int(flags), C.byref(n)), "kf_marching_cubes_map")
+        return n.value
 
     def volume_origin(self):
         """(x, y, z): the sum of all shifts since the context was created / reset, in voxels (kf_volume_origin)"""

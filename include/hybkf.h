@@ -508,11 +508,47 @@ int kf_set_stream_out(kf_ctx* ctx, int on, int has_color, float threshold_marchi
  *   to the brick --, the weights being the TRUE weights kf_download_volume would have reported just before the brick left (the stored
  *   deferred-weight word applied); color[i][512][3] the colour bytes (untouched on a context without a colour plane).  Any pointer may be NULL.
  *   The order of the entries is unspecified, and stable as long as no shift, clear or reserve happens in between.  KF_ERR_ARG when
- *   first + count > held.  Blocking. */
+ *   first + count > held.  Blocking.
+ * kf_brick_store_bounds: the box of the world brick coordinates the store holds, half-open: lo_brick <= key < hi_brick on every axis, taken over the
+ *   held entries by one small reduction kernel.  lo == hi (all zeros) for an empty or absent store.  KF_ERR_ARG on a NULL pointer.  Blocking. */
 int kf_brick_store_reserve(kf_ctx* ctx, uint32_t max_bricks);
 int kf_brick_store_count(kf_ctx* ctx, uint32_t* held, uint64_t* dropped, uint64_t* restored);
 int kf_brick_store_clear(kf_ctx* ctx);
 int kf_read_brick_store(kf_ctx* ctx, uint32_t first, uint32_t count, int32_t* keys, float* tsdf, float* weight, uint8_t* color);
+int kf_brick_store_bounds(kf_ctx* ctx, int32_t lo_brick[3], int32_t hi_brick[3]);
+
+/* The map mesh: marching cubes over the brick store and the window together (no reference counterpart: the reference's one cube is its map).
+ * kf_marching_cubes_at: kf_marching_cubes_region in a VIRTUAL window.  Emits exactly the triangles -- the same bytes in the same order, appended to the
+ *   triangle buffer and clamped the same way -- that kf_marching_cubes_region(ctx, has_color, threshold, lo, hi, flags) would emit after
+ *   kf_shift_volume(frame_origin_vox - current origin) on this context, the store's bricks restored, WITHOUT moving anything: volume, flags, skip tables,
+ *   pose, model maps, store, deferred-weight words and every later frame are bit for bit what they are without the call.  lo / hi are cell indices in the
+ *   virtual window, [0, resolution), clamped, with the region call's rim rule; an empty or inverted box is a no-op.  flags: KF_MC_WORLD or 0; with
+ *   KF_MC_WORLD every position component i gets + (float)frame_origin_vox[i] * cell (the region call's world rule with the frame's origin in place of the
+ *   window's).  Where a brick of the virtual window comes from: world brick frame_origin_vox / 8 + b reads the WINDOW's copy if it lies inside the current
+ *   window (the newer one: a restored brick stays in the store as a stale copy, which must not win), otherwise the STORE's entry if its key is held
+ *   (read-only), otherwise it was never observed.  With frame_origin_vox == the current origin the call is kf_marching_cubes_region.  No store reserved
+ *   is not an error: bricks outside the window read as never observed.  Asynchronous on the context's stream: no synchronisation, no read-back; the first
+ *   call allocates one indirection table (16 bytes per brick of the window, plus one 4 KiB zero brick) with the extraction scratch.  kf_region_work
+ *   reports the call's work: out[0] bricks whose voxels were classified, out[1] blocks listed.
+ *   KF_ERR_ARG, with nothing touched: a NULL context, origin or box; a frame origin component that is no multiple of 8; flag bits other than KF_MC_WORLD;
+ *   a z-slab context; a frame any of whose bricks has a world brick coordinate outside [-2^20, 2^20).  KF_ERR_STATE: no triangle buffer, or has_color
+ *   without a colour plane.
+ * kf_marching_cubes_map: one mesh of everything ever fused, in world coordinates (KF_MC_WORLD is forced on; flags takes KF_MC_WORLD or 0), appended to the
+ *   triangle buffer.  Space is tiled on a lattice fixed in the WORLD: with T = resolution - 16, tile k of an axis is the frame F_k = k * T - 8 voxels and owns
+ *   the frame's local cells [8, resolution - 8), i.e. the world cells [k * T, (k + 1) * T).  Owned boxes are disjoint and cover space, and every owned
+ *   cell lies eight cells inside its frame, so no cell is lost to the rim rule and none is emitted twice.  The tiles visited are those whose frame meets
+ *   kf_brick_store_bounds' box or the window's bricks, in z, then y, then x order, ascending; each is one kf_marching_cubes_at over its owned box.
+ *   *n_tiles (may be NULL): tiles visited.  Because the lattice does not depend on where the window stands, the map mesh is the same bytes wherever the
+ *   window is, as long as no frame was fused in between and the store dropped nothing (kf_brick_store_count's `dropped`: a dropped brick is a hole).
+ *   Blocks once (the store's bounds), then enqueues.  Refusals as for kf_marching_cubes_at, and KF_ERR_ARG for a resolution below 32.
+ * kf_map_tile_frames: the lattice alone, on the host (no context): the frames (three voxel coordinates per tile, in visiting order) for a store box
+ *   (bricks, half-open; lo == hi: none), a window origin and a resolution.  Writes the first `cap` tiles to `frames` (may be NULL with cap 0) and returns
+ *   the number of tiles, or -1 for a NULL pointer or a resolution below 32 or no multiple of 8. */
+int kf_marching_cubes_at(kf_ctx* ctx, int has_color, float threshold_marchingcube, const int32_t frame_origin_vox[3], const int32_t lo[3], const int32_t hi[3],
+                         int flags);
+int kf_marching_cubes_map(kf_ctx* ctx, int has_color, float threshold_marchingcube, int flags, uint32_t* n_tiles);
+int64_t kf_map_tile_frames(const int32_t store_lo_brick[3], const int32_t store_hi_brick[3], const int32_t origin_vox[3], int32_t resolution, int32_t* frames,
+                           int64_t cap);
 
 /* test hook: counts fp32 quotients where the kernels' split exact-division helper differs from the compiler's `/` (must be 0) */
 int kf_selftest_div(kf_ctx* ctx, unsigned n, unsigned seed, int mode, unsigned* mismatches);
