@@ -125,6 +125,12 @@ struct kf_group {
   uint64_t* view_ta_min = nullptr;
   float* view_cand_sum = nullptr;
   size_t view_cap_px = 0;
+  // the moving volume (kf_group_shift_volume): per member the feed buffer its move reads and, on RCCL, the send buffer its packs go to; sized to the
+  // plan, grown on demand.  world_cuts: the whole layout -- the group's own cuts, or on RCCL_RANK what the first shift gathered from the ranks
+  uint8_t* feed[KF_GROUP_MAX_MEMBERS] = {};
+  uint8_t* sendb[KF_GROUP_MAX_MEMBERS] = {};
+  size_t feed_cap[KF_GROUP_MAX_MEMBERS] = {}, send_cap[KF_GROUP_MAX_MEMBERS] = {};
+  std::vector<uint32_t> world_cuts;
   bool failed = false;
   bool timing = false;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> ev;   // merge timers: a pool of at most KF_GROUP_MAX_TIMED_FRAMES, ev_used of them recorded since the last read
@@ -195,7 +201,8 @@ void release(kf_group* g) {
     hipSetDevice(g->dev[i]);
     if (g->comm[i]) ncclCommDestroy(g->comm[i]);
     if (g->m[i]) kf_destroy(g->m[i]);            // (a member on the group stream returns to its own stream first)
-    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i], g->rgb[i], g->view_ta[i], g->view_ta_own[i], g->view_spec[i], g->view_cand[i]};
+    void* bufs[] = {g->ta[i], g->ta_own[i], g->spec[i], g->cand[i], g->depth[i], g->rgb[i], g->view_ta[i], g->view_ta_own[i], g->view_spec[i], g->view_cand[i],
+                    g->feed[i], g->sendb[i]};
     for (void* b : bufs) if (b) hipFree(b);
   }
   if (g->n) hipSetDevice(g->dev[0]);
@@ -279,6 +286,15 @@ int member_maps(kf_group* g, uint32_t i, const uint64_t* ta_min, const float* ca
                   : kf_set_model_maps_rays(g->m[i], nullptr, &g->base.depth_camera, ta_min, cand);
 }
 
+// step 5 of the frame in the group's kind
+int member_cross(kf_group* g, uint32_t i) {
+  const kf_group_params& p = g->p;
+  const kf_camera_params* cam = &g->base.depth_camera;
+  uint64_t* own = g->backend == KF_GROUP_LOCAL ? g->ta[i] : g->ta_own[i];
+  return g->color ? kf_raycast_volume_slab_cross_spec_color(g->m[i], nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i])
+                  : kf_raycast_volume_slab_cross_spec(g->m[i], nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i]);
+}
+
 // steps 6-9 of the frame
 int merge(kf_group* g) {
   const kf_camera_params* cam = &g->base.depth_camera;
@@ -344,14 +360,8 @@ int frame(kf_group* g, const uint16_t* const* dev_mm, const uint16_t* host_mm, u
     }
     if ((st = kf_preprocess(c, p.trunc_min, p.trunc_max, p.sigma_pixel, p.sigma_depth, cam))) return st;
     if ((st = kf_icp_track(c, frame_id, &p.icp, cam))) return st;
-    uint64_t* own = g->backend == KF_GROUP_LOCAL ? g->ta[i] : g->ta_own[i];
-    if (g->color) {
-      if ((st = kf_integrate_volume(c, 1, g->angle_weight, nullptr, &p.integrate, cam, rcam))) return st;
-      if ((st = kf_raycast_volume_slab_cross_spec_color(c, nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i]))) return st;
-    } else {
-      if ((st = kf_integrate_volume(c, 0, 0, nullptr, &p.integrate, cam, cam))) return st;
-      if ((st = kf_raycast_volume_slab_cross_spec(c, nullptr, &p.raycast, cam, p.trunc_min, p.trunc_max, g->ta[i], own, g->spec[i]))) return st;
-    }
+    if ((st = g->color ? kf_integrate_volume(c, 1, g->angle_weight, nullptr, &p.integrate, cam, rcam) : kf_integrate_volume(c, 0, 0, nullptr, &p.integrate, cam, cam))) return st;
+    if ((st = member_cross(g, i))) return st;
   }
   hipEvent_t e1 = nullptr;
   if (g->timing && g->ev_used < KF_GROUP_MAX_TIMED_FRAMES) {          // (a full pool: this frame's merge goes untimed until the next read)
@@ -443,6 +453,128 @@ int view(kf_group* g, int mode, const kf_mat44* pose, const kf_camera_params* ca
   }
   if ((st = hipSetDevice(g->dev[0]))) return st;
   return kf_view_from_rays(g->m[0], mode, pose, cam, local ? g->view_ta_min : g->view_ta[0], local ? g->view_cand_sum : g->view_cand[0], words, dev_v, dev_n);
+}
+
+// ---- the moving volume ----------------------------------------------------------------------------------------------------------------------
+// stored voxel layers of the member that owns [z0, z1) with `halo` layers around them (kf_create's arithmetic: whole bricks, clamped to the volume)
+void stored_layers(uint32_t res, uint32_t z0, uint32_t z1, uint32_t halo, uint32_t* s0, uint32_t* s1) {
+  const uint32_t h = (halo + 7) / 8 * 8;
+  *s0 = z0 > h ? z0 - h : 0;
+  *s1 = z1 + h < res ? z1 + h : res;
+}
+bool layout_ok(uint32_t res, uint32_t members, const uint32_t* cuts) {
+  if (res == 0 || res % 8 || members < 1 || members > res / 8 || !cuts || cuts[0] != 0 || cuts[members] != res) return false;
+  for (uint32_t i = 0; i < members; ++i) if (cuts[i + 1] <= cuts[i] || cuts[i + 1] % 8) return false;
+  return true;
+}
+
+int grow(uint8_t** buf, size_t* cap, size_t bytes) {      // (hipFree waits for the work that still reads the old buffer)
+  if (bytes <= *cap) return 0;
+  if (*buf) { hipFree(*buf); *buf = nullptr; *cap = 0; }
+  const int st = group_alloc((void**)buf, bytes);
+  if (!st) *cap = bytes;
+  return st;
+}
+
+// RCCL_RANK: the ranks' (z0, z1), gathered once (blocking) and kept; LOCAL / RCCL_ALL: the group's own cuts
+int world_layout(kf_group* g) {
+  if (!g->world_cuts.empty()) return 0;
+  if (g->backend != KF_GROUP_RCCL_RANK || g->world == 1) {
+    g->world_cuts.assign(g->cuts, g->cuts + g->n + 1);
+    return 0;
+  }
+  int st = 0;
+  uint32_t* dev = nullptr;
+  std::vector<uint32_t> pairs(2 * (size_t)g->world);
+  if ((st = (int)hipSetDevice(g->dev[0]))) return st;
+  if ((st = group_alloc((void**)&dev, pairs.size() * sizeof(uint32_t)))) return st;
+  hipStream_t s = member_stream(g, 0);
+  st = (int)hipMemcpyAsync(dev + 2 * g->rank, g->cuts, 2 * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+  if (!st) st = nccl_status(ncclAllGather(dev + 2 * g->rank, dev, 2, ncclUint32, g->comm[0], s));
+  if (!st) st = (int)hipMemcpyAsync(pairs.data(), dev, pairs.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, s);
+  if (!st) st = (int)hipStreamSynchronize(s);
+  hipFree(dev);
+  if (st) return st;
+  std::vector<uint32_t> cuts(g->world + 1);
+  cuts[0] = pairs[0];
+  for (uint32_t r = 0; r < g->world; ++r) {
+    if (pairs[2 * r] != cuts[r]) return KF_GROUP_ERR_STATE;       // the ranks' slabs do not tile the volume in rank order
+    cuts[r + 1] = pairs[2 * r + 1];
+  }
+  if (!layout_ok(g->base.volume.resolution, g->world, cuts.data())) return KF_GROUP_ERR_STATE;
+  g->world_cuts = cuts;
+  return 0;
+}
+
+// the three steps of kf_group_shift_volume; the arguments have passed its checks
+int shift(kf_group* g, int32_t dx, int32_t dy, int32_t dz) {
+  int st = 0;
+  if ((st = world_layout(g))) return st;
+  const uint32_t world = (uint32_t)g->world_cuts.size() - 1;
+  const bool local = g->backend == KF_GROUP_LOCAL, by_rank = g->backend == KF_GROUP_RCCL_RANK;
+  std::vector<kf_group_transfer> plan(2 * (size_t)world + 2);
+  int n_plan = kf_group_shift_plan(g->base.volume.resolution, world, g->world_cuts.data(), g->halo, dz, plan.data(), (uint32_t)plan.size());
+  if (n_plan > (int)plan.size()) {
+    plan.resize((size_t)n_plan);
+    n_plan = kf_group_shift_plan(g->base.volume.resolution, world, g->world_cuts.data(), g->halo, dz, plan.data(), (uint32_t)plan.size());
+  }
+  if (n_plan < 0) return KF_GROUP_ERR_STATE;
+  plan.resize((size_t)n_plan);
+  // member r of the layout is member `at(r)` of this process (or none of its members)
+  auto at = [&](uint32_t r) -> int { return by_rank ? (r == g->rank ? 0 : -1) : (int)r; };
+  const size_t lb = kf_slab_layer_bytes(g->m[0]);
+  uint32_t need0[KF_GROUP_MAX_MEMBERS], need1[KF_GROUP_MAX_MEMBERS];
+  size_t fed[KF_GROUP_MAX_MEMBERS] = {}, sent[KF_GROUP_MAX_MEMBERS] = {};
+  for (uint32_t i = 0; i < g->n; ++i)
+    if ((st = kf_slab_shift_needs(g->m[i], dz, &need0[i], &need1[i]))) return st;
+  for (const kf_group_transfer& t : plan) {                      // the plan feeds every member exactly what it needs: checked before a byte moves
+    const int to = at(t.to_member), from = at(t.from_member);
+    if (to >= 0) {
+      if (t.bz_begin != need0[to] + fed[to] || t.bz_end > need1[to]) return KF_GROUP_ERR_STATE;
+      fed[to] += t.bz_end - t.bz_begin;
+    }
+    if (from >= 0) sent[from] += t.bz_end - t.bz_begin;
+  }
+  for (uint32_t i = 0; i < g->n; ++i) {
+    if (fed[i] != need1[i] - need0[i]) return KF_GROUP_ERR_STATE;
+    if ((st = (int)hipSetDevice(g->dev[i]))) return st;
+    if ((st = grow(&g->feed[i], &g->feed_cap[i], fed[i] * lb))) return st;
+    if (!local && (st = grow(&g->sendb[i], &g->send_cap[i], sent[i] * lb))) return st;
+  }
+  // 1. every owner packs what the plan sends: LOCAL straight into the receiver's feed, RCCL into its send buffer in plan order
+  size_t off[KF_GROUP_MAX_MEMBERS] = {};
+  for (const kf_group_transfer& t : plan) {
+    const int from = at(t.from_member);
+    if (from < 0) continue;
+    uint8_t* dst = local ? g->feed[t.to_member] + (size_t)(t.bz_begin - need0[t.to_member]) * lb : g->sendb[from] + off[from];
+    off[from] += (size_t)(t.bz_end - t.bz_begin) * lb;
+    if ((st = (int)hipSetDevice(g->dev[from]))) return st;
+    if ((st = kf_slab_pack_layers(g->m[from], t.bz_begin, t.bz_end, dst))) return st;
+  }
+  // 2. the exchange.  LOCAL: none -- one stream, and every pack above precedes every move below
+  if (!local && !plan.empty()) {
+    for (uint32_t i = 0; i < g->n; ++i) off[i] = 0;
+    if ((st = nccl_status(ncclGroupStart()))) return st;
+    for (size_t k = 0; k < plan.size() && !st; ++k) {
+      const kf_group_transfer& t = plan[k];
+      const int from = at(t.from_member), to = at(t.to_member);
+      const size_t bytes = (size_t)(t.bz_end - t.bz_begin) * lb;
+      if (from >= 0) {
+        st = nccl_status(ncclSend(g->sendb[from] + off[from], bytes, ncclUint8, (int)t.to_member, g->comm[from], member_stream(g, (uint32_t)from)));
+        off[from] += bytes;
+      }
+      if (to >= 0 && !st)
+        st = nccl_status(ncclRecv(g->feed[to] + (size_t)(t.bz_begin - need0[to]) * lb, bytes, ncclUint8, (int)t.from_member, g->comm[to], member_stream(g, (uint32_t)to)));
+    }
+    const int st_end = nccl_status(ncclGroupEnd());
+    if (st || st_end) return st ? st : st_end;
+  }
+  // 3. the move
+  for (uint32_t i = 0; i < g->n; ++i) {
+    if ((st = (int)hipSetDevice(g->dev[i]))) return st;
+    if ((st = kf_shift_slab(g->m[i], dx, dy, dz, need0[i] < need1[i] ? g->feed[i] : nullptr, need0[i], need1[i]))) return st;
+  }
+  return 0;
 }
 }  // namespace
 
@@ -706,6 +838,61 @@ int kf_group_read_merge_ms(kf_group* g, float* total_ms, uint32_t* frames) {
   *frames = (uint32_t)g->ev_used;
   g->ev_used = 0;
   return 0;
+}
+
+int kf_group_shift_plan(uint32_t resolution, uint32_t members, const uint32_t* z_cuts, uint32_t halo, int32_t dz, kf_group_transfer* out, uint32_t cap) {
+  if (!layout_ok(resolution, members, z_cuts) || dz % 8 || (!out && cap)) return -1;
+  int n = 0;
+  for (uint32_t to = 0; to < members; ++to) {
+    uint32_t s0, s1, lo, hi;
+    stored_layers(resolution, z_cuts[to], z_cuts[to + 1], halo, &s0, &s1);
+    if (kf_slab_needs(resolution, s0, s1, dz, &lo, &hi)) return -1;      // the member's need range: libhybkf's own rule (kf_slab_shift_needs)
+    for (uint32_t from = 0; from < members && lo < hi; ++from) {      // the owners in layer order: the need range cut by who owns each layer
+      const uint32_t o1 = z_cuts[from + 1] / 8;                        // the owner of layer lo is the first member whose slab ends behind it
+      if (o1 <= lo) continue;
+      const uint32_t end = hi < o1 ? hi : o1;
+      if ((uint32_t)n < cap) { out[n].from_member = from; out[n].to_member = to; out[n].bz_begin = lo; out[n].bz_end = end; }
+      ++n;
+      lo = end;
+    }
+  }
+  return n;
+}
+
+int kf_group_shift_volume(kf_group* g, int32_t dx, int32_t dy, int32_t dz) {
+  if (!g) return KF_GROUP_ERR_ARG;
+  if (dx % 8 || dy % 8 || dz % 8) return KF_GROUP_ERR_ARG;
+  int32_t org[3];
+  if (kf_volume_origin(g->m[0], org)) return KF_GROUP_ERR_ARG;
+  const int32_t d[3] = {dx, dy, dz};
+  for (int k = 0; k < 3; ++k) { const int64_t o = (int64_t)org[k] + d[k]; if (o > INT32_MAX || o < INT32_MIN) return KF_GROUP_ERR_ARG; }
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  if (dx == 0 && dy == 0 && dz == 0) return 0;
+  DeviceGuard guard;
+  return fail(g, shift(g, dx, dy, dz));
+}
+
+int kf_group_raycast(kf_group* g) {
+  if (!g) return KF_GROUP_ERR_ARG;
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  DeviceGuard guard;
+  for (uint32_t i = 0; i < g->n; ++i) {
+    int st = (int)hipSetDevice(g->dev[i]);
+    if (!st) st = member_cross(g, i);
+    if (st) return fail(g, st);
+  }
+  return fail(g, merge(g));
+}
+
+int kf_group_volume_origin(kf_group* g, int32_t origin_vox[3]) {
+  if (!g || !origin_vox) return KF_GROUP_ERR_ARG;
+  if (g->failed) return KF_GROUP_ERR_STATE;
+  int st = kf_volume_origin(g->m[0], origin_vox);
+  for (uint32_t i = 1; i < g->n && !st; ++i) {
+    int32_t o[3];
+    if (!(st = kf_volume_origin(g->m[i], o)) && memcmp(o, origin_vox, sizeof(o))) return KF_GROUP_ERR_STATE;
+  }
+  return st;
 }
 
 int kf_group_synchronize(kf_group* g) {

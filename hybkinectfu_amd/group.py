@@ -28,7 +28,12 @@ SYMBOLS = [
     "kf_group_stream",
     "kf_group_create_color", "kf_group_validate_color", "kf_group_frame_color", "kf_group_frame_members_color",
     "kf_group_view_validate", "kf_group_render_view", "kf_group_view_size", "kf_group_view_device", "kf_group_read_view",
+    "kf_group_shift_plan", "kf_group_shift_volume", "kf_group_raycast", "kf_group_volume_origin",
 ]
+
+
+class Transfer(C.Structure):
+    _fields_ = [("from_member", C.c_uint32), ("to_member", C.c_uint32), ("bz_begin", C.c_uint32), ("bz_end", C.c_uint32)]
 
 
 class GroupParams(C.Structure):
@@ -50,6 +55,9 @@ def load():
         _lib.kf_group_error_string.restype = C.c_char_p
         _lib.kf_group_stream.restype = C.c_void_p
         _lib.kf_group_view_device.restype = C.c_void_p
+        _lib.kf_group_shift_plan.argtypes = [C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.c_uint32, C.c_int32, C.POINTER(Transfer), C.c_uint32]
+        _lib.kf_group_shift_volume.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.kf_group_volume_origin.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     return _lib
 
 
@@ -109,6 +117,19 @@ def validate_color_status(cfg, params, backend, cuts, devices=None, halo=0, uid=
 def view_validate_status(color_group, mode, cam):
     """kf_group_view_validate: the refusals of kf_group_render_view alone (no HIP call); cam: lib.camera or None"""
     return load().kf_group_view_validate(int(bool(color_group)), int(mode), C.byref(cam) if cam is not None else None)
+
+
+def shift_plan(res, cuts, halo, dz):
+    """kf_group_shift_plan: the transfers (from_member, to_member, bz_begin, bz_end) of a z shift by dz voxels, ordered by receiver, then by layer;
+    None for arguments the library refuses.  Host only"""
+    lib = load()
+    cuts_a = (C.c_uint32 * len(cuts))(*cuts)
+    n = lib.kf_group_shift_plan(int(res), len(cuts) - 1, cuts_a, int(halo), int(dz), None, 0)
+    if n < 0:
+        return None
+    out = (Transfer * max(n, 1))()
+    assert lib.kf_group_shift_plan(int(res), len(cuts) - 1, cuts_a, int(halo), int(dz), out, n) == n
+    return [(t.from_member, t.to_member, t.bz_begin, t.bz_end) for t in out[:n]]
 
 
 def create_status(cfg, params, backend, cuts, devices=None, halo=0, uid=None, rank=0, world=1):
@@ -247,6 +268,22 @@ class Group:
         if n.value:
             _chk(self.lib.kf_group_read_triangles(self.h, out.ctypes.data_as(C.c_void_p), 0, n.value), "kf_group_read_triangles")
         return out
+
+    # ---- the moving volume ----
+    def shift_volume(self, dx, dy, dz):
+        """the window moves by whole bricks on every member, brick layers travelling between members for a z shift; asynchronous.  The model maps
+        are stale afterwards: raycast() before the next frame (kf_group_shift_volume)"""
+        _chk(self.lib.kf_group_shift_volume(self.h, int(dx), int(dy), int(dz)), "kf_group_shift_volume")
+
+    def raycast(self):
+        """the merged raycast from the device-resident pose alone: steps 5-9 of a frame (kf_group_raycast)"""
+        _chk(self.lib.kf_group_raycast(self.h), "kf_group_raycast")
+
+    def volume_origin(self):
+        """(x, y, z): the sum of all shifts, in voxels; the members agree (kf_group_volume_origin)"""
+        o = (C.c_int32 * 3)()
+        _chk(self.lib.kf_group_volume_origin(self.h, o), "kf_group_volume_origin")
+        return tuple(o)
 
     # ---- merged views ----
     def render_view(self, mode, pose, cam, near, far, dev_v=None, dev_n=None):

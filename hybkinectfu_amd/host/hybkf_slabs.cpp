@@ -10,7 +10,16 @@ std::vector<unsigned> SlabLayout::evenCuts(unsigned resolution, unsigned members
   return cuts;
 }
 
-HybKinectfuSlabs::~HybKinectfuSlabs() { if (_group) kf_group_destroy(_group); _group = nullptr; }
+HybKinectfuSlabs::~HybKinectfuSlabs() {
+  delete _recorder; _recorder = nullptr;
+  if (_group) kf_group_destroy(_group);
+  _group = nullptr;
+}
+
+static float volume_cell() {                                   // KfVolume::cell: the fp32 quotient (tsdfVolume.h:44-46)
+  const AppParams* p = AppParams::instance();
+  return p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+}
 
 bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectfu::init (src/HybKinectfu.cpp:28-61) with a group for the data manager
   if (_inited) return false;
@@ -45,6 +54,7 @@ bool HybKinectfuSlabs::init(const SlabLayout& layout) {            // HybKinectf
   kf_mat44 k; memcpy(k.m, camera_pose0.entries, sizeof(k.m));
   if (!check(kf_group_set_pose(_group, &k))) return false;
   _pose = camera_pose0;
+  if (p->_switch_params.recordTrajectory) _recorder = new TrajectoryRecorder(p->_io_params.trajWriteFilename);
   _inited = true;
   return true;
 }
@@ -64,7 +74,43 @@ bool HybKinectfuSlabs::enqueueFrame(const DepthFrameData& d, const ColorFrameDat
 }
 
 bool HybKinectfuSlabs::processNewFrame(const DepthFrameData& d, const ColorFrameData& c) {   // :98-160
-  return enqueueFrame(d, c) && syncVerdict();
+  if (!enqueueFrame(d, c) || !syncVerdict()) return false;
+  if (_last_tracked && _recorder) {                             // HybKinectfu::processNewFrame: the pose in world coordinates, before the window moves
+    int o[3]; volumeOrigin(o);
+    const int32_t o32[3] = {o[0], o[1], o[2]};
+    Mat44 w = _pose;
+    hkf_world_pose(w.entries, o32, volume_cell());
+    _recorder->recordCameraPose(w, d.timeStamp());
+  }
+  if (_last_tracked && AppParams::instance()->_volume_params.fRecentreDist > 0.f) return recentre();
+  return true;
+}
+
+// ---- the moving volume (HybKinectfu::shiftVolume / volumeOrigin / recentre over the group) ------------------------------------------------------
+void HybKinectfuSlabs::volumeOrigin(int out[3]) {
+  int32_t o[3] = {0, 0, 0};
+  if (_inited) check(kf_group_volume_origin(_group, o));
+  for (int k = 0; k < 3; ++k) out[k] = (int)o[k];
+}
+
+bool HybKinectfuSlabs::shiftVolume(int dx, int dy, int dz) {
+  if (!_inited) return false;
+  lastTracked();                                                // the host's pose is the one the members hold
+  if (!check(kf_group_shift_volume(_group, dx, dy, dz))) return false;
+  if (dx == 0 && dy == 0 && dz == 0) return true;
+  const float cell = volume_cell();                             // the same expression as on the device
+  _pose.entries[3] = _pose.entries[3] - (float)dx * cell;
+  _pose.entries[7] = _pose.entries[7] - (float)dy * cell;
+  _pose.entries[11] = _pose.entries[11] - (float)dz * cell;
+  return check(kf_group_raycast(_group));
+}
+
+bool HybKinectfuSlabs::recentre() {
+  const AppParams* p = AppParams::instance();
+  int32_t d[3];
+  hkf_recentre_shift(_pose.entries, p->_volume_params.fVolumeMeterSize, p->_volume_params.nResolution, p->_volume_params.fRecentreDist, d);
+  if (d[0] == 0 && d[1] == 0 && d[2] == 0) return true;
+  return shiftVolume(d[0], d[1], d[2]);
 }
 
 bool HybKinectfuSlabs::syncVerdict() {
@@ -128,5 +174,8 @@ bool HybKinectfuSlabs::saveMesh(const std::string& filename) {   // :61-96 on th
   if (!check(kf_group_read_triangles(_group, tris.data(), 0, n))) return false;
   _mesh.setTriangles(tris.data(), n, _color);
   _mesh.weldMesh();
+  int o[3]; volumeOrigin(o);                                   // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
+  const int32_t o32[3] = {o[0], o[1], o[2]};
+  hkf_world_positions(_mesh.data().vertices.data(), _mesh.data().vertices.size() / 3, o32, volume_cell());
   return _mesh.mesh().saveToFile(filename);
 }

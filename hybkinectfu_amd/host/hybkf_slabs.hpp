@@ -46,13 +46,26 @@ public:
   // whole volume's picture): any camera, from `pose` (nullptr: the current camera pose, device-resident on every member); the increment and the
   // planes come from AppParams, as processNewFrame uses them; it leaves tracking state alone.  Blocking (the read-back).
   bool renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra);
+  // The moving volume, with HybKinectfu's semantics (hybkf_host.hpp).  shiftVolume: kf_group_shift_volume by (dx, dy, dz) voxels, multiples of 8 -- brick
+  // layers travel between the members for a z shift --, then the merged raycast (kf_group_raycast), so every member's model maps show the new window
+  // before the next frame is tracked.  false: not initialised, or the shift was refused.  volumeOrigin: the sum of all shifts, in voxels.
+  // With AppParams::_volume_params.fRecentreDist > 0 processNewFrame recentres by itself after a tracked frame (hkf_recentre_shift on the pose it has
+  // just waited for); enqueueFrame never does: it holds no host pose to decide on.  getCameraPose stays in the window's coordinates; the recorded
+  // trajectory (switch recordTrajectory, AppParams::_io_params.trajWriteFilename) and saved meshes are in WORLD coordinates (hkf_world_pose /
+  // hkf_world_positions); with a zero origin every byte is what it always was.  A group's window forgets what leaves it: brick store, stream-out
+  // and map mesh (nBrickStoreBricks, nStreamMeshTriangles, bMapMesh) are HybKinectfu's alone.
+  bool shiftVolume(int dx, int dy, int dz);
+  void volumeOrigin(int out[3]);
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:
+  struct SlabMesh : MeshGeneratorMarchingcube { MeshData& data() { return _meshes; } };
   bool check(int status) { if (status) _err = status; return status == 0; }
   bool syncVerdict();
+  bool recentre();
   kf_group* _group = nullptr;
-  MeshGeneratorMarchingcube _mesh;
+  SlabMesh _mesh;
+  TrajectoryRecorder* _recorder = nullptr;                   // switch recordTrajectory, as in HybKinectfu
   Mat44 _pose = Mat44::getIdentity();
   bool _inited = false, _last_tracked = true, _pending = false, _color = false;
   int _err = 0;

@@ -3,7 +3,10 @@
 #include <string.h>
 
 static HybKinectfuSlabs* g_slabs = nullptr;
+#include <string>
+
 static struct { bool use_rgb = false, angle_weight = true; } g_switch;      // [Switch] useRGBData / colorAngleWeight, applied by hkf_slabs_init
+static std::string g_traj_write;                                            // [IO] trajWriteFilename + [Switch] recordTrajectory, applied by hkf_slabs_init
 
 extern "C" {
 
@@ -23,6 +26,7 @@ int hkf_slabs_init(unsigned volume_res, float volume_size, unsigned depth_cols, 
   p->device = device;
   p->_switch_params.useRGBData = g_switch.use_rgb;
   if (g_switch.use_rgb) p->_switch_params.colorAngleWeight = g_switch.angle_weight;
+  p->_io_params.trajWriteFilename = g_traj_write; p->_switch_params.recordTrajectory = !g_traj_write.empty();
   delete g_slabs; g_slabs = nullptr;
   SlabLayout layout;
   layout.backend = backend;
@@ -36,6 +40,8 @@ int hkf_slabs_init(unsigned volume_res, float volume_size, unsigned depth_cols, 
 }
 // call BEFORE hkf_slabs_init: useRGBData (and, with it, colorAngleWeight) for the next init; off until called
 void hkf_slabs_configure_color(int use_rgb, int angle_weight) { g_switch.use_rgb = use_rgb != 0; g_switch.angle_weight = angle_weight != 0; }
+// call BEFORE hkf_slabs_init: the trajectory file of the next init (NULL / empty: none), as hkf_app_configure_io's traj_write
+void hkf_slabs_configure_traj(const char* traj_write) { g_traj_write = traj_write ? traj_write : ""; }
 void hkf_slabs_shutdown() { delete g_slabs; g_slabs = nullptr; }
 void* hkf_slabs_group() { return g_slabs ? (void*)g_slabs->group() : nullptr; }
 
@@ -44,6 +50,15 @@ int hkf_slabs_process_frame(const uint16_t* mm, int on_device, unsigned frame_id
   if (!g_slabs) return -1;
   const CameraParams& c = AppParams::instance()->_depth_camera_params;
   DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = on_device != 0;
+  ColorFrameData col;
+  if (!g_slabs->processNewFrame(d, col)) return -2;
+  return g_slabs->lastTracked() ? 1 : 0;
+}
+// the same with the frame's time stamp (what the trajectory recorder writes), as hkf_app_process_frame
+int hkf_slabs_process_frame_stamped(const uint16_t* mm, int on_device, unsigned frame_id, double stamp) {
+  if (!g_slabs) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.time_stamp = stamp; d.on_device = on_device != 0;
   ColorFrameData col;
   if (!g_slabs->processNewFrame(d, col)) return -2;
   return g_slabs->lastTracked() ? 1 : 0;
@@ -107,5 +122,10 @@ int hkf_slabs_render_view(int mode, const float* pose16, unsigned cols, unsigned
   memcpy(out, img.data(), img.size());
   return 0;
 }
+// the moving volume: HybKinectfuSlabs::shiftVolume / volumeOrigin, and AppParams::_volume_params.fRecentreDist (call AFTER hkf_slabs_init, which restores
+// the defaults; 0 = off), as hkf_app_*.  hkf_slabs_shift_volume: 1 shifted, 0 refused, -1 without a group
+int hkf_slabs_shift_volume(int dx, int dy, int dz) { if (!g_slabs) return -1; return g_slabs->shiftVolume(dx, dy, dz) ? 1 : 0; }
+int hkf_slabs_volume_origin(int out3[3]) { if (!g_slabs) return -1; g_slabs->volumeOrigin(out3); return 0; }
+int hkf_slabs_set_recentre(float dist) { if (!g_slabs) return -1; AppParams::instance()->_volume_params.fRecentreDist = dist; return 0; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

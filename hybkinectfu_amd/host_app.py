@@ -176,8 +176,11 @@ def load_slabs():
 class SlabsApp:
     """HybKinectfuSlabs through hkf_slabs_*: the application over a slab group (one per process).  backend / cuts: hybkf_group.h"""
 
-    def __init__(self, res, size, cam, cuts, backend=0, max_triangles=0, sdf_trunc=0.0, integrate_dist=0.0, trunc_max=0.0, device=0, halo=0):
+    def __init__(self, res, size, cam, cuts, backend=0, max_triangles=0, sdf_trunc=0.0, integrate_dist=0.0, trunc_max=0.0, device=0, halo=0,
+                 traj_write=""):
+        """traj_write: record the tracked poses there (TrajectoryRecorder), in world coordinates"""
         self.h = load_slabs()
+        self.h.hkf_slabs_configure_traj(traj_write.encode())
         cuts_a = (C.c_uint32 * len(cuts))(*cuts)
         st = self.h.hkf_slabs_init(res, C.c_float(size), cam[0], cam[1], C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
                                    max_triangles, C.c_float(sdf_trunc), C.c_float(integrate_dist), C.c_float(trunc_max), device, backend,
@@ -186,12 +189,39 @@ class SlabsApp:
             raise K.KfError("hkf_slabs_init failed: %d" % st)
         self.cam = cam
 
-    def process_frame(self, mm, frame_id):
+    def process_frame(self, mm, frame_id, stamp=0.0):
         mm = np.ascontiguousarray(mm, np.uint16)
-        r = self.h.hkf_slabs_process_frame(mm.ctypes.data_as(C.c_void_p), 0, frame_id)
+        r = self.h.hkf_slabs_process_frame_stamped(mm.ctypes.data_as(C.c_void_p), 0, frame_id, C.c_double(stamp))
         if r < 0:
             raise K.KfError("processNewFrame failed: %d" % r)
         return bool(r)
+
+    def shift_volume(self, dx, dy, dz):
+        """HybKinectfuSlabs::shiftVolume: the group's window moves by (dx, dy, dz) voxels (multiples of 8), then the merged raycast; False: refused"""
+        r = self.h.hkf_slabs_shift_volume(int(dx), int(dy), int(dz))
+        if r < 0:
+            raise K.KfError("hkf_slabs_shift_volume: no group")
+        return bool(r)
+
+    def volume_origin(self):
+        """HybKinectfuSlabs::volumeOrigin: the sum of all shifts, in voxels"""
+        o = (C.c_int * 3)()
+        if self.h.hkf_slabs_volume_origin(o) != 0:
+            raise K.KfError("hkf_slabs_volume_origin: no group")
+        return tuple(int(x) for x in o)
+
+    def set_recentre(self, dist):
+        """AppParams::_volume_params.fRecentreDist for the slab class, as App.set_recentre (0: off, the default)"""
+        if self.h.hkf_slabs_set_recentre(C.c_float(dist)) != 0:
+            raise K.KfError("hkf_slabs_set_recentre: no group")
+
+    def generate_mesh(self):
+        return self.h.hkf_slabs_generate_mesh()
+
+    def save_mesh(self, filename):
+        nv, nf = C.c_uint32(), C.c_uint32()
+        ok = self.h.hkf_slabs_save_mesh(filename.encode(), C.byref(nv), C.byref(nf))
+        return bool(ok), nv.value, nf.value
 
     def pose(self):
         out = np.zeros(16, np.float32)
@@ -221,6 +251,7 @@ class SlabsApp:
 
     def close(self):
         self.h.hkf_slabs_shutdown()
+        self.h.hkf_slabs_configure_traj(b"")
 
 
 # ---- GPU-free helpers of the dataset / trajectory code -------------------------------------------------------------------------

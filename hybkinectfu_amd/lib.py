@@ -122,6 +122,7 @@ SYMBOLS = [
     "kf_append_world_soup", "kf_set_stream_out",
     "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
+    "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
 
 
@@ -168,6 +169,11 @@ def load():
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
         _lib.kf_map_tile_frames.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64]
         _lib.kf_map_tile_frames.restype = C.c_int64
+        _lib.kf_slab_layer_bytes.argtypes = [C.c_void_p]
+        _lib.kf_slab_layer_bytes.restype = C.c_size_t
+        _lib.kf_slab_shift_needs.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        _lib.kf_slab_pack_layers.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        _lib.kf_shift_slab.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_uint32, C.c_uint32]
     return _lib
 
 
@@ -672,6 +678,26 @@ class Context:
     def append_world_soup(self):
         """device to device: the world soup behind what the triangle buffer holds, clamped (kf_append_world_soup)"""
         _chk(self.lib.kf_append_world_soup(self.h), "kf_append_world_soup")
+
+    def slab_layer_bytes(self):
+        """bytes of one brick layer in transit between two members (kf_slab_layer_bytes)"""
+        return int(self.lib.kf_slab_layer_bytes(self.h))
+
+    def slab_shift_needs(self, dz):
+        """(bz_begin, bz_end): the global brick layers this context must be fed for a z shift of dz; (0, 0) when none (kf_slab_shift_needs)"""
+        a, b = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_slab_shift_needs(self.h, int(dz), C.byref(a), C.byref(b)), "kf_slab_shift_needs")
+        return a.value, b.value
+
+    def pack_layers(self, bz_begin, bz_end, dev_dst):
+        """stored brick layers [bz_begin, bz_end) into the device buffer at address dev_dst, in the transit layout; asynchronous (kf_slab_pack_layers)"""
+        _chk(self.lib.kf_slab_pack_layers(self.h, int(bz_begin), int(bz_end), C.c_void_p(int(dev_dst))), "kf_slab_pack_layers")
+
+    def shift_slab(self, dx, dy, dz, dev_feed=None, feed=(0, 0)):
+        """shift_volume for a context that stores only some brick layers: dev_feed (a device address) holds the brick layers `feed` = slab_shift_needs(dz)
+        as their owners packed them; asynchronous, the model maps are stale afterwards (kf_shift_slab)"""
+        _chk(self.lib.kf_shift_slab(self.h, int(dx), int(dy), int(dz), C.c_void_p(int(dev_feed)) if dev_feed else None, int(feed[0]), int(feed[1])),
+             "kf_shift_slab")
 
     def set_stream_out(self, on, thr=0.0, has_color=False):
         """on: every shift_volume first extracts the surface that is about to leave into the world soup (kf_set_stream_out)"""

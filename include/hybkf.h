@@ -445,6 +445,40 @@ int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /*
 int kf_shift_volume(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz);
 int kf_volume_origin(kf_ctx* ctx, int32_t origin_vox[3]);
 
+/* The moving volume on z-slab contexts (slabshift.hip): what a slab group runs on its members (hybkf_group.h: kf_group_shift_volume).  kf_shift_volume
+ * itself keeps refusing a z-slab context.  A context stores brick layers [bz0, bz1) = kf_stored_z_range / 8.
+ * THE RULE: stored destination brick (bx, by, p) takes source brick (bx + dx/8, by + dy/8, p + dz/8) -- from the context's own copy where that layer is
+ *   stored here (owned or halo: a halo layer holds its owner's bits), else from the feed buffer where the layer lies in the feed range, else it reads
+ *   as never observed; a source whose x or y lies outside the volume reads as never observed too.  So halo layers become owned layers and back.
+ * THE TRANSIT LAYOUT of one brick layer, kf_slab_layer_bytes(ctx) bytes (n = (resolution / 8)^2 bricks, brick (bx, by) at index by * (resolution / 8) + bx):
+ *   n x 4 KiB of (tsdf, weight), brick after brick as they lie in the volume (voxel (x, y, z) of a brick at ((z & 7) << 6 | (y & 7) << 3 | (x & 7)));
+ *   then, on a context with a colour plane, n x 2 KiB of colour (4 bytes per voxel, same order); then n 8-byte deferred-weight words, padded to a
+ *   multiple of 16 bytes.  The layers of a range follow each other at that pitch.  It is what two members exchange.  0 for a NULL context.
+ * kf_slab_shift_needs: host bookkeeping, never blocks.  The half-open range of GLOBAL brick layers this context must be fed for a z shift of dz: the
+ *   source layers p + dz/8 of its stored layers p that lie in [0, resolution / 8) and are not stored here.  Always one range; (0, 0) when empty
+ *   (dz = 0, a whole-volume context, a shift out of the volume).  KF_ERR_ARG for a dz that is no multiple of 8.
+ *   kf_slab_needs: the same rule without a context, for stored voxel layers [stored_z_begin, stored_z_end) (kf_stored_z_range's) of a volume of
+ *   `resolution` -- what a planner uses (kf_group_shift_plan); no HIP call.  KF_ERR_ARG for a range that is empty, not brick-aligned or outside.
+ * kf_slab_pack_layers: asynchronous on the context's stream.  The stored brick layers [bz_begin, bz_end) into the caller's device buffer dev_dst
+ *   ((bz_end - bz_begin) * kf_slab_layer_bytes bytes, 16-byte aligned) in the transit layout, x and y as they lie.  The deferred weights are
+ *   flushed first, so the bytes do not depend on how a brick's weights were split between voxels and word: the words are states that travel
+ *   verbatim.  KF_ERR_ARG for an empty range or one not stored here.
+ * kf_shift_slab: kf_shift_volume's move under the rule above, in place, the planes walked in the safe order; the same pass rebuilds flags,
+ *   has-negative bits and the context's skip tables; the deferred-weight words travel with their bricks.  The bookkeeping is kf_shift_volume's: the
+ *   device-resident pose moves (every member of a group gets the same bits), kf_volume_origin advances, the observed-voxel count is re-based, and
+ *   THE MODEL MAPS ARE STALE afterwards.  The owned and stored ranges do not change: they are window coordinates.  dev_feed holds the layers
+ *   [feed_bz_begin, feed_bz_end) in the transit layout and is read in stream order.  Asynchronous: no allocation, no synchronisation.
+ *   On a whole-volume context the need is empty and the call is kf_shift_volume without brick store or stream-out, bit for bit.
+ *   A z shift wider than the slab is legal: the whole destination then comes from the feed or reads as never observed.
+ *   Refused with nothing touched -- KF_ERR_ARG: a component that is no multiple of 8; a feed range that is not exactly kf_slab_shift_needs' (an empty
+ *   need takes any empty range); a NULL feed with a non-empty need; a sum of shifts beyond 32 bits.  KF_ERR_STATE: a brick store reserved or
+ *   stream-out on -- those stay whole-volume features of kf_shift_volume; a slab's window forgets what leaves it. */
+size_t kf_slab_layer_bytes(kf_ctx* ctx);
+int kf_slab_shift_needs(kf_ctx* ctx, int32_t dz, uint32_t* bz_begin, uint32_t* bz_end);
+int kf_slab_needs(uint32_t resolution, uint32_t stored_z_begin, uint32_t stored_z_end, int32_t dz, uint32_t* bz_begin, uint32_t* bz_end);
+int kf_slab_pack_layers(kf_ctx* ctx, uint32_t bz_begin, uint32_t bz_end, void* dev_dst);
+int kf_shift_slab(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz, const void* dev_feed, uint32_t feed_bz_begin, uint32_t feed_bz_end);
+
 /* Streaming the departing surface into a world mesh (no reference counterpart).  kf_shift_volume overwrites what leaves the window; these
  * entry points keep its surface: a marching cubes limited to a box of cells, and a second, context-owned triangle buffer in WORLD coordinates
  * (world position = volume position + origin * cell, see kf_volume_origin) that outlives the window the triangles were extracted under.

@@ -152,6 +152,36 @@ int kf_group_read_triangles(kf_group* g, kf_triangle* dst, uint32_t first, uint3
 int kf_group_merge_timing(kf_group* g, int on);
 int kf_group_read_merge_ms(kf_group* g, float* total_ms, uint32_t* frames);
 int kf_group_synchronize(kf_group* g);
+
+/* The moving volume over a group (hybkf.h: kf_shift_volume, and kf_shift_slab for THE RULE and the transit layout).  A group shifts its window by whole
+ * bricks on any axis, in place and on the members' streams; every member's stored layers -- owned and halo -- end up bit for bit what a whole-volume
+ * context holds there after kf_shift_volume.  An x or y shift is local to every member; a z shift moves brick layers between members.
+ * kf_group_shift_plan: the transfers of a z shift by dz voxels, host only (no HIP or RCCL call) -- the one place the rule "who feeds whom" lives, and what
+ *   kf_group_shift_volume executes.  For every member (stored brick layers: its slab of z_cuts plus `halo` voxel layers on each side, rounded up to
+ *   bricks, clamped to the volume) it takes the need range -- the source layers p + dz / 8 of its stored layers p that lie inside the volume and are not
+ *   stored there (kf_slab_shift_needs) -- and cuts it by who OWNS each layer: the member j whose [z_cuts[j], z_cuts[j + 1]) holds it.  Layers nobody has
+ *   to send (they lie outside the volume) read as never observed.  Order: by receiver, then by layer.  Writes at most `cap` transfers and returns their
+ *   number (call again with a larger buffer if it exceeds cap), or -1 for bad arguments: a resolution that is no multiple of 8, cuts that do not tile
+ *   [0, resolution) rising in multiples of 8, a dz that is no multiple of 8, out NULL with cap > 0.
+ * kf_group_shift_volume: asynchronous on the members' streams, three steps --
+ *   1. every owner packs what the plan sends (kf_slab_pack_layers): LOCAL straight into the receiver's feed buffer at the layer's offset, RCCL into a
+ *      send buffer;   2. the exchange: LOCAL needs none (one stream: every pack precedes every move), RCCL_ALL / RCCL_RANK ncclSend / ncclRecv of bytes
+ *      inside one ncclGroupStart / End on the members' streams;   3. kf_shift_slab on every member with its feed.
+ *   Every pack of the whole group precedes every move: an owner's layers leave before it overwrites them.  Feed and send buffers are the group's own,
+ *   sized to the plan (not to the slab), grow on demand (only then does the call block) and are freed by kf_group_destroy.  The cuts do not change
+ *   (re-balancing stays kf_resize_slab's job); brick store, stream-out and map mesh stay whole-volume features: a group's window forgets what leaves.
+ *   KF_GROUP_RCCL_RANK: the call is collective; the first shift all-gathers the ranks' (z0, z1) once (blocking) and keeps them, so every rank derives
+ *   the same plan.  d = (0, 0, 0) returns 0 and enqueues nothing.  KF_GROUP_ERR_ARG, with nothing enqueued, no collective issued and the group still
+ *   usable: a component that is no multiple of 8, a sum of shifts beyond 32 bits.  A failure mid-sequence puts the group into the failed state.
+ *   THE MODEL MAPS ARE STALE on every member afterwards: call kf_group_raycast before the next frame.
+ * kf_group_raycast: steps 5-9 of kf_group_frame alone -- the merged raycast from the device-resident pose, in the colour forms on a colour group;
+ *   the whole-volume counterpart is kf_raycast_volume(transform = NULL).  Asynchronous; collective on RCCL_RANK.
+ * kf_group_volume_origin: member 0's kf_volume_origin; in-process members that disagree give KF_GROUP_ERR_STATE. */
+typedef struct kf_group_transfer { uint32_t from_member, to_member, bz_begin, bz_end; } kf_group_transfer;   /* brick layers [bz_begin, bz_end) */
+int kf_group_shift_plan(uint32_t resolution, uint32_t members, const uint32_t* z_cuts, uint32_t halo, int32_t dz, kf_group_transfer* out, uint32_t cap);
+int kf_group_shift_volume(kf_group* g, int32_t dx, int32_t dy, int32_t dz);
+int kf_group_raycast(kf_group* g);
+int kf_group_volume_origin(kf_group* g, int32_t origin_vox[3]);
 /* the stream member i's work is enqueued on (LOCAL: the one group stream) */
 void* kf_group_stream(kf_group* g, uint32_t i);
 
