@@ -120,7 +120,7 @@ extern "C" int kf_destroy(kf_ctx* c) {
   if (c->own_stream) hipStreamSynchronize(c->own_stream);
   void* ptrs[] = {c->up_dev[0], c->up_dev[1], c->up_dev[2], c->raw_depth, c->trunced_depth, c->filtered_depth, c->raw_rgb, c->raycast_rgb, c->icp_partials, c->icp_loop_slots,
                   c->track, c->counters, c->scratch_mats, c->vol.tw, c->vol.color, c->vol.flags, c->vol.macrobits, c->vol.negbits, c->vol.pend, c->layer_work, c->active_bricks,
-                  c->tile_max_depth, c->view_img, c->triangles, c->mc_block_counts, c->mc_list, c->mc_nbr_bits, c->mc_partials, c->mc_codes, c->mc_surv, c->mc_block_bits, c->mc_recs, c->mc_d1_list, c->mc_vtab};
+                  c->tile_max_depth, c->view_img, c->triangles, c->mc_block_counts, c->mc_list, c->mc_nbr_bits, c->mc_partials, c->mc_codes, c->mc_surv, c->mc_block_bits, c->mc_recs, c->mc_d1_list, c->mc_vtab, c->view_at_scratch};
   for (void* p : ptrs) if (p) hipFree(p);
   kf_weld_free(c);
   kf_world_soup_free(c);
@@ -669,10 +669,10 @@ extern "C" int kf_resize_slab(kf_ctx* c, uint32_t z_begin, uint32_t z_end, uint3
     return st;
   }
   void* old[] = {v.tw, v.color, v.flags, v.negbits, v.pend, c->active_bricks, c->mc_block_counts,
-                 c->mc_list, c->mc_nbr_bits, c->mc_partials, c->mc_codes, c->mc_surv, c->mc_block_bits, c->mc_recs, c->mc_d1_list, c->mc_vtab};
+                 c->mc_list, c->mc_nbr_bits, c->mc_partials, c->mc_codes, c->mc_surv, c->mc_block_bits, c->mc_recs, c->mc_d1_list, c->mc_vtab, c->view_at_scratch};
   for (void* p : old) if (p) hipFree(p);
   v.tw = tw; v.color = color; v.flags = flags; v.negbits = negbits; v.pend = pend; c->active_bricks = queue; c->mc_block_counts = mc_counts;
-  c->mc_list = nullptr; c->mc_nbr_bits = nullptr; c->mc_partials = nullptr; c->mc_codes = nullptr; c->mc_surv = nullptr; c->mc_block_bits = nullptr; c->mc_recs = nullptr; c->mc_d1_list = nullptr; c->mc_vtab = nullptr;
+  c->mc_list = nullptr; c->mc_nbr_bits = nullptr; c->mc_partials = nullptr; c->mc_codes = nullptr; c->mc_surv = nullptr; c->mc_block_bits = nullptr; c->mc_recs = nullptr; c->mc_d1_list = nullptr; c->mc_vtab = nullptr; c->view_at_scratch = nullptr;
   v.bz0 = nb0; v.bz1 = nb1; v.own_z0 = (int)z_begin; v.own_z1 = (int)z_end;
   c->cfg.slab_z_begin = z_begin; c->cfg.slab_z_end = z_end; c->cfg.slab_halo = halo;
   c->n_stored_bricks = n_new; c->n_stored_vox = n_new * KF_BRICK_VOX; c->mc_blocks_cap = (c->n_stored_vox + 255) / 256;

@@ -267,6 +267,9 @@ struct kf_ctx {
   // the virtual window of kf_marching_cubes_at (mapmesh.hip): one all-zero brick (4 KiB), then 16 bytes per brick slot -- where that brick's voxels and colours
   // are read from.  Part of the extraction scratch: allocated by the first kf_marching_cubes_at, freed with the rest.
   void* mc_vtab;
+  // the virtual window of kf_render_view_at (viewat.hip), the call's own scratch: one all-zero brick (4 KiB), 16 bytes per brick slot, the virtual skip tables
+  // (kf_skip_table_words), the virtual has-negative bits (kf_negbit_words) and 16 floats of pose.  Allocated by the first call, freed with the volume's planes.
+  void* view_at_scratch;
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,

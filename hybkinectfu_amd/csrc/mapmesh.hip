@@ -24,50 +24,11 @@
 #include "brick_key.h"
 #include "brick_find.h"
 #include "map_tiles.h"
+#include "vwindow.h"
 #include <stdint.h>
 #include <vector>
 
 namespace mapmesh {
-
-struct McVBrick { const float2* tw; const uchar4* color; };        // one virtual brick slot: its 512 (tsdf, weight) pairs, its 512 colours
-
-// the eight gathers of a lookup (kf_interp_load) through the table
-__device__ __forceinline__ void v_interp_load(const McVBrick* __restrict__ tab, const KfVolume& v, const KfInterp& it, float2 q[8]) {
-#pragma unroll
-  for (int k = 0; k < 8; ++k) q[k] = make_float2(0.f, 0.f);
-  if (it.ok) {
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const int x = it.g.x + (k >> 2), y = it.g.y + ((k >> 1) & 1), z = it.g.z + (k & 1);
-      q[k] = tab[kf_brick_slot(v, x >> 3, y >> 3, z >> 3)].tw[((z & 7) << 6) | ((y & 7) << 3) | (x & 7)];
-    }
-  }
-}
-// kf_interpolate_color through the table: the same arithmetic in the same order
-__device__ __forceinline__ bool v_interp_color(const McVBrick* __restrict__ tab, const KfVolume& v, float3 pos, uchar4& out) {
-  int3 g; float a, b, c;
-  if (!kf_interp_params(v, pos, g, a, b, c)) return false;
-  if (!kf_z_stored(v, g.z) || !kf_z_stored(v, g.z + 1)) return false;
-  float ia = 1 - a, ib = 1 - b, ic = 1 - c;
-  float wgt[8]; uchar4 col[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    const int x = g.x + (k >> 2), y = g.y + ((k >> 1) & 1), z = g.z + (k & 1);
-    const McVBrick e = tab[kf_brick_slot(v, x >> 3, y >> 3, z >> 3)];
-    const int o = ((z & 7) << 6) | ((y & 7) << 3) | (x & 7);
-    wgt[k] = e.tw[o].y; col[k] = e.color[o];
-  }
-  float acc[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-  for (int k = 0; k < 8; ++k) {
-    if (wgt[k] == 0.f) return false;
-    float wa = (k >> 2) ? a : ia, wb = ((k >> 1) & 1) ? b : ib, wc = (k & 1) ? c : ic;
-    float t0 = (float)col[k].x * wa * wb * wc, t1 = (float)col[k].y * wa * wb * wc, t2 = (float)col[k].z * wa * wb * wc;
-    acc[0] = (k == 0) ? t0 : acc[0] + t0; acc[1] = (k == 0) ? t1 : acc[1] + t1; acc[2] = (k == 0) ? t2 : acc[2] + t2;
-  }
-  out = make_uchar4((unsigned char)acc[0], (unsigned char)acc[1], (unsigned char)acc[2], 0);
-  return true;
-}
 
 // The hooks of mc_kernels.h for the virtual window.  McArgs::vol is the window's KfVolume for its shape (res, nb, cell, size) with `negbits` pointing at the
 // VIRTUAL has-negative bits; its voxel, colour and flag pointers are not used by any kernel compiled here.
@@ -80,9 +41,7 @@ __device__ __forceinline__ bool v_interp_color(const McVBrick* __restrict__ tab,
 #define MC_REGION_ONLY
 #include "mc_kernels.h"
 
-// ---- resolve -------------------------------------------------------------------------------------------------------------------------------
-// wlo, wn: the widened brick range of the virtual window; fb: the frame's origin in world bricks; ob: the window's
-struct McResolve { int wlo[3], wn[3], fb[3], ob[3]; };
+// ---- resolve (vwindow.h: map_resolve_brick, shared with kf_render_view_at) ------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_map_resolve(KfVolume v, KfBrickStore st, McResolve g, McVBrick* __restrict__ vtab, const float2* __restrict__ zero,
                                                      unsigned* __restrict__ vneg) {
   const unsigned n = (unsigned)g.wn[0] * (unsigned)g.wn[1] * (unsigned)g.wn[2];
@@ -92,27 +51,8 @@ __global__ void __launch_bounds__(256) k_map_resolve(KfVolume v, KfBrickStore st
     const int bx = g.wlo[0] + (int)(i % (unsigned)g.wn[0]), by = g.wlo[1] + (int)((i / (unsigned)g.wn[0]) % (unsigned)g.wn[1]);
     const int bz = g.wlo[2] + (int)(i / ((unsigned)g.wn[0] * (unsigned)g.wn[1]));
     const unsigned vslot = ((unsigned)bz * (unsigned)nb + (unsigned)by) * (unsigned)nb + (unsigned)bx;
-    const int wx = g.fb[0] + bx, wy = g.fb[1] + by, wz = g.fb[2] + bz;                             // the world brick
-    const int lx = wx - g.ob[0], ly = wy - g.ob[1], lz = wz - g.ob[2];                             // ... in the window's bricks
-    McVBrick e; e.tw = zero; e.color = reinterpret_cast<const uchar4*>(zero);
-    bool neg = false;
-    if ((unsigned)lx < (unsigned)nb && (unsigned)ly < (unsigned)nb && (unsigned)lz < (unsigned)nb) {
-      const size_t s = ((size_t)lz * nb + (size_t)ly) * nb + (size_t)lx;
-      e.tw = v.tw + s * KF_BRICK_VOX;
-      if (v.color) e.color = v.color + s * KF_BRICK_VOX;
-      neg = (v.negbits[s >> 5] >> (s & 31u)) & 1u;
-    } else if (st.max_bricks) {
-      const unsigned s = store_find(st, kf_brick_key_pack(wx, wy, wz));
-      if (s != KF_BRICK_NO_SLOT) {
-        e.tw = st.tw + (size_t)s * KF_BRICK_VOX;
-        if (st.color) e.color = st.color + (size_t)s * KF_BRICK_VOX;
-        const float4* p = reinterpret_cast<const float4*>(e.tw);
-        bool mine = false;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { const float4 q = p[lane + 64u * (unsigned)k]; mine = mine || q.x < 0.f || q.z < 0.f; }
-        neg = __ballot(mine) != 0ull;
-      }
-    }
+    bool neg;
+    const McVBrick e = map_resolve_brick(v, st, g, bx, by, bz, zero, lane, neg);
     if (lane == 0) {
       vtab[vslot] = e;
       if (neg) atomicOr(&vneg[vslot >> 5], 1u << (vslot & 31u));
@@ -129,15 +69,6 @@ static int vtab_scratch(kf_ctx* c) {
   if (m != hipSuccess) { hipFree(p); return (int)m; }
   c->mc_vtab = p;
   return 0;
-}
-
-// does every brick of the frame at `fo` (voxels, multiples of 8) have a key?
-static bool frame_in_key_range(const int32_t fo[3], int nb) {
-  for (int k = 0; k < 3; ++k) {
-    const int64_t b = fo[k] / KF_BRICK;
-    if (!kf_brick_key_in_range(b) || !kf_brick_key_in_range(b + nb - 1)) return false;
-  }
-  return true;
 }
 
 // kf_marching_cubes_at past its argument checks

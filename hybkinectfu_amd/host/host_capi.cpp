@@ -109,6 +109,26 @@ int hkf_app_render_view(int mode, const float* pose16, unsigned cols, unsigned r
   if (!g_app->renderView(pose16 ? &m : nullptr, cam, mode, img)) return -2;
   return copy_view(img, out, out_cap);
 }
+// HybKinectfu::renderViewAt / renderMapView with hkf_app_render_view's arguments and return values.  frame3: the window's origin in voxels of the first
+// cube; pose16 of hkf_app_render_view_at in that frame's coordinates (NULL: the current camera pose), world_pose16 of hkf_app_render_map_view in the first cube's
+int hkf_app_render_view_at(int mode, const int* frame3, const float* pose16, unsigned cols, unsigned rows, float cx, float cy, float fx, float fy, uint8_t* out, size_t out_cap) {
+  if (!g_app) return -1;
+  if (!frame3) return -2;
+  Mat44 m; if (pose16) memcpy(m.entries, pose16, 64);
+  const kf_camera_params cam = {cols, rows, cx, cy, fx, fy};
+  std::vector<uint8_t> img;
+  if (!g_app->renderViewAt(mode, frame3, pose16 ? &m : nullptr, cam, img)) return -2;
+  return copy_view(img, out, out_cap);
+}
+int hkf_app_render_map_view(int mode, const float* world_pose16, unsigned cols, unsigned rows, float cx, float cy, float fx, float fy, uint8_t* out, size_t out_cap) {
+  if (!g_app) return -1;
+  if (!world_pose16) return -2;
+  Mat44 m; memcpy(m.entries, world_pose16, 64);
+  const kf_camera_params cam = {cols, rows, cx, cy, fx, fy};
+  std::vector<uint8_t> img;
+  if (!g_app->renderMapView(mode, m, cam, img)) return -2;
+  return copy_view(img, out, out_cap);
+}
 int hkf_app_view_model_maps(int mode, uint8_t* out, size_t out_cap) {
   if (!g_app) return -1;
   std::vector<uint8_t> img;

@@ -468,6 +468,32 @@ bool HybKinectfu::renderView(const Mat44* pose, const kf_camera_params& cam, int
   if (dm->check(kf_render_view(dm->ctx(), mode, tp, &cam, &rp, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, nullptr, nullptr))) return false;
   return read_view(dm, bgra);
 }
+bool HybKinectfu::renderViewAt(int mode, const int frame[3], const Mat44* pose, const kf_camera_params& cam, std::vector<uint8_t>& bgra) {
+  if (!_inited || !frame) return false;
+  const AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  const int32_t f32[3] = {frame[0], frame[1], frame[2]};
+  kf_mat44 kp; const kf_mat44* tp = nullptr;
+  if (pose) { kp = to_kf(*pose); tp = &kp; }
+  else if (!_camera_pose_finder->deviceResident()) {            // the host's copy, into the frame's coordinates: the same expression as k_shift_pose
+    int o[3]; volumeOrigin(o);
+    Mat44 moved = _camera_pose_finder->getCameraPose();
+    const float cell = volume_cell();
+    for (int k = 0; k < 3; ++k) moved.entries[4 * k + 3] = moved.entries[4 * k + 3] - (float)(frame[k] - o[k]) * cell;
+    kp = to_kf(moved); tp = &kp;
+  }
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
+  if (dm->check(kf_render_view_at(dm->ctx(), mode, f32, tp, &cam, &rp, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, nullptr, nullptr))) return false;
+  return read_view(dm, bgra);
+}
+bool HybKinectfu::renderMapView(int mode, const Mat44& world_pose, const kf_camera_params& cam, std::vector<uint8_t>& bgra) {
+  if (!_inited) return false;
+  const AppParams* p = AppParams::instance();
+  int32_t f[3]; Mat44 local;
+  hkf_view_frame(world_pose.entries, p->_volume_params.fVolumeMeterSize, p->_volume_params.nResolution, f, local.entries);
+  const int frame[3] = {(int)f[0], (int)f[1], (int)f[2]};
+  return renderViewAt(mode, frame, &local, cam, bgra);
+}
 bool HybKinectfu::viewModelMaps(int mode, std::vector<uint8_t>& bgra) {
   if (!_inited) return false;
   CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();

@@ -186,6 +186,11 @@ extern "C" {
 // (size_m / 2 each way).  If any component of (focus - centre) exceeds `dist` in magnitude, out[i] = trunc((focus - centre)[i] / (8 cell)) * 8 voxels
 // (truncation toward zero, cell = size_m / res), else zeros; dist <= 0 or a pose that is not finite gives zeros.  fp32, one rounding per operation.
 void hkf_recentre_shift(const float pose[16], float size_m, uint32_t res, float dist, int32_t out[3]);
+// The frame of the map a view from `world_pose` (camera -> world in the FIRST cube's coordinates, as hkf_world_pose gives them) looks into: frame[i] =
+// trunc((focus - centre)[i] / (8 cell)) * 8 voxels with hkf_recentre_shift's focus t + R (0, 0, size_m / 2), truncation and +-1e6-brick clamp -- the window
+// centred on the focus to within a brick -- and local_pose = world_pose with t - (float)frame * cell: the pose in that frame's coordinates.  A pose that
+// is not finite gives frame 0 and the pose unchanged.  fp32, one rounding per operation.
+void hkf_view_frame(const float world_pose[16], float size_m, uint32_t res, int32_t frame[3], float local_pose[16]);
 // volume coordinates -> world coordinates: + (float)origin_vox * cell on the pose's translation / on n xyz positions.  A zero origin leaves every bit.
 void hkf_world_pose(float pose[16], const int32_t origin_vox[3], float cell);
 void hkf_world_positions(float* xyz, size_t n, const int32_t origin_vox[3], float cell);
@@ -257,6 +262,12 @@ public:
   // tracking state alone.  viewModelMaps: the tracking camera's view from the current model maps, no march.  Blocking (the read-back).
   bool renderView(const Mat44* pose, const kf_camera_params& cam, int mode, std::vector<uint8_t>& bgra);
   bool viewModelMaps(int mode, std::vector<uint8_t>& bgra);
+  // The same picture of a window that stands elsewhere in the map (kf_render_view_at: the brick store's bricks where the window has moved on; nothing
+  // moves, tracking state is left alone).  renderViewAt: the window at `frame` (voxels of the first cube, multiples of 8), `pose` in that frame's
+  // coordinates (nullptr: the current camera pose, translated into the frame).  renderMapView: `world_pose` in the first cube's coordinates (what
+  // worldPose returns); the frame is the one that centres the window on the view's focus (hkf_view_frame).  Single GPU, like the brick store.
+  bool renderViewAt(int mode, const int frame[3], const Mat44* pose, const kf_camera_params& cam, std::vector<uint8_t>& bgra);
+  bool renderMapView(int mode, const Mat44& world_pose, const kf_camera_params& cam, std::vector<uint8_t>& bgra);
   // The moving volume (no reference counterpart).  shiftVolume: kf_shift_volume by (dx, dy, dz) voxels, multiples of 8, then the raycast with the
   // moved pose and the stock parameters, so the model maps show the new window before the next frame is tracked.  A finder that keeps its pose on
   // the host gets the translated pose through setCameraPose -- the same fp32 expression as on the device.  false: not initialised, or the shift

@@ -91,6 +91,31 @@ class App:
             raise K.KfError("renderView failed: %d" % r)
         return out
 
+    def render_view_at(self, mode, frame, pose, cam):
+        """HybKinectfu::renderViewAt: render_view of the window as it would stand at `frame` (voxels of the first cube, multiples of 8), the brick
+        store's bricks restored, without moving anything; `pose` in that frame's coordinates (None: the current camera pose, translated)"""
+        out = np.empty((cam[1], cam[0], 4), np.uint8)
+        p = np.ascontiguousarray(pose, np.float32).reshape(16) if pose is not None else None
+        f = (C.c_int * 3)(*[int(x) for x in frame])
+        r = self.h.hkf_app_render_view_at(int(mode), f, p.ctypes.data_as(C.c_void_p) if p is not None else None, int(cam[0]), int(cam[1]),
+                                          C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
+                                          out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("renderViewAt failed: %d" % r)
+        return out
+
+    def render_map_view(self, mode, world_pose, cam):
+        """HybKinectfu::renderMapView: a view of the MAP from `world_pose` (camera -> world in the first cube's coordinates): the window is placed
+        around the view's focus (view_frame) and rendered there (render_view_at)"""
+        out = np.empty((cam[1], cam[0], 4), np.uint8)
+        p = np.ascontiguousarray(world_pose, np.float32).reshape(16)
+        r = self.h.hkf_app_render_map_view(int(mode), p.ctypes.data_as(C.c_void_p), int(cam[0]), int(cam[1]),
+                                           C.c_float(cam[2]), C.c_float(cam[3]), C.c_float(cam[4]), C.c_float(cam[5]),
+                                           out.ctypes.data_as(C.c_void_p), C.c_size_t(out.nbytes))
+        if r != 0:
+            raise K.KfError("renderMapView failed: %d" % r)
+        return out
+
     def view_model_maps(self, mode):
         """HybKinectfu::viewModelMaps: the tracking camera's view from the current model maps, (rows, cols, 4) uint8"""
         out = np.empty((self.cam[1], self.cam[0], 4), np.uint8)
@@ -368,3 +393,14 @@ def recentre_shift(pose, size, res, dist):
     out = (C.c_int32 * 3)()
     h.hkf_recentre_shift(p.ctypes.data_as(C.c_void_p), C.c_float(size), C.c_uint32(res), C.c_float(dist), out)
     return tuple(int(x) for x in out)
+
+
+def view_frame(world_pose, size, res):
+    """hkf_view_frame: (frame, local_pose) -- the frame (voxels, multiples of 8) whose window is centred on the focus of a view from `world_pose`
+    (first-cube coordinates), and the pose in that frame's coordinates: what App.render_map_view hands render_view_at; GPU-free"""
+    h = load()
+    p = np.ascontiguousarray(world_pose, np.float32).reshape(16)
+    f = (C.c_int32 * 3)()
+    out = np.zeros(16, np.float32)
+    h.hkf_view_frame(p.ctypes.data_as(C.c_void_p), C.c_float(size), C.c_uint32(res), f, out.ctypes.data_as(C.c_void_p))
+    return tuple(int(x) for x in f), out.reshape(4, 4)

@@ -115,7 +115,7 @@ SYMBOLS = [
     "kf_get_fusion_form", "kf_get_raycast_form",
     "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
     "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
-    "kf_render_view", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
+    "kf_render_view", "kf_render_view_at", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
     "kf_view_slab_cross", "kf_view_slab_normals", "kf_view_from_rays",
     "kf_shift_volume", "kf_volume_origin",
     "kf_marching_cubes_region", "kf_region_work", "kf_world_soup_reserve", "kf_world_soup_count", "kf_read_world_soup", "kf_clear_world_soup",
@@ -166,6 +166,7 @@ def load():
         _lib.kf_read_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.kf_brick_store_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
+        _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
         _lib.kf_map_tile_frames.argtypes = [C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int32, C.c_void_p, C.c_int64]
         _lib.kf_map_tile_frames.restype = C.c_int64
@@ -440,6 +441,16 @@ class Context:
         tp = C.byref(Mat44.of(pose)) if pose is not None else None
         _chk(self.lib.kf_render_view(self.h, int(mode), tp, C.byref(cam), C.byref(rp), C.c_float(near), C.c_float(far),
                                      C.c_void_p(dev_v), C.c_void_p(dev_n)), "kf_render_view")
+
+    def render_view_at(self, mode, frame_origin, pose, cam, inc, near, far, dev_v=None, dev_n=None):
+        """render_view of a window that stands elsewhere: the bytes render_view would give after shift_volume(frame_origin - origin), store included,
+        without moving anything.  `pose` in that frame's coordinates (None: the device-resident pose as that shift would leave it) (kf_render_view_at)"""
+        rp = RaycastParams(inc) if inc is not None else None       # (frame_origin, cam, inc None: NULL -- refused, for the tests of the refusals)
+        m = Mat44.of(pose) if pose is not None else None
+        f = (C.c_int32 * 3)(*[int(x) for x in frame_origin]) if frame_origin is not None else None
+        _chk(self.lib.kf_render_view_at(self.h, int(mode), f, C.byref(m) if m is not None else None, C.byref(cam) if cam is not None else None,
+                                        C.byref(rp) if rp is not None else None, C.c_float(near), C.c_float(far), C.c_void_p(dev_v), C.c_void_p(dev_n)),
+             "kf_render_view_at")
 
     def view_model_maps(self, mode):
         """the tracking camera's view from the current model maps, KF_MAP_RAYCAST_RGB and the device pose: no march (kf_view_model_maps)"""

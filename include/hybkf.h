@@ -363,10 +363,24 @@ int kf_weld_release(kf_ctx* ctx);
  * kf_view_model_maps: the tracking camera's view without a march -- the same bytes from level 0 of the context's CURRENT model maps,
  *   KF_MAP_RAYCAST_RGB and the device-resident pose.  Allowed on z-slab contexts: after kf_set_model_maps_rays every member holds the merged maps.
  * kf_view_size: the size of the last view (KF_ERR_STATE before one).  kf_view_device: the image in HBM, valid in stream order until the next view
- *   (NULL before one).  kf_read_view: blocking copy of cols * rows * 4 bytes. */
+ *   (NULL before one).  kf_read_view: blocking copy of cols * rows * 4 bytes.
+ * kf_render_view_at: kf_render_view of a window that stands ELSEWHERE (no reference counterpart: the reference's cube never moves) -- the display bytes and
+ *   the optional dev_v / dev_n maps, bit for bit, that kf_render_view would produce after kf_shift_volume had moved the window to frame_origin_vox (voxels of
+ *   the first cube, multiples of 8) with the brick store's bricks restored; it moves nothing.  A brick is read from the window's copy where its world brick
+ *   lies in the window (the newer copy), else from the store's slot, else from one shared all-zero brick: kf_marching_cubes_at's rule.  `pose` is given in the
+ *   virtual frame's coordinates, the numbers one would hand kf_render_view after that shift; NULL: the device-resident pose as that shift would have left it,
+ *   t - (float)(frame - origin) * cell per axis, computed on the device (no read-back).  Asynchronous on the context's stream; the image is the context's view
+ *   image (kf_view_size / kf_view_device / kf_read_view).  A bystander, strictly: volume, flags, skip tables, deferred-weight words (neither consulted nor
+ *   flushed), store, device pose, model maps, KF_MAP_RAYCAST_RGB, kf_get_raycast_form's record, a pending kf_prefetch_frame, stage timers, work counters,
+ *   the triangle buffer and the extraction scratch are what they were.  A context without a reserved store is no error: window or zero.
+ *   KF_ERR_ARG: NULL context, frame, camera or increment, bad mode, bad camera (kf_render_view's limits), a frame component that is not a multiple of 8, a
+ *   frame whose bricks fall outside the brick key range or that kf_shift_volume could not reach in one call.  KF_ERR_STATE: KF_VIEW_COLOR without a colour
+ *   plane, a z-slab context.  On any error nothing is touched and the last view stays the last view. */
 enum { KF_VIEW_NORMALS = 0, KF_VIEW_SHADED = 1, KF_VIEW_COLOR = 2 };
 int kf_render_view(kf_ctx* ctx, int mode, const kf_mat44* pose, const kf_camera_params* view_cam, const kf_raycast_params* raycast_params,
                    float near_plane, float far_plane, float* dev_v, float* dev_n);
+int kf_render_view_at(kf_ctx* ctx, int mode, const int32_t frame_origin_vox[3], const kf_mat44* pose, const kf_camera_params* view_cam,
+                      const kf_raycast_params* raycast_params, float near_plane, float far_plane, float* dev_v, float* dev_n);
 int kf_view_model_maps(kf_ctx* ctx, int mode);
 int kf_view_size(kf_ctx* ctx, uint32_t* cols, uint32_t* rows);
 const uint8_t* kf_view_device(kf_ctx* ctx);

@@ -2,8 +2,14 @@
 """Pictures of a scanned model from an orbit of viewpoints: fuse Scene S, then render N poses on a circle around the volume's centre with
 kf_render_view at a chosen size and mode, and write one picture per pose into a directory.
   usage: tools/render_orbit.py OUT_DIR [--n 12] [--size 640x480] [--mode normals|shaded|color] [--res 256] [--volume 3.0] [--frames 12] [--slabs N]
+                               [--frame X Y Z | --world]
 --slabs N: the same orbit through a LOCAL slab group of N members (kf_group_render_view: every member marches its own layers, the merge gives
 the whole volume's picture -- the same bytes).
+--frame X Y Z: the orbit of a window that stands at that origin (voxels of the first cube, multiples of 8) instead of the current one, with
+kf_render_view_at: nothing moves; the poses are that frame's.
+--world: an orbit of the MAP.  A brick store is reserved, the window is shifted half its width along x after the scan -- so half of what was scanned lives
+in the store alone -- and every pose of the orbit around the FIRST cube's centre, given in world coordinates, is rendered in the frame hkf_view_frame
+centres on its focus (what HybKinectfu::renderMapView does).
 PNG through PIL where it is installed, binary PPM otherwise (no hit: black)."""
 import argparse, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -20,7 +26,13 @@ ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--volume", type=float, default=3.0)
 ap.add_argument("--frames", type=int, default=12)
 ap.add_argument("--slabs", type=int, default=0, help="render through a LOCAL slab group of N members")
+ap.add_argument("--frame", type=int, nargs=3, metavar=("X", "Y", "Z"), help="render the window as it would stand at this origin (kf_render_view_at)")
+ap.add_argument("--world", action="store_true", help="an orbit of the map: brick store, window shifted away, poses in world coordinates")
 args = ap.parse_args()
+if args.slabs and (args.frame or args.world):
+    ap.error("--frame / --world: the brick store and kf_render_view_at are single-GPU features")
+if args.frame and args.world:
+    ap.error("--frame or --world, not both")
 cols, rows = (int(v) for v in args.size.lower().split("x"))
 mode = dict(normals=K.VIEW_NORMALS, shaded=K.VIEW_SHADED, color=K.VIEW_COLOR)[args.mode]
 P, cam, size, res = S.STOCK, S.vga_camera(), args.volume, args.res
@@ -47,6 +59,8 @@ if args.slabs:
     group.sync()
 else:
     ctx = K.Context(K.camera(*cam), res, size, P["volume_max_weight"], levels=3, has_color=color)
+    if args.world:
+        ctx.brick_store_reserve((res // 8) ** 3)
     for k in range(args.frames):
         pose = S.trajectory_pose(k, size).astype(np.float32)
         mm = S.render_depth_mm(pose, cam, size)
@@ -55,6 +69,9 @@ else:
             ctx.upload_rgb(ramp(mm))
         ctx.preprocess(P["depth_trunc_min"], P["depth_trunc_max"], P["filter_sigma_pixel"], P["filter_sigma_depth"])
         ctx.integrate(pose, trunc, P["integrate_depth_trunc"], has_color=color, angle_weight=color)
+    if args.world:
+        ctx.shift_volume(8 * (res // 16), 0, 0)
+        print("window at", ctx.volume_origin(), " bricks in the store:", ctx.brick_store_count()[0])
 
 
 def look(eye, target):
@@ -91,6 +108,14 @@ for i in range(args.n):
     if group:
         group.render_view(mode, look(eye, centre), view_cam, 0.05, 4.0 * size)
         img = group.read_view()
+    elif args.world:
+        from hybkinectfu_amd import host_app as H
+        frame, local = H.view_frame(look(eye, centre), size, res)
+        ctx.render_view_at(mode, frame, local, view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
+        img = ctx.read_view()
+    elif args.frame:
+        ctx.render_view_at(mode, args.frame, look(eye, centre), view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
+        img = ctx.read_view()
     else:
         ctx.render_view(mode, look(eye, centre), view_cam, P["raycast_increment_factor"] * trunc, 0.05, 4.0 * size)
         img = ctx.read_view()
