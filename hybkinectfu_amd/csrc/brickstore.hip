@@ -14,7 +14,10 @@
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"
+#include "brick_keys_unique.h"
 #include <stdint.h>
+#include <new>
+#include <vector>
 
 // Up to three disjoint boxes of bricks (half-open), numbered one behind the other: iteration i < end[0] lies in box 0, i < end[1] in box 1, ...
 // (end[] of a missing box = the total).  Constant indices only: a by-value kernel argument indexed at run time would be copied to scratch.
@@ -119,6 +122,38 @@ __global__ void __launch_bounds__(256) k_store_export(KfBrickStore st, unsigned 
   }
 }
 
+// Import for kf_write_brick_store, k_store_export's inverse: staged entries [0, count) in kf_read_brick_store's layout -> slots.  One workgroup iteration
+// per entry, each lane two voxels: a float2 of tsdf and a float2 of weight in, one float4 (t, w, t, w) out; for colour six bytes in (three 16-bit loads, the
+// staged bytes are 2-byte aligned) and one uint2 out, the fourth byte 0 as kf_upload_volume writes it.  An entry with no weight > 0 takes no slot, as in
+// k_store_evict.  The weights are TRUE weights, so the deferred-weight word is 0: nothing is pending on them.  Every key occurs once per launch (the caller
+// has checked), so store_claim's reasoning holds: no two workgroups settle the same key.
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_store_import(KfBrickStore st, unsigned count, const int32_t* __restrict__ keys, const float* __restrict__ tsdf,
+                                                      const float* __restrict__ weight, const unsigned char* __restrict__ color) {
+  __shared__ unsigned s_slot;
+  for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
+    const size_t o = (size_t)e * KF_BRICK_VOX;
+    const float2 t = reinterpret_cast<const float2*>(tsdf + o)[threadIdx.x];
+    const float2 w = reinterpret_cast<const float2*>(weight + o)[threadIdx.x];
+    if (!__syncthreads_or(w.x > 0.f || w.y > 0.f)) continue;                  // (workgroup-uniform) never observed: nothing to keep
+    const unsigned long long key = kf_brick_key_pack(keys[3 * e], keys[3 * e + 1], keys[3 * e + 2]);
+    if (threadIdx.x == 0) s_slot = store_claim(st, key);                      // everybody has read the last iteration's slot: the barrier above
+    __syncthreads();
+    const unsigned slot = s_slot;
+    if (slot == KF_BRICK_NO_SLOT) continue;
+    reinterpret_cast<float4*>(st.tw + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_float4(t.x, w.x, t.y, w.y);
+    if (COLOR) {                                                              // the store has a colour plane; no colour given (kernel-uniform): zeros, never stale bytes
+      unsigned a = 0u, b = 0u, c = 0u;
+      if (color) {
+        const unsigned short* cs = reinterpret_cast<const unsigned short*>(color + 3 * o) + 3u * threadIdx.x;
+        a = cs[0]; b = cs[1]; c = cs[2];                                      // the bytes of two voxels: c0 c1 | c2 c0' | c1' c2'
+      }
+      reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_uint2(a | ((b & 255u) << 16), (b >> 8) | (c << 8));
+    }
+    if (threadIdx.x == 0) { st.pend[slot] = 0ull; st.key[slot] = key; }
+  }
+}
+
 // The bricks that leave under a shift of s bricks (source brick q leaves when q - s lies outside [0, nb) on some axis), as up to three disjoint boxes:
 // the x strip in full, the y strip without the x strip, the z strip without both -- departing_boxes' decomposition (shift.hip), on bricks.  Along one
 // axis with s > 0 the bricks [0, s) leave, with s < 0 the bricks [nb + s, nb).  The bricks that ENTER (destination brick b enters when b + s lies
@@ -181,6 +216,7 @@ void kf_brick_store_free(kf_ctx* c) {
   void* ptrs[] = {st.tw, st.color, st.pend, st.key, st.tkey, st.tslot, st.cnt};
   for (void* p : ptrs) if (p) hipFree(p);
   st = KfBrickStore{};
+  if (c->bstore_stage) { hipFree(c->bstore_stage); c->bstore_stage = nullptr; }
 }
 
 extern "C" int kf_brick_store_reserve(kf_ctx* c, uint32_t max_bricks) {
@@ -258,4 +294,64 @@ extern "C" int kf_read_brick_store(kf_ctx* c, uint32_t first, uint32_t count, in
   if (dw) hipFree(dw);
   if (dc) hipFree(dc);
   return e == hipSuccess ? 0 : (int)e;
+}
+
+// Capture: every observed brick of the window into the store, under the window's origin -- the eviction of a shift that makes everything leave (one box of
+// all nb^3 bricks), without the shift.  Pending weights are flushed first, as the shift does, so the slots hold what a departing brick would have held.
+int kf_brick_store_capture_enqueue(kf_ctx* c) {
+  { const int fs = kf_flush_pending(c); if (fs) return fs; }
+  const int all[3] = {c->vol.nb, 0, 0};
+  return kf_brick_store_evict(c, all, c->origin_vox);
+}
+extern "C" int kf_brick_store_capture(kf_ctx* c) {
+  if (!c) return KF_ERR_ARG;
+  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;
+  if (!c->bstore.max_bricks) return KF_ERR_STATE;
+  for (int k = 0; k < 3; ++k) {                              // (a window that shifts with a store reserved never leaves the key range; one that moved before the reserve may have)
+    const int64_t b = c->origin_vox[k] / KF_BRICK;
+    if (!kf_brick_key_in_range(b) || !kf_brick_key_in_range(b + c->vol.nb - 1)) return KF_ERR_ARG;
+  }
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  return kf_brick_store_capture_enqueue(c);
+}
+
+// kf_write_brick_store: the staging buffer holds KF_BSTORE_STAGE_BRICKS entries, plane after plane -- keys, tsdf, weight, colour bytes -- each plane 16-byte aligned
+#define KF_BSTORE_STAGE_BRICKS 256u
+extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color) {
+  if (!c) return KF_ERR_ARG;
+  if (!c->bstore.max_bricks) return KF_ERR_STATE;
+  if (color && !c->bstore.color) return KF_ERR_STATE;
+  if (count == 0) return 0;                                  // nothing to write: the arrays are not looked at
+  if (!keys || !tsdf || !weight) return KF_ERR_ARG;
+  try {                                                      // (no exception crosses the C boundary)
+    std::vector<unsigned long long> packed(count);
+    for (uint32_t i = 0; i < count; ++i) {
+      for (int k = 0; k < 3; ++k) if (!kf_brick_key_in_range(keys[3 * (size_t)i + k])) return KF_ERR_ARG;
+      packed[i] = kf_brick_key_pack(keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
+    }
+    if (!kf_brick_keys_unique(packed.data(), packed.size())) return KF_ERR_ARG;
+  } catch (const std::bad_alloc&) { return KF_ERR_ALLOC; }
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  const size_t cap = KF_BSTORE_STAGE_BRICKS, plane = cap * KF_BRICK_VOX * sizeof(float);
+  const size_t off_t = cap * 3 * sizeof(int32_t), off_w = off_t + plane, off_c = off_w + plane, bytes = off_c + cap * KF_BRICK_VOX * 3;
+  if (!c->bstore_stage && hipMalloc(&c->bstore_stage, bytes) != hipSuccess) { c->bstore_stage = nullptr; (void)hipGetLastError(); return KF_ERR_ALLOC; }
+  unsigned char* base = (unsigned char*)c->bstore_stage;
+  int32_t* dk = (int32_t*)base; float *dt = (float*)(base + off_t), *dw = (float*)(base + off_w); unsigned char* dc = base + off_c;
+  const bool with_color = color && c->bstore.color;
+  hipError_t e = hipSuccess;
+  for (uint32_t first = 0; first < count && e == hipSuccess; first += KF_BSTORE_STAGE_BRICKS) {   // stream order: a chunk's launch has read the buffer before the next chunk's copies write it
+    const uint32_t n = count - first < KF_BSTORE_STAGE_BRICKS ? count - first : KF_BSTORE_STAGE_BRICKS;
+    const size_t vox = (size_t)n * KF_BRICK_VOX, at = (size_t)first * KF_BRICK_VOX;
+    e = hipMemcpyAsync(dk, keys + 3 * (size_t)first, (size_t)n * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dt, tsdf + at, vox * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dw, weight + at, vox * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && with_color) e = hipMemcpyAsync(dc, color + 3 * at, vox * 3, hipMemcpyHostToDevice, c->stream);
+    if (e != hipSuccess) break;
+    const dim3 grid(n), block(256);                          // n <= KF_BSTORE_STAGE_BRICKS: below store_pass's cap of 4096 workgroups
+    if (c->bstore.color) hipLaunchKernelGGL(k_store_import<true>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, with_color ? dc : (unsigned char*)nullptr);
+    else hipLaunchKernelGGL(k_store_import<false>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, (unsigned char*)nullptr);
+    e = hipGetLastError();
+  }
+  const hipError_t se = hipStreamSynchronize(c->stream);     // on success and on failure alike: no copy out of the caller's arrays is still queued when the call returns
+  return (int)(e != hipSuccess ? e : se);
 }

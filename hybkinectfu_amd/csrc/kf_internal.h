@@ -264,6 +264,7 @@ struct kf_ctx {
   // since kf_create / kf_reset_volume.  Host bookkeeping only: no kernel reads it.
   int32_t origin_vox[3];
   KfBrickStore bstore;           // the brick store (brickstore.hip): absent (max_bricks == 0) until kf_brick_store_reserve
+  void* bstore_stage;            // kf_write_brick_store's device staging for KF_BSTORE_STAGE_BRICKS entries; allocated by the first write, freed with the store
   // the virtual window of kf_marching_cubes_at (mapmesh.hip): one all-zero brick (4 KiB), then 16 bytes per brick slot -- where that brick's voxels and colours
   // are read from.  Part of the extraction scratch: allocated by the first kf_marching_cubes_at, freed with the rest.
   void* mc_vtab;
@@ -683,5 +684,6 @@ int kf_mc_scratch(kf_ctx* ctx);          // (mcubes.hip) the extraction scratch,
 // origin the keys are formed with -- the old one for the eviction (before anything moves), the new one for the restore (after the move)
 int kf_brick_store_evict(kf_ctx* ctx, const int s[3], const int32_t origin_vox[3]);
 int kf_brick_store_restore(kf_ctx* ctx, const int s[3], const int32_t origin_vox[3]);
+int kf_brick_store_capture_enqueue(kf_ctx* ctx);   // kf_brick_store_capture past its checks (kf_place_window); asynchronous
 int kf_brick_store_reset(kf_ctx* ctx);   // no entries, counts zero (kf_brick_store_clear, kf_reset_volume); asynchronous
 void kf_brick_store_free(kf_ctx* ctx);   // for kf_destroy and kf_brick_store_reserve: the caller has synchronised the stream

@@ -142,6 +142,48 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
   return (int)hipGetLastError();
 }
 
+// kf_place_window: the window at any origin, filled from the store.  kf_shift_volume restores only what ENTERS, so a window moved by less than its width onto
+// a filled store stays empty where it overlaps its old place.  This call leaves what capture, a shift to a frame that overlaps neither window, and a
+// shift from there to (ox, oy, oz) leave: after the capture the store alone is the whole map, the first hop empties the window (everything leaves, already
+// captured), the second restores all nb^3 bricks.  Done directly: capture, the shift's clears plus the planes themselves, the pose moved once, the restore
+// over one box of all bricks.  No stream-out: the bricks are kept, not lost.
+extern "C" int kf_place_window(kf_ctx* c, int32_t ox, int32_t oy, int32_t oz) {
+  if (!c) return KF_ERR_ARG;
+  if ((ox % KF_BRICK) || (oy % KF_BRICK) || (oz % KF_BRICK)) return KF_ERR_ARG;
+  KfVolume& v = c->vol;
+  if (v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_ARG;
+  if (!c->bstore.max_bricks) return KF_ERR_STATE;
+  const int32_t org[3] = {ox, oy, oz};
+  for (int k = 0; k < 3; ++k) {
+    const int64_t b_old = c->origin_vox[k] / KF_BRICK, b_new = org[k] / KF_BRICK;
+    if (!kf_brick_key_in_range(b_old) || !kf_brick_key_in_range(b_old + v.nb - 1) || !kf_brick_key_in_range(b_new) || !kf_brick_key_in_range(b_new + v.nb - 1)) return KF_ERR_ARG;
+  }
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  // the counts before and after the capture, one blocking read: a brick the capture dropped exists in the window only, so the window stays
+  KfBrickStoreCounts* h = (KfBrickStoreCounts*)c->host_pinned;
+  KF_CHECK(hipMemcpyAsync(&h[0], c->bstore.cnt, sizeof(KfBrickStoreCounts), hipMemcpyDeviceToHost, c->stream));
+  { const int cs = kf_brick_store_capture_enqueue(c); if (cs) return cs; }
+  KF_CHECK(hipMemcpyAsync(&h[1], c->bstore.cnt, sizeof(KfBrickStoreCounts), hipMemcpyDeviceToHost, c->stream));
+  KF_CHECK(hipStreamSynchronize(c->stream));
+  if (h[1].dropped != h[0].dropped) return KF_ERR_ALLOC;         // (the bricks that were captured are harmless copies)
+  // kf_shift_volume's bookkeeping and clears; the planes, flags and deferred-weight words as k_shift_bricks leaves a window everything has left
+  { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
+  ++c->vol_flags_serial;
+  c->wgt0_valid = 0;
+  c->model_pyr_ok = 0;
+  KF_CHECK(hipMemsetAsync(v.macrobits, 0, kf_skip_table_words(v) * sizeof(unsigned), c->stream));
+  KF_CHECK(hipMemsetAsync(v.negbits, 0, kf_negbit_words(c->n_stored_bricks) * sizeof(unsigned), c->stream));
+  KF_CHECK(hipMemsetAsync(v.tw, 0, c->n_stored_vox * sizeof(float2), c->stream));
+  if (v.color) KF_CHECK(hipMemsetAsync(v.color, 0, c->n_stored_vox * sizeof(uchar4), c->stream));
+  KF_CHECK(hipMemsetAsync(v.flags, 0, c->n_stored_bricks, c->stream));
+  KF_CHECK(hipMemsetAsync(v.pend, 0, c->n_stored_bricks * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_shift_pose, dim3(1), dim3(64), 0, c->stream, c->track, (int)(ox - c->origin_vox[0]), (int)(oy - c->origin_vox[1]), (int)(oz - c->origin_vox[2]), v.cell);
+  for (int k = 0; k < 3; ++k) c->origin_vox[k] = org[k];
+  const int all[3] = {v.nb, 0, 0};                                // what enters when everything has left: one box of all bricks
+  { const int rs = kf_brick_store_restore(c, all, c->origin_vox); if (rs) return rs; }
+  return (int)hipGetLastError();
+}
+
 extern "C" int kf_volume_origin(kf_ctx* c, int32_t origin_vox[3]) {
   if (!c || !origin_vox) return KF_ERR_ARG;
   for (int k = 0; k < 3; ++k) origin_vox[k] = c->origin_vox[k];

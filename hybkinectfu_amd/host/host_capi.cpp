@@ -2,6 +2,7 @@
 // way src/MainController.cpp drives the reference: init -> per frame processNewFrame -> generateMesh/saveMesh.
 #include "hybkf_host.hpp"
 #include "png_reader.hpp"
+#include "map_file.hpp"
 #include <string.h>
 
 static HybKinectfu* g_app = nullptr;
@@ -154,6 +155,25 @@ int hkf_app_brick_store_count(uint64_t out3[3]) {
   unsigned held = 0; uint64_t dropped = 0, restored = 0;
   if (!g_app->brickStoreCounts(held, dropped, restored)) return -2;
   out3[0] = held; out3[1] = dropped; out3[2] = restored;
+  return 0;
+}
+// The map on disk: HybKinectfu::saveMap / loadMap / frameId.  1 done, 0 refused or failed (stderr says why), -1 without an application.
+// hkf_map_file_info needs neither application nor device: every check of the reader (map_file.hpp), then the header's fields -- u32x4[0..3] = version,
+// resolution, brick edge, colour flag; f32x2 = size, max weight; origin3; frame_id; pose16; u64x2 = n_bricks, dropped.  Any pointer may be NULL.
+// Returns 0 or the reader's HKF_MAP_ERR_* (negative).
+int hkf_app_save_map(const char* path) { if (!g_app) return -1; return path && g_app->saveMap(path) ? 1 : 0; }
+int hkf_app_load_map(const char* path) { if (!g_app) return -1; return path && g_app->loadMap(path) ? 1 : 0; }
+int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
+int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {
+  HkfMapHeader h;
+  const int st = hkf_map_info(path, &h);
+  if (st != HKF_MAP_OK) return st;
+  if (u32x4) { u32x4[0] = h.version; u32x4[1] = h.resolution; u32x4[2] = h.brick_edge; u32x4[3] = h.has_color; }
+  if (f32x2) { f32x2[0] = h.size_m; f32x2[1] = h.max_weight; }
+  if (origin3) memcpy(origin3, h.origin_vox, 12);
+  if (frame_id) *frame_id = h.frame_id;
+  if (pose16) memcpy(pose16, h.pose, 64);
+  if (u64x2) { u64x2[0] = h.n_bricks; u64x2[1] = h.dropped; }
   return 0;
 }
 // MeshGeneratorMarchingcube::setMapMesh (call AFTER hkf_app_init, which restores the defaults): with a brick store reserved, generateMesh builds the map mesh

@@ -2,6 +2,7 @@
 // Reference files followed: src/HybKinectfu.cpp, src/CameraPoseFinderICP.cpp, src/CameraPoseFinderSDF.cpp,
 // src/utils/eigen_utils.cpp, src/MeshGeneratorMarchingcube.cpp, src/utils/mesh/meshData.{h,cpp}, src/utils/mesh/MeshIO.cpp.
 #include "hybkf_host.hpp"
+#include "map_file.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -314,6 +315,7 @@ bool HybKinectfu::enqueueFrame(const DepthFrameData& depth_frame, const ColorFra
   // a finder that computes its pose on the host (file-driven, or a plugin with the reference's two virtuals) has no streaming
   // form: the frame takes the reference's own sequence, which also handles a lost frame (no integrate, raycast with the old pose)
   if (!_camera_pose_finder->deviceResident()) return processNewFrame(depth_frame, rgb_frame);
+  _frame_id = depth_frame.frameId();
   copyFrameToGPU(depth_frame, rgb_frame);
   if (dm->check(kf_preprocess(ctx, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, p->_depth_prepocess_params.fSigmaPixel,
                               p->_depth_prepocess_params.fSigmaDepth, &p->_depth_camera_params))) return false;      // :106-110
@@ -333,6 +335,7 @@ bool HybKinectfu::processNewFrame(const DepthFrameData& depth_frame, const Color
   const AppParams* p = AppParams::instance();
   CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
   kf_ctx* ctx = dm->ctx();
+  _frame_id = depth_frame.frameId();
   copyFrameToGPU(depth_frame, rgb_frame);
   if (dm->check(kf_preprocess(ctx, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, p->_depth_prepocess_params.fSigmaPixel,
                               p->_depth_prepocess_params.fSigmaDepth, &p->_depth_camera_params))) return false;
@@ -440,6 +443,82 @@ bool HybKinectfu::brickStoreCounts(unsigned& held, uint64_t& dropped, uint64_t& 
   if (dm->check(kf_brick_store_count(dm->ctx(), &h, &dropped, &restored))) return false;
   held = h;
   return true;
+}
+// ---- the map on disk (map_file.hpp) ---------------------------------------------------------------------------------------------------------
+static const uint32_t kMapChunkBricks = 256;                   // bricks per kf_read_brick_store / kf_write_brick_store call: 1.4 MiB of host memory
+bool HybKinectfu::saveMap(const std::string& path) {
+  if (!_inited) return false;
+  const AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  uint32_t held = 0; uint64_t dropped_before = 0, dropped = 0;
+  if (dm->check(kf_brick_store_count(ctx, nullptr, &dropped_before, nullptr))) return false;
+  if (dm->check(kf_brick_store_capture(ctx))) return false;    // KF_ERR_STATE without a store
+  if (dm->check(kf_brick_store_count(ctx, &held, &dropped, nullptr))) return false;
+  if (dropped != dropped_before) {
+    fprintf(stderr, "saveMap: the brick store is full: %llu bricks of the window did not fit; nothing written\n", (unsigned long long)(dropped - dropped_before));
+    return false;
+  }
+  if (dropped) fprintf(stderr, "saveMap: the brick store has dropped %llu bricks for want of room: the map has holes there\n", (unsigned long long)dropped);
+  HkfMapHeader h;
+  memset(&h, 0, sizeof(h));
+  h.resolution = p->_volume_params.nResolution; h.has_color = p->_switch_params.useRGBData ? 1u : 0u;
+  h.size_m = p->_volume_params.fVolumeMeterSize; h.max_weight = p->_volume_params.fWeightMax;
+  int o[3]; volumeOrigin(o);
+  for (int k = 0; k < 3; ++k) h.origin_vox[k] = o[k];
+  h.frame_id = _frame_id;
+  Mat44 pose = getCameraPose();                                 // (waits for a pending verdict)
+  if (_camera_pose_finder->deviceResident()) {                  // the device holds the pose: a window placed behind the host's back has moved it there only
+    kf_track_result r;
+    if (dm->check(kf_read_track_result(ctx, &r))) return false;
+    memcpy(pose.entries, r.pose.m, 64);
+  }
+  memcpy(h.pose, pose.entries, 64);
+  h.n_bricks = held; h.dropped = dropped;
+  const bool color = h.has_color != 0;
+  const int st = hkf_map_write(path.c_str(), h, kMapChunkBricks, [&](uint32_t first, uint32_t count, int32_t* keys, float* tsdf, float* weight, uint8_t* col) {
+    return 0 == dm->check(kf_read_brick_store(ctx, first, count, keys, tsdf, weight, color ? col : nullptr));
+  });
+  if (st != HKF_MAP_OK) fprintf(stderr, "saveMap: writing %s failed (%d)\n", path.c_str(), st);
+  return st == HKF_MAP_OK;
+}
+bool HybKinectfu::loadMap(const std::string& path) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  HkfMapHeader h;
+  bool store_ok = true, touched = false;
+  lastTracked();                                                // a frame still in flight settles first: afterwards the loaded pose is the one that counts
+  const HkfMapAccept accept = [&](const HkfMapHeader& f) {      // the whole file has passed the reader's checks; nothing is touched before this returns true
+    if (f.resolution != p->_volume_params.nResolution || memcmp(&f.size_m, &p->_volume_params.fVolumeMeterSize, 4) != 0 ||
+        memcmp(&f.max_weight, &p->_volume_params.fWeightMax, 4) != 0 || (f.has_color != 0) != p->_switch_params.useRGBData) return false;
+    h = f;
+    touched = true;                                            // from here on a failure leaves an EMPTY map: see below
+    if (dm->check(kf_reset_volume(ctx))) { store_ok = false; return false; }
+    const uint64_t want = f.n_bricks > p->_volume_params.nBrickStoreBricks ? f.n_bricks : p->_volume_params.nBrickStoreBricks;
+    store_ok = setBrickStore((unsigned)(want ? want : 1u));   // (a store of one brick for an empty map: kf_place_window needs a store)
+    return store_ok;
+  };
+  const int st = hkf_map_read(path.c_str(), kMapChunkBricks, accept, [&](uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* col) {
+    return 0 == dm->check(kf_write_brick_store(ctx, count, keys, tsdf, weight, col));
+  });
+  if (st != HKF_MAP_OK) {
+    fprintf(stderr, "loadMap: %s refused (%d)%s\n", path.c_str(), st, st == HKF_MAP_ERR_REFUSED && store_ok ? ": its volume is not this instance's" : "");
+    // The file was checked as a whole before anything was touched, so a failure past that point is a read error or a device error.  It must not leave a
+    // partly filled store under an empty window: volume and store are reset once more.  The host's pose and frame id are still the old session's.
+    if (touched) dm->check(kf_reset_volume(ctx));
+    return false;
+  }
+  if (dm->check(kf_place_window(ctx, h.origin_vox[0], h.origin_vox[1], h.origin_vox[2]))) { dm->check(kf_reset_volume(ctx)); return false; }
+  Mat44 pose; memcpy(pose.entries, h.pose, 64);
+  _camera_pose_finder->setCameraPose(pose);                    // host copy and device-resident pose (kf_set_pose: "tracked")
+  _frame_id = h.frame_id; _last_tracked = true; _pending = false;
+  const bool resident = _camera_pose_finder->deviceResident();
+  const kf_mat44 kp = to_kf(pose);
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};  // shiftVolume's raycast: the model maps show the loaded window before the next frame is tracked
+  return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
+                                          p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
 }
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();

@@ -285,6 +285,19 @@ public:
   // window that returns finds what it left; 0 frees it.  brickStoreCounts: bricks held, dropped for want of room, restored (blocking).
   bool setBrickStore(unsigned max_bricks);
   bool brickStoreCounts(unsigned& held, uint64_t& dropped, uint64_t& restored);
+  // The map on disk (map_file.hpp; needs the brick store).  saveMap: the window is captured into the store (kf_brick_store_capture: nothing moves, later
+  // frames are what they are without the call), the store is read out in chunks and written with the current pose, origin and frameId().  false: no store,
+  // a brick dropped during the capture (the file would have a hole nobody asked for), an I/O error.  Bricks dropped BEFORE the call are logged and
+  // recorded in the header.  loadMap: reads and checks the whole file and refuses (false, nothing touched) one whose resolution, size, max weight or
+  // colour differ from this instance's; then resets the volume, reserves the store at max(its capacity, the file's bricks), writes the bricks back
+  // (kf_write_brick_store), places the window at the saved origin (kf_place_window), sets pose and frame id and raycasts as shiftVolume does, so
+  // that the next processNewFrame is TRACKED against the loaded model.  A failure after the file was accepted (a read error, a device error) leaves an
+  // empty volume and an empty store, never a half-loaded map.  frameId: the id of the last frame processed, or the one loadMap set.
+  // The pose saved is the host's copy; with a device-resident finder it is read from the device, which also holds a pose that kf_place_window moved on the
+  // raw context.  A finder that keeps its pose on the host does not see such a move: placing the window behind this class's back is not supported there.
+  bool saveMap(const std::string& path);
+  bool loadMap(const std::string& path);
+  unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();
   Mat44 worldPose(const Mat44& pose);
@@ -294,6 +307,7 @@ private:
   bool _inited;
   bool _last_tracked = true;      // verdict of the last processNewFrame
   bool _pending = false;          // frames enqueued whose verdict still lives on the device
+  unsigned _frame_id = 0;         // frameId() of the last frame handed to processNewFrame / enqueueFrame (saveMap records it, loadMap sets it)
 };
 
 // ---- src/MeshGenerator.h, src/MeshGeneratorMarchingcube.{h,cpp}, src/utils/mesh/meshData.* (the parts saveMesh uses) ----------

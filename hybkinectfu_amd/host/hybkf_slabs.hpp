@@ -56,6 +56,9 @@ public:
   // and map mesh (nBrickStoreBricks, nStreamMeshTriangles, bMapMesh) are HybKinectfu's alone.
   bool shiftVolume(int dx, int dy, int dz);
   void volumeOrigin(int out[3]);
+  // HybKinectfu's map on disk is built on the brick store, a single-GPU feature: a slab group has no store to save from or load into.  Always false.
+  bool saveMap(const std::string&) { return false; }
+  bool loadMap(const std::string&) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

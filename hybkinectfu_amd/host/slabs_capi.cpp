@@ -127,5 +127,8 @@ int hkf_slabs_render_view(int mode, const float* pose16, unsigned cols, unsigned
 int hkf_slabs_shift_volume(int dx, int dy, int dz) { if (!g_slabs) return -1; return g_slabs->shiftVolume(dx, dy, dz) ? 1 : 0; }
 int hkf_slabs_volume_origin(int out3[3]) { if (!g_slabs) return -1; g_slabs->volumeOrigin(out3); return 0; }
 int hkf_slabs_set_recentre(float dist) { if (!g_slabs) return -1; AppParams::instance()->_volume_params.fRecentreDist = dist; return 0; }
+// HybKinectfuSlabs::saveMap / loadMap: 0 refused -- always: the map file is built on the brick store, which a slab group does not have --, -1 without a group
+int hkf_slabs_save_map(const char* path) { if (!g_slabs) return -1; return path && g_slabs->saveMap(path) ? 1 : 0; }
+int hkf_slabs_load_map(const char* path) { if (!g_slabs) return -1; return path && g_slabs->loadMap(path) ? 1 : 0; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

@@ -179,8 +179,46 @@ class App:
             raise K.KfError("hkf_app_brick_store_count failed: %d" % r)
         return int(out[0]), int(out[1]), int(out[2])
 
+    def save_map(self, path):
+        """HybKinectfu::saveMap: capture the window into the brick store (nothing moves) and write store, pose, origin and frame id to `path`;
+        False: no store, a brick did not fit during the capture, or an I/O error"""
+        r = self.h.hkf_app_save_map(os.fsencode(path))
+        if r < 0:
+            raise K.KfError("hkf_app_save_map: no application")
+        return bool(r)
+
+    def load_map(self, path):
+        """HybKinectfu::loadMap: the file's map into the store, the window placed at the saved origin, pose and frame id set, the model maps raycast:
+        the next process_frame is tracked against the loaded model.  False, with nothing touched: an unreadable, truncated or foreign file, or one
+        of another resolution, size, max weight or colour"""
+        r = self.h.hkf_app_load_map(os.fsencode(path))
+        if r < 0:
+            raise K.KfError("hkf_app_load_map: no application")
+        return bool(r)
+
+    def frame_id(self):
+        """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
+        r = self.h.hkf_app_frame_id()
+        if r < 0:
+            raise K.KfError("hkf_app_frame_id: no application")
+        return r
+
     def close(self):
         self.h.hkf_app_shutdown()
+
+
+def map_file_info(path):
+    """hkf_map_file_info: the header of a map file after every check of the reader (magic, version, brick edge, length, keys ascending, unique and in
+    range), as a dict; raises KfError with the reader's code for a file it refuses.  Needs no GPU."""
+    h = load()
+    u, f, o, fid = (C.c_uint32 * 4)(), (C.c_float * 2)(), (C.c_int32 * 3)(), C.c_uint32()
+    pose, q = np.zeros(16, np.float32), (C.c_uint64 * 2)()
+    h.hkf_map_file_info.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    r = h.hkf_map_file_info(os.fsencode(path), u, f, o, C.byref(fid), pose.ctypes.data_as(C.c_void_p), q)
+    if r != 0:
+        raise K.KfError("map file refused: %d" % r)
+    return dict(version=int(u[0]), resolution=int(u[1]), brick_edge=int(u[2]), has_color=bool(u[3]), size=float(f[0]), max_weight=float(f[1]),
+                origin_vox=tuple(int(x) for x in o), frame_id=int(fid.value), pose=pose.reshape(4, 4), n_bricks=int(q[0]), dropped=int(q[1]))
 
 
 SLABS_LIB = os.path.join(K.PKG_DIR, "libhybkf_slabs.so")
@@ -273,6 +311,14 @@ class SlabsApp:
         if r != 0:
             raise K.KfError("viewModelMaps failed: %d" % r)
         return out
+
+    def save_map(self, path):
+        """HybKinectfuSlabs::saveMap: always False -- the map file is built on the brick store, which a slab group does not have"""
+        return self.h.hkf_slabs_save_map(os.fsencode(path)) > 0
+
+    def load_map(self, path):
+        """HybKinectfuSlabs::loadMap: always False, nothing touched"""
+        return self.h.hkf_slabs_load_map(os.fsencode(path)) > 0
 
     def close(self):
         self.h.hkf_slabs_shutdown()

@@ -121,6 +121,7 @@ SYMBOLS = [
     "kf_marching_cubes_region", "kf_region_work", "kf_world_soup_reserve", "kf_world_soup_count", "kf_read_world_soup", "kf_clear_world_soup",
     "kf_append_world_soup", "kf_set_stream_out",
     "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
+    "kf_write_brick_store", "kf_brick_store_capture", "kf_place_window",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -165,6 +166,9 @@ def load():
         _lib.kf_brick_store_clear.argtypes = [C.c_void_p]
         _lib.kf_read_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.kf_brick_store_bounds.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+        _lib.kf_write_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.kf_brick_store_capture.argtypes = [C.c_void_p]
+        _lib.kf_place_window.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -739,6 +743,25 @@ class Context:
         if n:
             _chk(self.lib.kf_read_brick_store(self.h, 0, n, _p(keys), _p(t), _p(w), _p(c) if color else None), "kf_read_brick_store")
         return keys, t, w, c
+
+    def write_brick_store(self, keys, tsdf, weight, color=None):
+        """brick_store()'s inverse: every entry with a weight > 0 into the store under its key, a held key overwritten; keys (n, 3) world brick
+        coordinates, each once; tsdf / weight (n, 8, 8, 8) in (z, y, x) order, true weights; color (n, 8, 8, 8, 3) or None (kf_write_brick_store)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        n = len(keys)
+        t, w = np.ascontiguousarray(tsdf, np.float32), np.ascontiguousarray(weight, np.float32)
+        c = np.ascontiguousarray(color, np.uint8) if color is not None else None
+        assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
+        _chk(self.lib.kf_write_brick_store(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None), "kf_write_brick_store")
+
+    def brick_store_capture(self):
+        """every observed brick of the current window into the store, without a shift; nothing moves (kf_brick_store_capture)"""
+        _chk(self.lib.kf_brick_store_capture(self.h), "kf_brick_store_capture")
+
+    def place_window(self, x, y, z):
+        """the window at origin (x, y, z) voxels, multiples of 8, filled from the store: what capture, a shift far away and a shift to there leave; the
+        model maps are stale until the next raycast (kf_place_window)"""
+        _chk(self.lib.kf_place_window(self.h, int(x), int(y), int(z)), "kf_place_window")
 
     def brick_store_bounds(self):
         """(lo, hi): the half-open box of the world brick coordinates the store holds; lo == hi for an empty or absent store (kf_brick_store_bounds)"""

@@ -565,6 +565,33 @@ int kf_brick_store_clear(kf_ctx* ctx);
 int kf_read_brick_store(kf_ctx* ctx, uint32_t first, uint32_t count, int32_t* keys, float* tsdf, float* weight, uint8_t* color);
 int kf_brick_store_bounds(kf_ctx* ctx, int32_t lo_brick[3], int32_t hi_brick[3]);
 
+/* Saving and loading the map: the store written back, the window captured, the window placed (no reference counterpart).
+ * kf_write_brick_store: kf_read_brick_store's inverse, the same layout and in-brick order.  Every entry with a weight > 0 ends up in a slot under its
+ *   key -- (tsdf, weight) pairs, colour bytes (zeros when `color` is NULL on a context with a colour plane), a deferred-weight word of 0: the weights
+ *   written are the true weights.  A key the store holds is overwritten in place: the caller's copy is the newer one.  An entry with no weight > 0 takes
+ *   no slot; with the store full an entry is counted as dropped and claims nothing.  The window, the pose, the model maps and later frames are untouched.
+ *   A written key that lies inside the current window is SHADOWED by the window's copy wherever window and store are read together (the source
+ *   precedence of kf_marching_cubes_at and kf_render_view_at), and is overwritten when that brick next leaves the window.  The entries travel through a
+ *   context-owned staging buffer (allocated by the first call, freed with the store) in chunks on the context's stream.  Blocking.  Refused with nothing
+ *   touched -- KF_ERR_ARG: a NULL context; with count > 0, NULL keys, tsdf or weight, a key component outside [-2^20, 2^20), a key that occurs twice in
+ *   the call (count == 0 writes nothing and looks at no array).
+ *   KF_ERR_STATE: no store reserved; `color` on a context without a colour plane.
+ * kf_brick_store_capture: every observed brick of the CURRENT window into the store, under the current origin, without a shift: pending weights are
+ *   flushed as kf_shift_volume flushes them, then the eviction runs over all bricks.  Nothing moves; planes (as kf_download_volume reports them), pose,
+ *   flags, tables and every later frame are bit for bit what they are without the call.  Afterwards the store alone holds the whole map (unless
+ *   kf_brick_store_count's `dropped` grew).  Asynchronous.  KF_ERR_ARG on a z-slab context; KF_ERR_STATE without a store.
+ * kf_place_window: stands the window at origin (ox, oy, oz), each a multiple of 8, filled from the store.  It leaves the state -- planes, flags,
+ *   has-negative bits, skip tables, deferred-weight words, observed-voxel count, kf_volume_origin, the store and its counts -- that
+ *   kf_brick_store_capture, a kf_shift_volume to a frame overlapping neither the old nor the new window (and no brick of the store), and a
+ *   kf_shift_volume from there to (ox, oy, oz) leave, without stream-out; the device-resident pose is translated ONCE by (new - old origin), the pose
+ *   kf_render_view_at(pose = NULL) uses for that frame.  The model maps are stale afterwards, as after a shift.  Blocks once (the store's counts):
+ *   when the capture dropped a brick the call returns KF_ERR_ALLOC with window, origin and pose untouched (what was captured are harmless copies).
+ *   Otherwise refused with nothing touched -- KF_ERR_ARG: a component that is no multiple of 8, a z-slab context, a brick of the old or the new window
+ *   outside the key range.  KF_ERR_STATE: no store. */
+int kf_write_brick_store(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color);
+int kf_brick_store_capture(kf_ctx* ctx);
+int kf_place_window(kf_ctx* ctx, int32_t ox, int32_t oy, int32_t oz);
+
 /* The map mesh: marching cubes over the brick store and the window together (no reference counterpart: the reference's one cube is its map).
  * kf_marching_cubes_at: kf_marching_cubes_region in a VIRTUAL window.  Emits exactly the triangles -- the same bytes in the same order, appended to the
  *   triangle buffer and clamped the same way -- that kf_marching_cubes_region(ctx, has_color, threshold, lo, hi, flags) would emit after
