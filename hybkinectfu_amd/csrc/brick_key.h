@@ -17,6 +17,15 @@
 
 __host__ __device__ static inline bool kf_brick_key_in_range(int64_t c) { return c >= KF_BRICK_KEY_MIN && c < KF_BRICK_KEY_MAX; }
 
+// does every brick of a window of nb bricks per axis that stands at origin_vox (voxels, multiples of 8) have a key?
+__host__ __device__ static inline bool kf_window_in_key_range(const int32_t origin_vox[3], int nb) {
+  for (int k = 0; k < 3; ++k) {
+    const int64_t b = origin_vox[k] / 8;
+    if (!kf_brick_key_in_range(b) || !kf_brick_key_in_range(b + nb - 1)) return false;
+  }
+  return true;
+}
+
 __host__ __device__ static inline unsigned long long kf_brick_key_pack(int32_t x, int32_t y, int32_t z) {
   const unsigned long long m = (1ull << KF_BRICK_KEY_BITS) - 1ull;
   return ((unsigned long long)(uint32_t)x & m) | (((unsigned long long)(uint32_t)y & m) << KF_BRICK_KEY_BITS) |

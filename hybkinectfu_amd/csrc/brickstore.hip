@@ -15,6 +15,7 @@
 #include "brick_key.h"
 #include "brick_find.h"
 #include "brick_keys_unique.h"
+#include "strip_boxes.h"
 #include <stdint.h>
 #include <new>
 #include <vector>
@@ -75,7 +76,7 @@ __global__ void __launch_bounds__(256) k_store_evict(KfVolume v, KfBrickStore st
 
 // Restore, after the move.  One workgroup iteration handles one brick that has entered the window: k_shift_bricks has left it never observed (zero
 // voxels, zero flags, zero deferred-weight word) and the shift has cleared negbits and the skip tables before the move, so a hit overwrites the
-// brick and ORs into the tables exactly as a moved brick does.  The store is only read, but for the count of restored bricks.
+// brick and ORs into the tables exactly as a moved brick does (kf_restate_brick).  The store is only read, but for the count of restored bricks.
 template <bool COLOR>
 __global__ void __launch_bounds__(256) k_store_restore(KfVolume v, KfBrickStore st, KfBrickBoxes boxes, unsigned total, int ox, int oy, int oz) {
   __shared__ unsigned s_slot[2];                         // double-buffered by iteration: a miss goes on without a second barrier
@@ -94,12 +95,7 @@ __global__ void __launch_bounds__(256) k_store_restore(KfVolume v, KfBrickStore 
     if (COLOR) reinterpret_cast<uint2*>(v.color + dst * KF_BRICK_VOX)[threadIdx.x] = reinterpret_cast<const uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x];
     const int obs = __syncthreads_or(q.y > 0.f || q.w > 0.f), neg = __syncthreads_or(q.x < 0.f || q.z < 0.f);
     if (threadIdx.x == 0) {
-      v.pend[dst] = st.pend[slot];
-      v.flags[dst] = (uint8_t)((obs ? KF_FLAG_OBSERVED : 0u) | (neg ? KF_FLAG_HASNEG : 0u));
-      if (neg) {
-        atomicOr(&v.negbits[dst >> 5], 1u << (dst & 31));
-        kf_mark_macro(v, bx, by, bz);
-      }
+      kf_restate_brick(v, dst, bx, by, bz, st.pend[slot], (obs ? KF_FLAG_OBSERVED : 0u) | (neg ? KF_FLAG_HASNEG : 0u));
       atomicAdd(&st.cnt->restored, 1ull);
     }
   }
@@ -155,34 +151,16 @@ __global__ void __launch_bounds__(256) k_store_import(KfBrickStore st, unsigned 
 }
 
 // The bricks that leave under a shift of s bricks (source brick q leaves when q - s lies outside [0, nb) on some axis), as up to three disjoint boxes:
-// the x strip in full, the y strip without the x strip, the z strip without both -- departing_boxes' decomposition (shift.hip), on bricks.  Along one
-// axis with s > 0 the bricks [0, s) leave, with s < 0 the bricks [nb + s, nb).  The bricks that ENTER (destination brick b enters when b + s lies
-// outside) are the ones that would leave under -s.  Returns the number of bricks.
+// the strip rule on bricks (strip_boxes.h, reach 0): along one axis with s > 0 the bricks [0, s) leave, with s < 0 the bricks [nb + s, nb).  The bricks
+// that ENTER (destination brick b enters when b + s lies outside) are the ones that would leave under -s.  Returns the number of bricks.
 static unsigned brick_boxes(const int s[3], int nb, bool entering, KfBrickBoxes& out) {
-  int slo[3], shi[3], klo[3], khi[3];                      // per axis: the strip, and what is left of the axis without it
-  for (int k = 0; k < 3; ++k) {
-    const int64_t ss = entering ? -(int64_t)s[k] : (int64_t)s[k];
-    if (ss > 0) { slo[k] = 0; shi[k] = (int)(ss > nb ? nb : ss); klo[k] = shi[k]; khi[k] = nb; }
-    else if (ss < 0) { shi[k] = nb; slo[k] = (int)(nb + ss < 0 ? 0 : nb + ss); klo[k] = 0; khi[k] = slo[k]; }
-    else { slo[k] = shi[k] = 0; klo[k] = 0; khi[k] = nb; }
-  }
-  int n = 0;
+  const int64_t sign = entering ? -1 : 1;
+  const int n = kf_strip_boxes(sign * s[0], sign * s[1], sign * s[2], nb, 0, out.lo, out.hi);
   unsigned total = 0;
   for (int k = 0; k < 3; ++k) {
-    if (slo[k] >= shi[k]) continue;
-    uint64_t vol = 1;
-    for (int j = 0; j < 3; ++j) {
-      out.lo[n][j] = j < k ? klo[j] : (j == k ? slo[j] : 0);
-      out.hi[n][j] = j < k ? khi[j] : (j == k ? shi[j] : nb);
-      vol *= out.lo[n][j] < out.hi[n][j] ? (uint64_t)(out.hi[n][j] - out.lo[n][j]) : 0u;
-    }
-    if (vol == 0) continue;
-    total += (unsigned)vol;                                // <= nb^3 <= 2^30 (kf_create: at most 1024 bricks per axis)
-    out.end[n++] = total;
-  }
-  for (int k = n; k < 3; ++k) {
+    if (k < n) total += (unsigned)(out.hi[k][0] - out.lo[k][0]) * (unsigned)(out.hi[k][1] - out.lo[k][1]) * (unsigned)(out.hi[k][2] - out.lo[k][2]);   // <= nb^3 <= 2^30
+    else for (int j = 0; j < 3; ++j) { out.lo[k][j] = 0; out.hi[k][j] = 1; }                                                  // (kf_create: at most 1024 bricks per axis)
     out.end[k] = total;
-    for (int j = 0; j < 3; ++j) { out.lo[k][j] = 0; out.hi[k][j] = 1; }
   }
   return total;
 }
@@ -307,10 +285,7 @@ extern "C" int kf_brick_store_capture(kf_ctx* c) {
   if (!c) return KF_ERR_ARG;
   if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
-  for (int k = 0; k < 3; ++k) {                              // (a window that shifts with a store reserved never leaves the key range; one that moved before the reserve may have)
-    const int64_t b = c->origin_vox[k] / KF_BRICK;
-    if (!kf_brick_key_in_range(b) || !kf_brick_key_in_range(b + c->vol.nb - 1)) return KF_ERR_ARG;
-  }
+  if (!kf_window_in_key_range(c->origin_vox, c->vol.nb)) return KF_ERR_ARG;   // (a window that shifts with a store reserved never leaves the key range; one that moved before the reserve may have)
   KF_CHECK(hipSetDevice(c->cfg.device));
   return kf_brick_store_capture_enqueue(c);
 }

@@ -468,6 +468,23 @@ __device__ __forceinline__ void kf_mark_macro(const KfVolume& v, int bx, int by,
   const unsigned qi = (unsigned)((((bz >> 1) * v.nq) + (by >> 1)) * v.nq + (bx >> 1));       // the meso cell: 2 bricks per edge
   atomicOr(&v.macrobits[v.macro_words + v.super_words + (qi >> 5)], 1u << (qi & 31u));
 }
+// A brick has landed in slot dst = brick (bx, by, bz) -- moved there (shift.hip) or restored from the store (brickstore.hip) -- and the workgroup has reduced
+// its flags fl: one thread restates the deferred-weight word, the flags byte, the has-negative bit and the skip tables.  negbits and the skip tables were
+// cleared before the window's contents changed: only atomicOr here.
+__device__ __forceinline__ void kf_restate_brick(const KfVolume& v, size_t dst, int bx, int by, int bz, unsigned long long pend, unsigned fl) {
+  v.pend[dst] = pend;
+  v.flags[dst] = (uint8_t)fl;
+  if (fl & KF_FLAG_HASNEG) {
+    atomicOr(&v.negbits[dst >> 5], 1u << (dst & 31));
+    kf_mark_macro(v, bx, by, bz);
+  }
+}
+// The translation of a pose when the window moves by d voxels: t - (float)d * cell, one rounded fp32 operation each (the library is built without contraction)
+__device__ __forceinline__ void kf_shift_translation(const float* pose, float* out, int dx, int dy, int dz, float cell) {
+  out[3] = pose[3] - (float)dx * cell;
+  out[7] = pose[7] - (float)dy * cell;
+  out[11] = pose[11] - (float)dz * cell;
+}
 __host__ __device__ static inline size_t kf_skip_table_words(const KfVolume& v) { return (size_t)v.macro_words + (size_t)v.super_words + (size_t)v.meso_words; }
 __device__ __forceinline__ unsigned kf_brick_slot(const KfVolume& v, int bx, int by, int bz) {
   return __umul24(__umul24((unsigned)(bz - v.bz0), (unsigned)v.nb) + (unsigned)by, (unsigned)v.nb) + (unsigned)bx;

@@ -191,7 +191,7 @@ extern "C" int kf_marching_cubes_at(kf_ctx* c, int has_color, float thr, const i
   if (!c || !frame_origin_vox || !lo || !hi) return KF_ERR_ARG;
   for (int k = 0; k < 3; ++k) if (frame_origin_vox[k] % KF_BRICK) return KF_ERR_ARG;
   { const int cs = mapmesh::check_common(c, has_color, flags); if (cs) return cs; }
-  if (!mapmesh::frame_in_key_range(frame_origin_vox, c->vol.nb)) return KF_ERR_ARG;
+  if (!kf_window_in_key_range(frame_origin_vox, c->vol.nb)) return KF_ERR_ARG;
   return mapmesh::enqueue_at(c, has_color, thr, frame_origin_vox, lo, hi, flags);
 }
 
@@ -211,7 +211,7 @@ extern "C" int kf_marching_cubes_map(kf_ctx* c, int has_color, float thr, int fl
   if (n < 0 || n > (int64_t)1 << 24) return KF_ERR_ARG;
   std::vector<int32_t> frames((size_t)n * 3);
   kf_map_tiles(slo, shi, c->origin_vox, R, frames.data(), n);
-  for (int64_t t = 0; t < n; ++t) if (!mapmesh::frame_in_key_range(&frames[3 * t], c->vol.nb)) return KF_ERR_ARG;     // refused before the first tile is enqueued
+  for (int64_t t = 0; t < n; ++t) if (!kf_window_in_key_range(&frames[3 * t], c->vol.nb)) return KF_ERR_ARG;     // refused before the first tile is enqueued
   const int32_t lo[3] = {KF_MAP_TILE_MARGIN, KF_MAP_TILE_MARGIN, KF_MAP_TILE_MARGIN}, hi[3] = {R - KF_MAP_TILE_MARGIN, R - KF_MAP_TILE_MARGIN, R - KF_MAP_TILE_MARGIN};
   for (int64_t t = 0; t < n; ++t) {
     const int as = mapmesh::enqueue_at(c, has_color, thr, &frames[3 * t], lo, hi, KF_MC_WORLD);

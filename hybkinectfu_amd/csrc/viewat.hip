@@ -6,7 +6,7 @@
 //   resolve : map_resolve_brick over ALL nb^3 bricks of the virtual window, a wave per brick -- the window's copy, else the store's slot, else the zero
 //             brick -- into the call's own indirection table; a brick with a negative voxel sets its bit in the virtual has-negative bits and marks its
 //             macro, super and meso cell in the virtual skip tables (kf_mark_macro's indexing).  All tables are cleared on the stream first.
-//   pose    : for pose == NULL, t - (float)d * cell per axis (k_shift_pose's arithmetic) from the device-resident pose into the scratch: no read-back.
+//   pose    : for pose == NULL, t - (float)d * cell per axis (kf_shift_translation, shared with k_shift_pose) from the device-resident pose into the scratch: no read-back.
 //   march   : raycast_tile<false, VIEW> of raycast_tile.h, compiled a second time here with the addressing hooks redefined: the sample's voxel, the lazily
 //             fetched previous sample, the trilinear taps, the colour taps go through the table, the has-negative flag is the virtual bit.  LDS placement,
 //             KF_RAYCAST_* switches, tile bounds, tile and workgroup shape follow raycast_args exactly as for kf_render_view.  The shared-neighbourhood
@@ -73,13 +73,11 @@ __global__ void __launch_bounds__(256) k_view_resolve(KfVolume v, KfVolume vv, K
   }
 }
 
-// the device-resident pose as kf_shift_volume(d) would leave it (k_shift_pose: one rounded fp32 operation each; the library is built without contraction)
+// the device-resident pose as kf_shift_volume(d) would leave it (kf_shift_translation, as in k_shift_pose)
 __global__ void k_view_pose(const KfTrackState* __restrict__ st, float* __restrict__ out, int dx, int dy, int dz, float cell) {
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   for (int i = 0; i < 16; ++i) out[i] = st->pose[i];
-  out[3] = st->pose[3] - (float)dx * cell;
-  out[7] = st->pose[7] - (float)dy * cell;
-  out[11] = st->pose[11] - (float)dz * cell;
+  kf_shift_translation(st->pose, out, dx, dy, dz, cell);
 }
 
 // the scratch: [zero brick | table | skip tables | has-negative bits | pose]; every part a multiple of 16 bytes
@@ -124,7 +122,7 @@ extern "C" int kf_render_view_at(kf_ctx* c, int mode, const int32_t frame_origin
   if (mode == KF_VIEW_COLOR && !c->vol.color) return KF_ERR_STATE;
   const KfVolume& v = c->vol;
   if (v.own_z0 > 0 || v.own_z1 < v.res || v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_STATE;      // a z-slab context, kf_render_view's code
-  if (!mapmesh::frame_in_key_range(frame_origin_vox, v.nb)) return KF_ERR_ARG;
+  if (!kf_window_in_key_range(frame_origin_vox, v.nb)) return KF_ERR_ARG;
   int d[3];
   for (int k = 0; k < 3; ++k) {                                            // the shift that would bring the window there: kf_shift_volume takes 32-bit components
     const int64_t dd = (int64_t)frame_origin_vox[k] - (int64_t)c->origin_vox[k];

@@ -100,13 +100,4 @@ __device__ __forceinline__ McVBrick map_resolve_brick(const KfVolume& v, const K
   return e;
 }
 
-// does every brick of the frame at `fo` (voxels, multiples of 8) have a key?
-static inline bool frame_in_key_range(const int32_t fo[3], int nb) {
-  for (int k = 0; k < 3; ++k) {
-    const int64_t b = fo[k] / KF_BRICK;
-    if (!kf_brick_key_in_range(b) || !kf_brick_key_in_range(b + nb - 1)) return false;
-  }
-  return true;
-}
-
 }  // namespace mapmesh

@@ -4,6 +4,7 @@
 // hkf_departing_boxes: which cells a shift makes unextractable for good -- the boxes kf_shift_volume's stream-out sends to the world soup.
 // Nothing here touches the device or another translation unit, so a stand-alone program can run it under a sanitizer (tests/shift_host_main.cpp).
 #include "hybkf_host.hpp"
+#include "../csrc/strip_boxes.h"
 #include <math.h>
 
 extern "C" void hkf_recentre_shift(const float pose[16], float size_m, uint32_t res, float dist, int32_t out[3]) {
@@ -51,29 +52,10 @@ extern "C" void hkf_view_frame(const float world_pose[16], float size_m, uint32_
 
 // The cells whose 27 voxels (x-1 .. x+1 each way) include a voxel that leaves the window when it moves by d: along one axis with d > 0 voxels
 // < d leave, so cells [0, d + 1); with d < 0 cells [res + d - 1, res); |d| >= res: every cell.  Over several axes the union, as disjoint boxes
-// in a fixed order: the x strip in full, the y strip without the x strip, the z strip without both.  Only non-empty boxes are written.
+// in a fixed order: the x strip in full, the y strip without the x strip, the z strip without both (strip_boxes.h, reach 1).  Only non-empty boxes are written.
 extern "C" int hkf_departing_boxes(const int32_t d[3], uint32_t res, int32_t lo[3][3], int32_t hi[3][3]) {
   if (res == 0 || res > 0x40000000u) return 0;
-  const int64_t R = (int64_t)res;
-  int64_t slo[3], shi[3], klo[3], khi[3];                          // per axis: the strip, and what the axis keeps without it
-  for (int k = 0; k < 3; ++k) {
-    const int64_t dd = d[k];
-    if (dd > 0) { slo[k] = 0; shi[k] = dd + 1 > R ? R : dd + 1; klo[k] = shi[k]; khi[k] = R; }
-    else if (dd < 0) { shi[k] = R; slo[k] = R + dd - 1 < 0 ? 0 : R + dd - 1; klo[k] = 0; khi[k] = slo[k]; }
-    else { slo[k] = shi[k] = 0; klo[k] = 0; khi[k] = R; }
-  }
-  int n = 0;
-  for (int k = 0; k < 3; ++k) {
-    if (slo[k] >= shi[k]) continue;
-    bool empty = false;
-    for (int j = 0; j < 3; ++j) {
-      const int64_t l = j < k ? klo[j] : (j == k ? slo[j] : 0), h = j < k ? khi[j] : (j == k ? shi[j] : R);
-      lo[n][j] = (int32_t)l; hi[n][j] = (int32_t)h;
-      if (l >= h) empty = true;
-    }
-    if (!empty) ++n;
-  }
-  return n;
+  return kf_strip_boxes(d[0], d[1], d[2], res, 1, lo, hi);
 }
 
 extern "C" void hkf_world_pose(float pose[16], const int32_t o[3], float cell) {

@@ -459,7 +459,7 @@ int kf_read_layer_work(kf_ctx* ctx, uint64_t* out, int reset);                /*
 int kf_shift_volume(kf_ctx* ctx, int32_t dx, int32_t dy, int32_t dz);
 int kf_volume_origin(kf_ctx* ctx, int32_t origin_vox[3]);
 
-/* The moving volume on z-slab contexts (slabshift.hip): what a slab group runs on its members (hybkf_group.h: kf_group_shift_volume).  kf_shift_volume
+/* The moving volume on z-slab contexts (shift.hip): what a slab group runs on its members (hybkf_group.h: kf_group_shift_volume).  kf_shift_volume
  * itself keeps refusing a z-slab context.  A context stores brick layers [bz0, bz1) = kf_stored_z_range / 8.
  * THE RULE: stored destination brick (bx, by, p) takes source brick (bx + dx/8, by + dy/8, p + dz/8) -- from the context's own copy where that layer is
  *   stored here (owned or halo: a halo layer holds its owner's bits), else from the feed buffer where the layer lies in the feed range, else it reads

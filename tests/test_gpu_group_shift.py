@@ -21,6 +21,7 @@ from hybkinectfu_amd import scene as S
 from test_gpu_group import bits, check_frame, check_volume, whole_frame
 from test_gpu_shift import moved_pose, np_shift, walk_pose, H_RES, H_SIZE, H_DIST
 from test_gpu_shift import CAM as SMALL_CAM
+import test_gpu_shift as SH
 
 pytestmark = pytest.mark.gpu
 P = S.STOCK
@@ -115,6 +116,32 @@ def test_shift_slab_on_a_whole_volume_context_equals_shift_volume():
             for map_id in (K.MAP_MODEL_VERTICES, K.MAP_MODEL_NORMALS):
                 assert np.array_equal(bits(a.download_map(map_id, level)), bits(b.download_map(map_id, level))), (d, level, map_id)
     assert a.volume_origin() == (8, -16, -16)
+    a.close(); b.close()
+
+
+def test_shift_slab_equals_shift_volume_with_colour_on_every_walked_axis():
+    """The two launch forms of the one brick move, on whole-volume colour contexts (64^3: 8 bricks per axis) after five fused frames: each of x, y and z
+    as the walked axis in both signs, a combined shift, and one that makes everything leave (|s| >= nb).  Bytes of tsdf, weight, colour, pose and origin,
+    and of the model maps and the raycast colours after a raycast."""
+    a, b = SH.make_ctx(64, True), SH.make_ctx(64, True)
+    SH.fuse(a, range(5), True)
+    SH.fuse(b, range(5), True)
+    shifts = [(8, 0, 0), (-8, 0, 0), (0, 8, 0), (0, -8, 0), (0, 0, 8), (0, 0, -8), (8, -8, 16), (0, -64, 0)]
+    for d in shifts:
+        a.shift_volume(*d)
+        b.shift_slab(*d)
+        pa, pb = SH.planes(a, True), SH.planes(b, True)
+        for x, y, what in zip(pa, pb, ("tsdf", "weight", "colour")):
+            assert SH.same_bits(x, y), (d, what)
+        assert SH.same_bits(pose_of(a), pose_of(b)) and a.volume_origin() == b.volume_origin(), d
+        if d != shifts[-1]:
+            assert np.count_nonzero(pa[1]) > 1000 and np.any(pa[0] < 0) and np.count_nonzero(pa[2]) > 1000, d      # something moved
+        else:
+            assert not pa[1].any() and not pa[2].any()
+        SH.raycast(a, True)
+        SH.raycast(b, True)
+        SH.assert_same_model(a, b, True)
+    assert a.volume_origin() == (8, -72, 16)
     a.close(); b.close()
 
 

@@ -98,3 +98,13 @@ def test_departing_boxes_under_sanitizers(tmp_path):
                            os.path.join(host, "recentre.cpp"), "-o", exe])
     out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     assert out.returncode == 0 and "stream host arithmetic ok" in out.stdout, out.stdout
+
+
+def test_strip_boxes_under_sanitizers(tmp_path):
+    """strip_boxes.h (the one statement of the strip rule, behind hkf_departing_boxes, the stream-out's boxes and the brick store's) + a main of its
+    own, -fsanitize=address,undefined, run on the CPU: n in {1, 2, 5, 8}, both reaches, every move in [-n-2, n+2]^3; nothing is loaded into Python"""
+    exe = str(tmp_path / "strip_boxes_main")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-I", os.path.join(ROOT, "hybkinectfu_amd", "csrc"), os.path.join(ROOT, "tests", "strip_boxes_main.cpp"), "-o", exe])
+    out = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0 and "strip boxes ok" in out.stdout, out.stdout
