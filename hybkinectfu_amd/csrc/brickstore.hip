@@ -150,6 +150,83 @@ __global__ void __launch_bounds__(256) k_store_import(KfBrickStore st, unsigned 
   }
 }
 
+// one voxel of kf_merge_brick_store's rule: a (held, TRUE weight) with b (incoming) -> the weighted running average of tsdfVolume.h:65-70, map to map.
+// One rounded fp32 operation per source operation (-ffp-contract=off; `/` is the correctly rounded division).  `blend`: both weights > 0, the colour is averaged
+// too; `take`: only b has been observed, b is copied verbatim -- (tb * wb) / wb is not always tb.  Neither: a stays, its weight stored as the true one.
+// (The two flags travel by value: as reference parameters they were kept in scratch.)
+__device__ __forceinline__ float2 merge_voxel(float ta, float wa, float tb, float wb, float max_weight, bool take, bool blend) {
+  if (blend) {
+    const float s = wa + wb;
+    return make_float2((ta * wa + tb * wb) / s, fminf(s, max_weight));
+  }
+  return take ? make_float2(tb, wb) : make_float2(ta, wa);
+}
+__device__ __forceinline__ unsigned merge_channel(unsigned ca, float wa, unsigned cb, float wb) {
+  return (unsigned)(unsigned char)fminf(255.f, ((float)ca * wa + (float)cb * wb) / (wa + wb));
+}
+// the packed colour (x | y << 8 | z << 16, fourth byte 0) of one voxel
+__device__ __forceinline__ unsigned merge_color(unsigned ca, float wa, unsigned cb, float wb, bool take, bool blend) {
+  if (take) return cb;
+  if (!blend) return ca;
+  return merge_channel(ca & 255u, wa, cb & 255u, wb) | (merge_channel((ca >> 8) & 255u, wa, (cb >> 8) & 255u, wb) << 8) |
+         (merge_channel((ca >> 16) & 255u, wa, (cb >> 16) & 255u, wb) << 16);
+}
+
+// Merge for kf_merge_brick_store: k_store_import's shape and staging layout, the keys translated by (ox, oy, oz) bricks.  Thread 0 looks the key up; a key
+// the store does not hold claims a slot and is written as k_store_import writes it, bit for bit.  A held slot is read, merged voxel by voxel and written
+// back in place: each lane the two voxels it loaded, the held weight being the TRUE weight (the slot's deferred-weight word applied as k_store_export
+// applies it; a lane's two voxels lie in quarter threadIdx.x >> 6).  Every weight written is a true weight, so the word becomes 0.  Thread 0 reads the
+// word before the barrier and is the only one to write it, and every key occurs once per launch: no two workgroups, and no two lanes, meet in a slot.
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_store_merge(KfBrickStore st, unsigned count, const int32_t* __restrict__ keys, const float* __restrict__ tsdf,
+                                                     const float* __restrict__ weight, const unsigned char* __restrict__ color, int ox, int oy, int oz,
+                                                     float max_weight) {
+  __shared__ unsigned s_slot, s_fresh;
+  __shared__ unsigned long long s_pend;
+  for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
+    const size_t o = (size_t)e * KF_BRICK_VOX;
+    const float2 t = reinterpret_cast<const float2*>(tsdf + o)[threadIdx.x];
+    const float2 w = reinterpret_cast<const float2*>(weight + o)[threadIdx.x];
+    if (!__syncthreads_or(w.x > 0.f || w.y > 0.f)) continue;                  // (workgroup-uniform) never observed: takes no slot, changes no held one
+    const unsigned long long key = kf_brick_key_pack(keys[3 * e] + ox, keys[3 * e + 1] + oy, keys[3 * e + 2] + oz);
+    if (threadIdx.x == 0) {                                                   // everybody has read the last iteration's words: the barrier above
+      unsigned slot = store_find(st, key);
+      const bool fresh = slot == KF_BRICK_NO_SLOT;
+      if (fresh) slot = store_claim(st, key);
+      s_slot = slot; s_fresh = fresh ? 1u : 0u;
+      s_pend = fresh ? 0ull : st.pend[slot];
+    }
+    __syncthreads();
+    const unsigned slot = s_slot;
+    if (slot == KF_BRICK_NO_SLOT) continue;                                   // the store is full: counted as dropped
+    unsigned cb0 = 0u, cb1 = 0u;                                              // the incoming colours of the lane's two voxels, packed
+    if (COLOR && color) {
+      const unsigned short* cs = reinterpret_cast<const unsigned short*>(color + 3 * o) + 3u * threadIdx.x;
+      const unsigned a = cs[0], b = cs[1], c = cs[2];                         // the bytes of two voxels: c0 c1 | c2 c0' | c1' c2'
+      cb0 = a | ((b & 255u) << 16); cb1 = (b >> 8) | (c << 8);
+    }
+    float4* tw = reinterpret_cast<float4*>(st.tw + (size_t)slot * KF_BRICK_VOX) + threadIdx.x;
+    if (s_fresh) {                                                            // (workgroup-uniform) k_store_import's write
+      *tw = make_float4(t.x, w.x, t.y, w.y);
+      if (COLOR) reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_uint2(cb0, cb1);
+      if (threadIdx.x == 0) { st.pend[slot] = 0ull; st.key[slot] = key; }
+      continue;
+    }
+    const unsigned pq = (unsigned)(s_pend >> (16u * (threadIdx.x >> 6))) & 0xFFFFu;   // (wave-uniform)
+    const float4 h = *tw;
+    const float wa0 = kf_pend_weight(h.y, pq, max_weight), wa1 = kf_pend_weight(h.w, pq, max_weight);
+    const bool blend0 = w.x > 0.f && wa0 > 0.f, take0 = w.x > 0.f && !(wa0 > 0.f), blend1 = w.y > 0.f && wa1 > 0.f, take1 = w.y > 0.f && !(wa1 > 0.f);
+    const float2 r0 = merge_voxel(h.x, wa0, t.x, w.x, max_weight, take0, blend0), r1 = merge_voxel(h.z, wa1, t.y, w.y, max_weight, take1, blend1);
+    *tw = make_float4(r0.x, r0.y, r1.x, r1.y);
+    if (COLOR && color) {                                                     // no colour given (kernel-uniform): the held colour stays
+      uint2* cp = reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX) + threadIdx.x;
+      const uint2 ca = *cp;
+      *cp = make_uint2(merge_color(ca.x, wa0, cb0, w.x, take0, blend0), merge_color(ca.y, wa1, cb1, w.y, take1, blend1));
+    }
+    if (threadIdx.x == 0) st.pend[slot] = 0ull;                               // (st.key[slot] stays)
+  }
+}
+
 // The bricks that leave under a shift of s bricks (source brick q leaves when q - s lies outside [0, nb) on some axis), as up to three disjoint boxes:
 // the strip rule on bricks (strip_boxes.h, reach 0): along one axis with s > 0 the bricks [0, s) leave, with s < 0 the bricks [nb + s, nb).  The bricks
 // that ENTER (destination brick b enters when b + s lies outside) are the ones that would leave under -s.  Returns the number of bricks.
@@ -292,7 +369,9 @@ extern "C" int kf_brick_store_capture(kf_ctx* c) {
 
 // kf_write_brick_store: the staging buffer holds KF_BSTORE_STAGE_BRICKS entries, plane after plane -- keys, tsdf, weight, colour bytes -- each plane 16-byte aligned
 #define KF_BSTORE_STAGE_BRICKS 256u
-extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color) {
+// kf_write_brick_store and kf_merge_brick_store: the checks, the staging and the chunked launches are one path.  off == nullptr: a write (the keys as they
+// are, k_store_import); else a merge (the keys translated by off, whole bricks, k_store_merge).  Refused before anything is touched.
+static int store_put(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color, const int32_t* off) {
   if (!c) return KF_ERR_ARG;
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   if (color && !c->bstore.color) return KF_ERR_STATE;
@@ -301,8 +380,13 @@ extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
   try {                                                      // (no exception crosses the C boundary)
     std::vector<unsigned long long> packed(count);
     for (uint32_t i = 0; i < count; ++i) {
-      for (int k = 0; k < 3; ++k) if (!kf_brick_key_in_range(keys[3 * (size_t)i + k])) return KF_ERR_ARG;
-      packed[i] = kf_brick_key_pack(keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
+      int32_t k3[3];
+      for (int k = 0; k < 3; ++k) {
+        const int64_t t = (int64_t)keys[3 * (size_t)i + k] + (off ? off[k] : 0);   // (64 bits: the sum of two int32 cannot overflow)
+        if (!kf_brick_key_in_range(t)) return KF_ERR_ARG;
+        k3[k] = (int32_t)t;
+      }
+      packed[i] = kf_brick_key_pack(k3[0], k3[1], k3[2]);
     }
     if (!kf_brick_keys_unique(packed.data(), packed.size())) return KF_ERR_ARG;
   } catch (const std::bad_alloc&) { return KF_ERR_ALLOC; }
@@ -313,6 +397,7 @@ extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
   unsigned char* base = (unsigned char*)c->bstore_stage;
   int32_t* dk = (int32_t*)base; float *dt = (float*)(base + off_t), *dw = (float*)(base + off_w); unsigned char* dc = base + off_c;
   const bool with_color = color && c->bstore.color;
+  const unsigned char* kc = with_color ? dc : (unsigned char*)nullptr;
   hipError_t e = hipSuccess;
   for (uint32_t first = 0; first < count && e == hipSuccess; first += KF_BSTORE_STAGE_BRICKS) {   // stream order: a chunk's launch has read the buffer before the next chunk's copies write it
     const uint32_t n = count - first < KF_BSTORE_STAGE_BRICKS ? count - first : KF_BSTORE_STAGE_BRICKS;
@@ -323,10 +408,23 @@ extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
     if (e == hipSuccess && with_color) e = hipMemcpyAsync(dc, color + 3 * at, vox * 3, hipMemcpyHostToDevice, c->stream);
     if (e != hipSuccess) break;
     const dim3 grid(n), block(256);                          // n <= KF_BSTORE_STAGE_BRICKS: below store_pass's cap of 4096 workgroups
-    if (c->bstore.color) hipLaunchKernelGGL(k_store_import<true>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, with_color ? dc : (unsigned char*)nullptr);
-    else hipLaunchKernelGGL(k_store_import<false>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, (unsigned char*)nullptr);
+    if (!off) {                                              // (k_store_import is named first: instantiations are emitted in this order, and its listing stays what it was)
+      if (c->bstore.color) hipLaunchKernelGGL(k_store_import<true>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, kc);
+      else hipLaunchKernelGGL(k_store_import<false>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, (unsigned char*)nullptr);
+    } else {
+      if (c->bstore.color) hipLaunchKernelGGL(k_store_merge<true>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, kc, (int)off[0], (int)off[1], (int)off[2], c->vol.max_weight);
+      else hipLaunchKernelGGL(k_store_merge<false>, grid, block, 0, c->stream, c->bstore, n, dk, dt, dw, (unsigned char*)nullptr, (int)off[0], (int)off[1], (int)off[2], c->vol.max_weight);
+    }
     e = hipGetLastError();
   }
   const hipError_t se = hipStreamSynchronize(c->stream);     // on success and on failure alike: no copy out of the caller's arrays is still queued when the call returns
   return (int)(e != hipSuccess ? e : se);
+}
+extern "C" int kf_write_brick_store(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color) {
+  return store_put(c, count, keys, tsdf, weight, color, nullptr);
+}
+extern "C" int kf_merge_brick_store(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
+                                    const int32_t offset_brick[3]) {
+  static const int32_t zero[3] = {0, 0, 0};
+  return store_put(c, count, keys, tsdf, weight, color, offset_brick ? offset_brick : zero);
 }

@@ -140,7 +140,8 @@ static bool moved_origin(const kf_ctx* c, const int32_t d[3], int32_t org[3]) {
 
 // The bookkeeping of a wholesale change, in kf_resize_slab's order, past the caller's tail-cull discard and flush: the serial, the tables cleared for the
 // atomicOrs to come, the pose moved by d.  `empty`: the window itself is cleared too, to what the move leaves of a window everything has left (kf_place_window).
-static int window_change(kf_ctx* c, const int32_t d[3], bool empty) {
+// d == nullptr: the window stays where it is (kf_refill_window) -- no pose move, not even by zero: the pose and its inverse are not written at all.
+static int window_change(kf_ctx* c, const int32_t* d, bool empty) {
   KfVolume& v = c->vol;
   ++c->vol_flags_serial;
   c->wgt0_valid = 0;
@@ -153,7 +154,7 @@ static int window_change(kf_ctx* c, const int32_t d[3], bool empty) {
     KF_CHECK(hipMemsetAsync(v.flags, 0, c->n_stored_bricks, c->stream));
     KF_CHECK(hipMemsetAsync(v.pend, 0, c->n_stored_bricks * sizeof(unsigned long long), c->stream));
   }
-  hipLaunchKernelGGL(k_shift_pose, dim3(1), dim3(64), 0, c->stream, c->track, (int)d[0], (int)d[1], (int)d[2], v.cell);
+  if (d) hipLaunchKernelGGL(k_shift_pose, dim3(1), dim3(64), 0, c->stream, c->track, (int)d[0], (int)d[1], (int)d[2], v.cell);
   return 0;
 }
 
@@ -237,6 +238,24 @@ extern "C" int kf_place_window(kf_ctx* c, int32_t ox, int32_t oy, int32_t oz) {
   { const int ws = window_change(c, d, true); if (ws) return ws; }
   for (int k = 0; k < 3; ++k) c->origin_vox[k] = org[k];
   const int all[3] = {v.nb, 0, 0};                                // what enters when everything has left: one box of all bricks
+  { const int rs = kf_brick_store_restore(c, all, c->origin_vox); if (rs) return rs; }
+  return (int)hipGetLastError();
+}
+
+// kf_refill_window: kf_place_window at the current origin with the capture left out -- the window is re-read from the store as the store is NOW.  That is
+// what a merge into the store needs (kf_merge_brick_store): a key inside the window is shadowed by the window's copy, and kf_place_window would capture
+// that stale copy over the merged slot before it refills.  The window does not move, so the pose is not touched; a brick the store does not hold reads as
+// never observed afterwards.  Asynchronous: no allocation, no synchronisation, no read-back.
+extern "C" int kf_refill_window(kf_ctx* c) {
+  if (!c) return KF_ERR_ARG;
+  KfVolume& v = c->vol;
+  if (v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_ARG;
+  if (!c->bstore.max_bricks) return KF_ERR_STATE;
+  if (!kf_window_in_key_range(c->origin_vox, v.nb)) return KF_ERR_ARG;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  { const int ds = kf_tail_cull_discard(c); if (ds) return ds; }
+  { const int ws = window_change(c, nullptr, true); if (ws) return ws; }   // (the deferred-weight words are cleared with the planes: nothing to flush)
+  const int all[3] = {v.nb, 0, 0};
   { const int rs = kf_brick_store_restore(c, all, c->origin_vox); if (rs) return rs; }
   return (int)hipGetLastError();
 }

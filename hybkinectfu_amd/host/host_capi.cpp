@@ -163,6 +163,12 @@ int hkf_app_brick_store_count(uint64_t out3[3]) {
 // Returns 0 or the reader's HKF_MAP_ERR_* (negative).
 int hkf_app_save_map(const char* path) { if (!g_app) return -1; return path && g_app->saveMap(path) ? 1 : 0; }
 int hkf_app_load_map(const char* path) { if (!g_app) return -1; return path && g_app->loadMap(path) ? 1 : 0; }
+// HybKinectfu::mergeMap, the offset in whole bricks: 1 merged, 0 refused or failed, -1 without an application
+int hkf_app_merge_map(const char* path, int ox, int oy, int oz) {
+  if (!g_app) return -1;
+  const int off[3] = {ox, oy, oz};
+  return path && g_app->mergeMap(path, off) ? 1 : 0;
+}
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
 int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {
   HkfMapHeader h;

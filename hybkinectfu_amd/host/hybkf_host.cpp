@@ -520,6 +520,64 @@ bool HybKinectfu::loadMap(const std::string& path) {
   return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
                                           p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
 }
+bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  const int32_t off[3] = {offsetBricks ? offsetBricks[0] : 0, offsetBricks ? offsetBricks[1] : 0, offsetBricks ? offsetBricks[2] : 0};
+  lastTracked();                                                // a frame still in flight settles first: the raycast below uses this session's pose
+  // 1. the whole file checked, every translated key in range, the volume this instance's: nothing is touched before
+  HkfMapHeader h;
+  const int is = hkf_map_info_offset(path.c_str(), off, &h);
+  if (is != HKF_MAP_OK || h.resolution != p->_volume_params.nResolution || memcmp(&h.size_m, &p->_volume_params.fVolumeMeterSize, 4) != 0 ||
+      memcmp(&h.max_weight, &p->_volume_params.fWeightMax, 4) != 0 || (h.has_color != 0) != p->_switch_params.useRGBData) {
+    fprintf(stderr, "mergeMap: %s refused (%d)%s\n", path.c_str(), is, is == HKF_MAP_OK ? ": its volume is not this instance's" : "");
+    return false;
+  }
+  const bool color = h.has_color != 0;
+  // a store that was never reserved: room for whatever the capture may bring (every brick of the window); the file's bricks are added below
+  if (p->_volume_params.nBrickStoreBricks == 0) {
+    const uint64_t nb = p->_volume_params.nResolution / 8u;
+    if (!setBrickStore((unsigned)(nb * nb * nb))) return false;
+  }
+  // 2. the window into the store: afterwards the store alone is this session's map
+  uint32_t held = 0; uint64_t dropped_before = 0, dropped = 0;
+  if (dm->check(kf_brick_store_count(ctx, nullptr, &dropped_before, nullptr))) return false;
+  if (dm->check(kf_brick_store_capture(ctx))) return false;
+  if (dm->check(kf_brick_store_count(ctx, &held, &dropped, nullptr))) return false;
+  if (dropped != dropped_before) {
+    fprintf(stderr, "mergeMap: the brick store is full: %llu bricks of the window did not fit; nothing merged\n", (unsigned long long)(dropped - dropped_before));
+    return false;
+  }
+  // 3. room for every brick of the file (all of them new, at worst): the store read out, reserved larger, written back -- the bricks verbatim, true weights
+  const uint64_t want = (uint64_t)held + h.n_bricks;
+  if (want > 0xFFFFFFFFull) return false;
+  if (want > p->_volume_params.nBrickStoreBricks) {
+    std::vector<int32_t> keys((size_t)held * 3);
+    std::vector<float> t((size_t)held * HKF_MAP_BRICK_VOX), w((size_t)held * HKF_MAP_BRICK_VOX);
+    std::vector<uint8_t> col(color ? (size_t)held * HKF_MAP_BRICK_VOX * 3 : 0);
+    if (held && dm->check(kf_read_brick_store(ctx, 0, held, keys.data(), t.data(), w.data(), color ? col.data() : nullptr))) return false;
+    if (!setBrickStore((unsigned)want)) return false;
+    if (held && dm->check(kf_write_brick_store(ctx, held, keys.data(), t.data(), w.data(), color ? col.data() : nullptr))) return false;
+  }
+  // 4. the file's bricks, translated, merged chunk by chunk (a file's keys are unique, so every call's are)
+  std::vector<int32_t> moved((size_t)kMapChunkBricks * 3);
+  const int st = hkf_map_read(path.c_str(), kMapChunkBricks, HkfMapAccept(), [&](uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* c) {
+    if (!hkf_map_offset_keys(count, keys, off, moved.data())) return false;
+    return 0 == dm->check(kf_merge_brick_store(ctx, count, moved.data(), tsdf, weight, c, nullptr));
+  });
+  if (st != HKF_MAP_OK) fprintf(stderr, "mergeMap: reading %s failed (%d): the store holds the bricks merged so far\n", path.c_str(), st);
+  // 5. the window shows the merged store (also after a failed read: window and store must not disagree); 6. shiftVolume's raycast, this session's pose
+  if (dm->check(kf_refill_window(ctx))) return false;
+  const Mat44 pose = _camera_pose_finder->getCameraPose();
+  const bool resident = _camera_pose_finder->deviceResident();
+  const kf_mat44 kp = to_kf(pose);
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
+  if (dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
+                                  p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc))) return false;
+  return st == HKF_MAP_OK;
+}
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();
   int32_t d[3];

@@ -297,6 +297,15 @@ public:
   // raw context.  A finder that keeps its pose on the host does not see such a move: placing the window behind this class's back is not supported there.
   bool saveMap(const std::string& path);
   bool loadMap(const std::string& path);
+  // mergeMap: fuses the map file into this session's map, voxel by voxel (kf_merge_brick_store: the weighted running average, exact in fp32, so merging
+  // A into B and B into A give the same bricks).  offsetBricks (nullptr: zero) translates the file's keys by whole bricks into this session's world
+  // frame; finding that offset, and offsets that are no whole bricks, are the caller's business.  The file is checked as loadMap checks it, and every
+  // translated key must lie in the key range: refused (false) with nothing touched otherwise.  Then: the window is captured into the store (false when a
+  // brick did not fit), the store is grown to held + the file's bricks where its capacity is below that (read out, reserved, written back: its dropped and
+  // restored counts start again), the file's bricks are merged, the window is re-read from the store (kf_refill_window) and the model maps are raycast
+  // as shiftVolume does, so the next processNewFrame is TRACKED against the merged model.  Pose and frame id stay this session's; the file's pose,
+  // origin and frame id are ignored.  A store that was never reserved is reserved by the call, with room for every brick of the window.
+  bool mergeMap(const std::string& path, const int offsetBricks[3]);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();

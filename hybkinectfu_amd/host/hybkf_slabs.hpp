@@ -59,6 +59,7 @@ public:
   // HybKinectfu's map on disk is built on the brick store, a single-GPU feature: a slab group has no store to save from or load into.  Always false.
   bool saveMap(const std::string&) { return false; }
   bool loadMap(const std::string&) { return false; }
+  bool mergeMap(const std::string&, const int*) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

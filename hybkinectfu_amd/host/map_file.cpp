@@ -105,8 +105,20 @@ int hkf_map_write(const char* path, const HkfMapHeader& h, uint32_t chunk, const
   return st;
 }
 
-// every check; leaves `f` anywhere
-static int check_file(FILE* f, HkfMapHeader& h) {
+bool hkf_map_offset_keys(uint32_t count, const int32_t* keys, const int32_t offset[3], int32_t* out) {
+  if (count && (!keys || !out)) return false;
+  for (int pass = 0; pass < 2; ++pass) {                       // all checked before the first is written
+    for (size_t i = 0; i < (size_t)count * 3; ++i) {
+      const int64_t t = (int64_t)keys[i] + (offset ? offset[i % 3] : 0);
+      if (pass == 0) { if (!kf_brick_key_in_range(t)) return false; }
+      else out[i] = (int32_t)t;
+    }
+  }
+  return true;
+}
+
+// every check; leaves `f` anywhere.  offset != nullptr: every key must stay in range when translated by it
+static int check_file(FILE* f, HkfMapHeader& h, const int32_t* offset = nullptr) {
   uint8_t head[HKF_MAP_HEADER_BYTES];
   if (!seek_to(f, 0)) return HKF_MAP_ERR_IO;
   if (fread(head, 1, sizeof(head), f) != sizeof(head) || memcmp(head, kMagic, 8) != 0) return HKF_MAP_ERR_MAGIC;
@@ -128,21 +140,23 @@ static int check_file(FILE* f, HkfMapHeader& h) {
     const uint64_t w = order_word(k);
     if (i && w <= last) return HKF_MAP_ERR_KEYS;
     last = w;
+    if (offset && !hkf_map_offset_keys(1, k, offset, k)) return HKF_MAP_ERR_KEYS;
   }
   return HKF_MAP_OK;
 }
 
-int hkf_map_info(const char* path, HkfMapHeader* out) {
+int hkf_map_info_offset(const char* path, const int32_t offset[3], HkfMapHeader* out) {
   if (!path || !out) return HKF_MAP_ERR_ARG;
   FILE* f = fopen(path, "rb");
   if (!f) return HKF_MAP_ERR_IO;
   HkfMapHeader h;
   memset(&h, 0, sizeof(h));
-  const int st = check_file(f, h);
+  const int st = check_file(f, h, offset);
   fclose(f);
   if (st == HKF_MAP_OK) *out = h;
   return st;
 }
+int hkf_map_info(const char* path, HkfMapHeader* out) { return hkf_map_info_offset(path, nullptr, out); }
 
 int hkf_map_read(const char* path, uint32_t chunk, const HkfMapAccept& accept, const HkfMapApply& apply) {
   if (!path || !apply || chunk == 0) return HKF_MAP_ERR_ARG;

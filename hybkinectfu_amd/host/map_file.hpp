@@ -66,3 +66,11 @@ int hkf_map_write(const char* path, const HkfMapHeader& h, uint32_t chunk, const
 int hkf_map_info(const char* path, HkfMapHeader* out);
 // hkf_map_info's checks, then accept(header) (may be empty: accepted), then the records in chunks of at most `chunk`
 int hkf_map_read(const char* path, uint32_t chunk, const HkfMapAccept& accept, const HkfMapApply& apply);
+
+// Merging a map that was recorded in another world frame (HybKinectfu::mergeMap): the file's keys translated by a whole number of bricks.
+// hkf_map_offset_keys: out[i] = keys[i] + offset (out may be keys itself; offset NULL: zero) for `count` keys of three components.  The sums are taken in
+// 64 bits, so no int32 overflows, and every translated component must lie in the key range [-2^20, 2^20): false, with `out` untouched, when one does
+// not.  Adding a constant keeps the (z, y, x) order of the records, so translated records need no re-sort.
+bool hkf_map_offset_keys(uint32_t count, const int32_t* keys, const int32_t offset[3], int32_t* out);
+// hkf_map_info's checks, then every key of the file translated by `offset`: HKF_MAP_ERR_KEYS when a translated key leaves the key range
+int hkf_map_info_offset(const char* path, const int32_t offset[3], HkfMapHeader* out);

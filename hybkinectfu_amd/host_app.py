@@ -196,6 +196,15 @@ class App:
             raise K.KfError("hkf_app_load_map: no application")
         return bool(r)
 
+    def merge_map(self, path, offset=(0, 0, 0)):
+        """HybKinectfu::mergeMap: the file's map fused into this session's voxel by voxel (the weighted running average), its keys translated by
+        `offset` whole bricks; the window shows the result and the next process_frame is tracked against it.  Pose and frame id stay.  False, with
+        nothing touched: a file load_map would refuse, or a translated key outside the key range"""
+        r = self.h.hkf_app_merge_map(os.fsencode(path), int(offset[0]), int(offset[1]), int(offset[2]))
+        if r < 0:
+            raise K.KfError("hkf_app_merge_map: no application")
+        return bool(r)
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -319,6 +328,10 @@ class SlabsApp:
     def load_map(self, path):
         """HybKinectfuSlabs::loadMap: always False, nothing touched"""
         return self.h.hkf_slabs_load_map(os.fsencode(path)) > 0
+
+    def merge_map(self, path, offset=(0, 0, 0)):
+        """always False, nothing touched: merging maps is built on the brick store, which a slab group does not have"""
+        return self.h.hkf_slabs_merge_map(os.fsencode(path), int(offset[0]), int(offset[1]), int(offset[2])) > 0
 
     def close(self):
         self.h.hkf_slabs_shutdown()

@@ -122,6 +122,7 @@ SYMBOLS = [
     "kf_append_world_soup", "kf_set_stream_out",
     "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
     "kf_write_brick_store", "kf_brick_store_capture", "kf_place_window",
+    "kf_merge_brick_store", "kf_refill_window",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -169,6 +170,8 @@ def load():
         _lib.kf_write_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.kf_brick_store_capture.argtypes = [C.c_void_p]
         _lib.kf_place_window.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        _lib.kf_merge_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+        _lib.kf_refill_window.argtypes = [C.c_void_p]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -762,6 +765,23 @@ class Context:
         """the window at origin (x, y, z) voxels, multiples of 8, filled from the store: what capture, a shift far away and a shift to there leave; the
         model maps are stale until the next raycast (kf_place_window)"""
         _chk(self.lib.kf_place_window(self.h, int(x), int(y), int(z)), "kf_place_window")
+
+    def merge_brick_store(self, keys, tsdf, weight, color=None, offset=(0, 0, 0)):
+        """write_brick_store's arguments, but a key the store holds is merged with the entry voxel by voxel -- the weighted running average, exact in
+        fp32 -- instead of overwritten; offset: whole bricks added to every key first.  The store only: follow with refill_window() to see the result in
+        the window (kf_merge_brick_store)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        n = len(keys)
+        t, w = np.ascontiguousarray(tsdf, np.float32), np.ascontiguousarray(weight, np.float32)
+        c = np.ascontiguousarray(color, np.uint8) if color is not None else None
+        assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
+        off = (C.c_int32 * 3)(*(int(x) for x in offset)) if offset is not None else None
+        _chk(self.lib.kf_merge_brick_store(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None, off), "kf_merge_brick_store")
+
+    def refill_window(self):
+        """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never
+        observed afterwards; pose and origin stay, the model maps are stale until the next raycast (kf_refill_window)"""
+        _chk(self.lib.kf_refill_window(self.h), "kf_refill_window")
 
     def brick_store_bounds(self):
         """(lo, hi): the half-open box of the world brick coordinates the store holds; lo == hi for an empty or absent store (kf_brick_store_bounds)"""

@@ -592,6 +592,37 @@ int kf_write_brick_store(kf_ctx* ctx, uint32_t count, const int32_t* keys, const
 int kf_brick_store_capture(kf_ctx* ctx);
 int kf_place_window(kf_ctx* ctx, int32_t ox, int32_t oy, int32_t oz);
 
+/* Merging maps: a second map fused into the store voxel by voxel, the window re-read from the store (no reference counterpart; the rule is the
+ * reference's frame-into-volume running average, tsdfVolume.h:65-70, applied map to map).
+ * kf_merge_brick_store: kf_write_brick_store's layout, in-brick order, staging, chunking and blocking behaviour, but a key the store already holds is
+ *   MERGED with the incoming entry where a write overwrites it.  offset_brick (NULL: zero) is added to every key first: a translation by whole bricks
+ *   between the two sessions' world frames; the key range [-2^20, 2^20) applies to the translated key.  A rigid transform between the maps -- a
+ *   rotation, or a translation that is no whole number of bricks -- needs resampling and is not offered.  The target is the store only: a translated
+ *   key inside the current window is shadowed by the window's copy exactly as a written one is (see kf_refill_window).
+ *   An entry with no weight > 0 does nothing: it takes no slot and changes no held one.  A key not held claims a slot and is copied verbatim (colour
+ *   zeros when `color` is NULL on a context with a colour plane), bit for bit what kf_write_brick_store writes; with the store full it is counted as
+ *   dropped and claims nothing.  A key held is merged per voxel, in fp32, one rounded operation per operation written here, the division correctly
+ *   rounded; a = the held voxel with its TRUE weight wa (what kf_read_brick_store reports), b = the incoming one:
+ *     wb <= 0:   the voxel keeps ta and its colour; the weight stored is wa
+ *     wa <= 0:   the voxel becomes (tb, wb, cb) verbatim ((tb * wb) / wb is not always tb)
+ *     both > 0:  s = wa + wb;  t = (ta * wa + tb * wb) / s;  w = fminf(s, max_weight);
+ *                each colour channel (unsigned char)fminf(255.f, ((float)ca * wa + (float)cb * wb) / s)
+ *   With `color` NULL on a context with a colour plane the colour of a held slot stays as it is, whatever the weights.  The slot's deferred-weight
+ *   word becomes 0: every weight now stored is a true weight.  fp32 add and multiply commute, so A merged with B equals B merged with A, bit for bit.
+ *   Refused with nothing touched, as kf_write_brick_store -- KF_ERR_ARG: a NULL context; with count > 0, NULL keys, tsdf or weight, a translated key
+ *   component out of range, a key that occurs twice in the call (count == 0 does nothing and looks at no array).  KF_ERR_STATE: no store reserved;
+ *   `color` on a context without a colour plane.
+ * kf_refill_window: re-reads the window from the store under its CURRENT origin -- the state kf_place_window(current origin) would leave if it did not
+ *   capture the window first: the tail cull discarded, the flags serial bumped, the observed-voxel count re-based, the model maps stale, skip tables,
+ *   has-negative bits, planes, flags and deferred-weight words cleared and every brick the store holds restored.  The pose and its inverse are not
+ *   written at all, kf_volume_origin is unchanged, and the store is only read (its `restored` count grows by the hits).  This is how a merged store
+ *   reaches the window: kf_place_window would capture the window's stale copy over the merged slots first.  A window brick the store does NOT hold
+ *   reads as never observed afterwards: call kf_brick_store_capture first to keep such bricks.  Asynchronous, no allocation, no synchronisation.
+ *   KF_ERR_ARG: a NULL context, a z-slab context, a brick of the window outside the key range.  KF_ERR_STATE: no store. */
+int kf_merge_brick_store(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
+                         const int32_t offset_brick[3]);
+int kf_refill_window(kf_ctx* ctx);
+
 /* The map mesh: marching cubes over the brick store and the window together (no reference counterpart: the reference's one cube is its map).
  * kf_marching_cubes_at: kf_marching_cubes_region in a VIRTUAL window.  Emits exactly the triangles -- the same bytes in the same order, appended to the
  *   triangle buffer and clamped the same way -- that kf_marching_cubes_region(ctx, has_color, threshold, lo, hi, flags) would emit after
