@@ -14,6 +14,7 @@
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"
+#include "store_merge.h"
 #include "brick_keys_unique.h"
 #include "strip_boxes.h"
 #include <stdint.h>
@@ -32,23 +33,6 @@ __device__ __forceinline__ void box_brick(const KfBrickBoxes& b, unsigned i, int
   const int lz = k == 0 ? b.lo[0][2] : (k == 1 ? b.lo[1][2] : b.lo[2][2]);
   const unsigned ex = (unsigned)(hx - lx), ey = (unsigned)(hy - ly);
   bx = lx + (int)(j % ex); by = ly + (int)((j / ex) % ey); bz = lz + (int)(j / (ex * ey));
-}
-
-// one lane per departing brick: the slot the brick is written to, or KF_BRICK_NO_SLOT when the store is full (counted as dropped)
-__device__ __forceinline__ unsigned store_claim(const KfBrickStore& st, unsigned long long key) {
-  const unsigned known = store_find(st, key);              // (other workgroups insert OTHER keys meanwhile: whether this one is there cannot change)
-  if (known != KF_BRICK_NO_SLOT) return known;
-  const unsigned slot = atomicAdd(&st.cnt->held, 1u);      // first sight: the next slot.  Once `held` has reached max_bricks every taker fails and undoes
-  if (slot >= st.max_bricks) {                             // its own step, so a successful taker always saw the number of successes before it
-    atomicSub(&st.cnt->held, 1u);
-    atomicAdd(&st.cnt->dropped, 1ull);
-    return KF_BRICK_NO_SLOT;
-  }
-  unsigned h = kf_brick_key_hash(key, st.mask);
-  for (unsigned p = 0; p <= st.mask; ++p, h = (h + 1u) & st.mask) {   // at most max_bricks <= (mask + 1) / 2 entries are taken: a free one exists
-    if (atomicCAS(&st.tkey[h], KF_BRICK_KEY_EMPTY, key) == KF_BRICK_KEY_EMPTY) { st.tslot[h] = slot; return slot; }
-  }
-  return KF_BRICK_NO_SLOT;                                 // (not reached)
 }
 
 // Eviction, before anything moves.  One workgroup iteration handles one departing brick of the window, 256 lanes x one float4 (two voxels), for
@@ -150,28 +134,7 @@ __global__ void __launch_bounds__(256) k_store_import(KfBrickStore st, unsigned 
   }
 }
 
-// one voxel of kf_merge_brick_store's rule: a (held, TRUE weight) with b (incoming) -> the weighted running average of tsdfVolume.h:65-70, map to map.
-// One rounded fp32 operation per source operation (-ffp-contract=off; `/` is the correctly rounded division).  `blend`: both weights > 0, the colour is averaged
-// too; `take`: only b has been observed, b is copied verbatim -- (tb * wb) / wb is not always tb.  Neither: a stays, its weight stored as the true one.
-// (The two flags travel by value: as reference parameters they were kept in scratch.)
-__device__ __forceinline__ float2 merge_voxel(float ta, float wa, float tb, float wb, float max_weight, bool take, bool blend) {
-  if (blend) {
-    const float s = wa + wb;
-    return make_float2((ta * wa + tb * wb) / s, fminf(s, max_weight));
-  }
-  return take ? make_float2(tb, wb) : make_float2(ta, wa);
-}
-__device__ __forceinline__ unsigned merge_channel(unsigned ca, float wa, unsigned cb, float wb) {
-  return (unsigned)(unsigned char)fminf(255.f, ((float)ca * wa + (float)cb * wb) / (wa + wb));
-}
-// the packed colour (x | y << 8 | z << 16, fourth byte 0) of one voxel
-__device__ __forceinline__ unsigned merge_color(unsigned ca, float wa, unsigned cb, float wb, bool take, bool blend) {
-  if (take) return cb;
-  if (!blend) return ca;
-  return merge_channel(ca & 255u, wa, cb & 255u, wb) | (merge_channel((ca >> 8) & 255u, wa, (cb >> 8) & 255u, wb) << 8) |
-         (merge_channel((ca >> 16) & 255u, wa, (cb >> 16) & 255u, wb) << 16);
-}
-
+// (store_claim and the voxel rule of a merge -- merge_voxel, merge_color -- are shared with resample.hip: store_merge.h)
 // Merge for kf_merge_brick_store: k_store_import's shape and staging layout, the keys translated by (ox, oy, oz) bricks.  Thread 0 looks the key up; a key
 // the store does not hold claims a slot and is written as k_store_import writes it, bit for bit.  A held slot is read, merged voxel by voxel and written
 // back in place: each lane the two voxels it loaded, the held weight being the TRUE weight (the slot's deferred-weight word applied as k_store_export

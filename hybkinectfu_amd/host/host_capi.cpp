@@ -169,6 +169,14 @@ int hkf_app_merge_map(const char* path, int ox, int oy, int oz) {
   const int off[3] = {ox, oy, oz};
   return path && g_app->mergeMap(path, off) ? 1 : 0;
 }
+// HybKinectfu::mergeMap under a rigid transform: m = the row-major 4x4 from the file's world frame to this session's, in metres.  Same answers
+int hkf_app_merge_map_rigid(const char* path, const float m[16]) {
+  if (!g_app) return -1;
+  if (!path || !m) return 0;
+  Mat44 t;
+  memcpy(t.entries, m, 64);
+  return g_app->mergeMap(path, t) ? 1 : 0;
+}
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
 int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {
   HkfMapHeader h;

@@ -8,6 +8,7 @@
 #include <stdio.h>
 #include <algorithm>
 #include <fstream>
+#include <new>
 #include <unordered_map>
 #include <unordered_set>
 
@@ -520,28 +521,26 @@ bool HybKinectfu::loadMap(const std::string& path) {
   return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
                                           p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
 }
-bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
-  if (!_inited) return false;
-  AppParams* p = AppParams::instance();
-  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
-  kf_ctx* ctx = dm->ctx();
-  const int32_t off[3] = {offsetBricks ? offsetBricks[0] : 0, offsetBricks ? offsetBricks[1] : 0, offsetBricks ? offsetBricks[2] : 0};
-  lastTracked();                                                // a frame still in flight settles first: the raycast below uses this session's pose
-  // 1. the whole file checked, every translated key in range, the volume this instance's: nothing is touched before
-  HkfMapHeader h;
-  const int is = hkf_map_info_offset(path.c_str(), off, &h);
+// the file's status and header against this instance's volume: resolution, size, max weight and colour flag
+static bool merge_file_is_ours(const std::string& path, int is, const HkfMapHeader& h) {
+  const AppParams* p = AppParams::instance();
   if (is != HKF_MAP_OK || h.resolution != p->_volume_params.nResolution || memcmp(&h.size_m, &p->_volume_params.fVolumeMeterSize, 4) != 0 ||
       memcmp(&h.max_weight, &p->_volume_params.fWeightMax, 4) != 0 || (h.has_color != 0) != p->_switch_params.useRGBData) {
     fprintf(stderr, "mergeMap: %s refused (%d)%s\n", path.c_str(), is, is == HKF_MAP_OK ? ": its volume is not this instance's" : "");
     return false;
   }
-  const bool color = h.has_color != 0;
-  // a store that was never reserved: room for whatever the capture may bring (every brick of the window); the file's bricks are added below
+  return true;
+}
+bool HybKinectfu::mergeMakeRoom(bool color, uint64_t incoming) {
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  // a store that was never reserved: room for whatever the capture may bring (every brick of the window); the incoming bricks are added below
   if (p->_volume_params.nBrickStoreBricks == 0) {
     const uint64_t nb = p->_volume_params.nResolution / 8u;
     if (!setBrickStore((unsigned)(nb * nb * nb))) return false;
   }
-  // 2. the window into the store: afterwards the store alone is this session's map
+  // the window into the store: afterwards the store alone is this session's map
   uint32_t held = 0; uint64_t dropped_before = 0, dropped = 0;
   if (dm->check(kf_brick_store_count(ctx, nullptr, &dropped_before, nullptr))) return false;
   if (dm->check(kf_brick_store_capture(ctx))) return false;
@@ -550,8 +549,8 @@ bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
     fprintf(stderr, "mergeMap: the brick store is full: %llu bricks of the window did not fit; nothing merged\n", (unsigned long long)(dropped - dropped_before));
     return false;
   }
-  // 3. room for every brick of the file (all of them new, at worst): the store read out, reserved larger, written back -- the bricks verbatim, true weights
-  const uint64_t want = (uint64_t)held + h.n_bricks;
+  // room for every incoming brick (all of them new, at worst): the store read out, reserved larger, written back -- the bricks verbatim, true weights
+  const uint64_t want = (uint64_t)held + incoming;
   if (want > 0xFFFFFFFFull) return false;
   if (want > p->_volume_params.nBrickStoreBricks) {
     std::vector<int32_t> keys((size_t)held * 3);
@@ -561,6 +560,32 @@ bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
     if (!setBrickStore((unsigned)want)) return false;
     if (held && dm->check(kf_write_brick_store(ctx, held, keys.data(), t.data(), w.data(), color ? col.data() : nullptr))) return false;
   }
+  return true;
+}
+bool HybKinectfu::mergeShow() {
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  if (dm->check(kf_refill_window(ctx))) return false;
+  const Mat44 pose = _camera_pose_finder->getCameraPose();
+  const bool resident = _camera_pose_finder->deviceResident();
+  const kf_mat44 kp = to_kf(pose);
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
+  return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
+                                          p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
+}
+bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
+  if (!_inited) return false;
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  const int32_t off[3] = {offsetBricks ? offsetBricks[0] : 0, offsetBricks ? offsetBricks[1] : 0, offsetBricks ? offsetBricks[2] : 0};
+  lastTracked();                                                // a frame still in flight settles first: the raycast below uses this session's pose
+  // 1. the whole file checked, every translated key in range, the volume this instance's: nothing is touched before
+  HkfMapHeader h;
+  const int is = hkf_map_info_offset(path.c_str(), off, &h);
+  if (!merge_file_is_ours(path, is, h)) return false;
+  // 2. the window captured; 3. room for every brick of the file
+  if (!mergeMakeRoom(h.has_color != 0, h.n_bricks)) return false;
   // 4. the file's bricks, translated, merged chunk by chunk (a file's keys are unique, so every call's are)
   std::vector<int32_t> moved((size_t)kMapChunkBricks * 3);
   const int st = hkf_map_read(path.c_str(), kMapChunkBricks, HkfMapAccept(), [&](uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* c) {
@@ -569,14 +594,57 @@ bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
   });
   if (st != HKF_MAP_OK) fprintf(stderr, "mergeMap: reading %s failed (%d): the store holds the bricks merged so far\n", path.c_str(), st);
   // 5. the window shows the merged store (also after a failed read: window and store must not disagree); 6. shiftVolume's raycast, this session's pose
-  if (dm->check(kf_refill_window(ctx))) return false;
-  const Mat44 pose = _camera_pose_finder->getCameraPose();
-  const bool resident = _camera_pose_finder->deviceResident();
-  const kf_mat44 kp = to_kf(pose);
-  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};
-  if (dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
-                                  p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc))) return false;
+  if (!mergeShow()) return false;
   return st == HKF_MAP_OK;
+}
+bool HybKinectfu::mergeMap(const std::string& path, const Mat44& srcToDst) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  lastTracked();
+  // 1. the file checked, the volume this instance's; the transform in voxels: the cell is the fp32 quotient the volume uses
+  HkfMapHeader h;
+  const int is = hkf_map_info(path.c_str(), &h);
+  if (!merge_file_is_ours(path, is, h)) return false;
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  double xf[12];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) xf[4 * i + j] = (double)srcToDst.entries[4 * i + j];
+    xf[4 * i + 3] = (double)srcToDst.entries[4 * i + 3] / (double)cell;
+  }
+  const bool color = h.has_color != 0;
+  if (h.n_bricks > 0xFFFFFFFFull) return false;
+  // 2. the whole file in host memory (a destination brick draws on up to 27 of its bricks: no chunks), and its candidate bricks: still nothing touched
+  std::vector<int32_t> keys;
+  std::vector<float> t, w;
+  std::vector<uint8_t> col;
+  int64_t candidates = -1;
+  try {
+    keys.reserve((size_t)h.n_bricks * 3); t.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX); w.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX);
+    if (color) col.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX * 3);
+    const int st = hkf_map_read(path.c_str(), kMapChunkBricks, HkfMapAccept(), [&](uint32_t count, const int32_t* k, const float* tsdf, const float* weight, const uint8_t* c) {
+      keys.insert(keys.end(), k, k + (size_t)count * 3);
+      t.insert(t.end(), tsdf, tsdf + (size_t)count * HKF_MAP_BRICK_VOX);
+      w.insert(w.end(), weight, weight + (size_t)count * HKF_MAP_BRICK_VOX);
+      if (color && c) col.insert(col.end(), c, c + (size_t)count * HKF_MAP_BRICK_VOX * 3);
+      return true;
+    });
+    if (st != HKF_MAP_OK || keys.size() != (size_t)h.n_bricks * 3 || (color && col.size() != t.size() * 3)) {
+      fprintf(stderr, "mergeMap: reading %s failed (%d); nothing merged\n", path.c_str(), st);
+      return false;
+    }
+  } catch (const std::bad_alloc&) { return false; }
+  candidates = kf_rigid_brick_keys((uint32_t)h.n_bricks, keys.data(), xf, nullptr, 0);
+  if (candidates < 0) {
+    fprintf(stderr, "mergeMap: %s refused: the matrix is no rigid transform, or it moves a brick out of the key range\n", path.c_str());
+    return false;
+  }
+  // 3. the window captured, room for every candidate brick; 4. one merge; 5. the window shows the merged store; 6. the raycast
+  if (!mergeMakeRoom(color, (uint64_t)candidates)) return false;
+  const int ms = dm->check(kf_merge_brick_store_rigid(ctx, (uint32_t)h.n_bricks, keys.data(), t.data(), w.data(), color ? col.data() : nullptr, xf));
+  if (!mergeShow()) return false;
+  return ms == 0;
 }
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();

@@ -306,9 +306,21 @@ public:
   // as shiftVolume does, so the next processNewFrame is TRACKED against the merged model.  Pose and frame id stay this session's; the file's pose,
   // origin and frame id are ignored.  A store that was never reserved is reserved by the call, with room for every brick of the window.
   bool mergeMap(const std::string& path, const int offsetBricks[3]);
+  // mergeMap under a rigid transform: srcToDst maps the file's world frame to this session's, in metres, as poses are (entries[3], [7], [11] the
+  // translation).  The file's map is resampled at this session's voxel centres (kf_merge_brick_store_rigid: trilinear, the least weight of the corners),
+  // then merged as above.  In voxels the translation is (double)t_m / (double)cell with cell the fp32 quotient size / resolution; the rotation is taken
+  // as it stands.  The same checks and the same steps as the other mergeMap, but: the whole file is read into host memory, the candidate bricks
+  // (kf_rigid_brick_keys) take the place of the file's bricks when the store is grown, and the merge is one call.  Refused (false) with nothing touched
+  // also for a matrix that is no rigid transform (kf_rigid_brick_keys' rule) or that moves a brick out of the key range.  A file of another cell size is
+  // refused like any other volume that is not this instance's.
+  bool mergeMap(const std::string& path, const Mat44& srcToDst);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();
+  // the steps both mergeMaps share.  mergeMakeRoom: a store reserved if there was none, the window captured, the store grown to held + `incoming` bricks;
+  // mergeShow: the window re-read from the store, the model maps raycast from this session's pose
+  bool mergeMakeRoom(bool color, uint64_t incoming);
+  bool mergeShow();
   Mat44 worldPose(const Mat44& pose);
   void copyFrameToGPU(const DepthFrameData& depth_frame, const ColorFrameData& color_frame);
   CameraPoseFinder* _camera_pose_finder;

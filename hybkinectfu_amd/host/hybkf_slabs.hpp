@@ -60,6 +60,7 @@ public:
   bool saveMap(const std::string&) { return false; }
   bool loadMap(const std::string&) { return false; }
   bool mergeMap(const std::string&, const int*) { return false; }
+  bool mergeMap(const std::string&, const Mat44&) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

@@ -132,5 +132,6 @@ int hkf_slabs_save_map(const char* path) { if (!g_slabs) return -1; return path 
 int hkf_slabs_load_map(const char* path) { if (!g_slabs) return -1; return path && g_slabs->loadMap(path) ? 1 : 0; }
 // merging maps is built on the brick store too: always -1, nothing touched
 int hkf_slabs_merge_map(const char*, int, int, int) { return -1; }
+int hkf_slabs_merge_map_rigid(const char*, const float*) { return -1; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

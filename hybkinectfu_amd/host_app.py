@@ -205,6 +205,16 @@ class App:
             raise K.KfError("hkf_app_merge_map: no application")
         return bool(r)
 
+    def merge_map_rigid(self, path, mat):
+        """HybKinectfu::mergeMap under a rigid transform: `mat` (4x4, metres, as poses are) maps the file's world frame to this session's; the file's map is
+        resampled at this session's voxel centres and merged.  False, with nothing touched: a file load_map would refuse, a matrix that is no rigid
+        transform, a brick moved out of the key range"""
+        m = np.ascontiguousarray(mat, np.float32).reshape(16)
+        r = self.h.hkf_app_merge_map_rigid(os.fsencode(path), m.ctypes.data_as(C.c_void_p))
+        if r < 0:
+            raise K.KfError("hkf_app_merge_map_rigid: no application")
+        return bool(r)
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -332,6 +342,11 @@ class SlabsApp:
     def merge_map(self, path, offset=(0, 0, 0)):
         """always False, nothing touched: merging maps is built on the brick store, which a slab group does not have"""
         return self.h.hkf_slabs_merge_map(os.fsencode(path), int(offset[0]), int(offset[1]), int(offset[2])) > 0
+
+    def merge_map_rigid(self, path, mat):
+        """always False, nothing touched, as merge_map"""
+        m = np.ascontiguousarray(mat, np.float32).reshape(16)
+        return self.h.hkf_slabs_merge_map_rigid(os.fsencode(path), m.ctypes.data_as(C.c_void_p)) > 0
 
     def close(self):
         self.h.hkf_slabs_shutdown()

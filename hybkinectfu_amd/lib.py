@@ -122,7 +122,7 @@ SYMBOLS = [
     "kf_append_world_soup", "kf_set_stream_out",
     "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
     "kf_write_brick_store", "kf_brick_store_capture", "kf_place_window",
-    "kf_merge_brick_store", "kf_refill_window",
+    "kf_merge_brick_store", "kf_refill_window", "kf_merge_brick_store_rigid", "kf_rigid_brick_keys",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -172,6 +172,9 @@ def load():
         _lib.kf_place_window.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
         _lib.kf_merge_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
         _lib.kf_refill_window.argtypes = [C.c_void_p]
+        _lib.kf_merge_brick_store_rigid.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
+        _lib.kf_rigid_brick_keys.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int64]
+        _lib.kf_rigid_brick_keys.restype = C.c_int64
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -200,6 +203,26 @@ def map_tiles(store_lo, store_hi, origin_vox, res):
 
 class KfError(RuntimeError):
     pass
+
+
+def rigid_xf(xf):
+    """a 3x4 [R | t] as the double[12] the C ABI takes"""
+    return (C.c_double * 12)(*np.asarray(xf, np.float64).reshape(12).tolist())
+
+
+def rigid_brick_keys(keys, xf):
+    """the candidate destination bricks (n, 3), sorted by (z, y, x), of a source map with brick keys `keys` under xf = [R | t], source -> destination, t in
+    voxels (kf_rigid_brick_keys)"""
+    lib = load()
+    keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+    x = rigid_xf(xf)
+    n = lib.kf_rigid_brick_keys(len(keys), _p(keys), x, None, 0)
+    if n < 0:
+        raise KfError("kf_rigid_brick_keys: no rigid transform, or a candidate brick outside the key range")
+    out = np.zeros((n, 3), np.int32)
+    if n:
+        lib.kf_rigid_brick_keys(len(keys), _p(keys), x, _p(out), n)
+    return out
 
 
 def _chk(st, what):
@@ -777,6 +800,16 @@ class Context:
         assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
         off = (C.c_int32 * 3)(*(int(x) for x in offset)) if offset is not None else None
         _chk(self.lib.kf_merge_brick_store(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None, off), "kf_merge_brick_store")
+
+    def merge_brick_store_rigid(self, keys, tsdf, weight, color, xf):
+        """merge_brick_store's arrays, but the map is first resampled under xf = [R | t] (3x4, source world -> this store's world, t in voxels): trilinear
+        in tsdf and colour, the least weight of the corners, unobserved where a corner is; then merged by the same rule (kf_merge_brick_store_rigid)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        n = len(keys)
+        t, w = np.ascontiguousarray(tsdf, np.float32), np.ascontiguousarray(weight, np.float32)
+        c = np.ascontiguousarray(color, np.uint8) if color is not None else None
+        assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
+        _chk(self.lib.kf_merge_brick_store_rigid(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None, rigid_xf(xf)), "kf_merge_brick_store_rigid")
 
     def refill_window(self):
         """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never

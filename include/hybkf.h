@@ -597,7 +597,7 @@ int kf_place_window(kf_ctx* ctx, int32_t ox, int32_t oy, int32_t oz);
  * kf_merge_brick_store: kf_write_brick_store's layout, in-brick order, staging, chunking and blocking behaviour, but a key the store already holds is
  *   MERGED with the incoming entry where a write overwrites it.  offset_brick (NULL: zero) is added to every key first: a translation by whole bricks
  *   between the two sessions' world frames; the key range [-2^20, 2^20) applies to the translated key.  A rigid transform between the maps -- a
- *   rotation, or a translation that is no whole number of bricks -- needs resampling and is not offered.  The target is the store only: a translated
+ *   rotation, or a translation that is no whole number of bricks -- needs resampling: kf_merge_brick_store_rigid, below.  The target is the store only: a translated
  *   key inside the current window is shadowed by the window's copy exactly as a written one is (see kf_refill_window).
  *   An entry with no weight > 0 does nothing: it takes no slot and changes no held one.  A key not held claims a slot and is copied verbatim (colour
  *   zeros when `color` is NULL on a context with a colour plane), bit for bit what kf_write_brick_store writes; with the store full it is counted as
@@ -622,6 +622,42 @@ int kf_place_window(kf_ctx* ctx, int32_t ox, int32_t oy, int32_t oz);
 int kf_merge_brick_store(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
                          const int32_t offset_brick[3]);
 int kf_refill_window(kf_ctx* ctx);
+
+/* Merging maps under a rigid transform: the incoming (source) map is resampled at the destination's voxel centres, then merged as above.
+ * Coordinates are world voxel indices: voxel g (brick key g >> 3, in-brick g & 7) has its centre at (g + 1/2) * cell.  xf is a row-major 3x4 [R | t], source
+ * world -> destination world, t in voxels: destination voxel d lies at s = R^T (d + 1/2 - t) - 1/2 in the source.  A VALID transform: all 12 values finite,
+ * max |R^T R - I| <= 1e-5 (a rotation stored in fp32 is orthonormal to a few 1e-7; the rest is room for a pose accumulated over a sequence), det R > 0.
+ * kf_rigid_brick_keys (no context, host only): the candidate destination bricks of a source map.  For every source brick k the 8 corners p of the box
+ *   [8k - 1, 8k + 8]^3 (the positions s whose corners floor(s), floor(s) + 1 can touch the brick) are mapped by
+ *   d_i = (((R[i][0] (p_0 + 1/2) + R[i][1] (p_1 + 1/2)) + R[i][2] (p_2 + 1/2)) + t_i) - 1/2 in fp64; every destination brick (>> 3) that the box
+ *   floor(min d) .. ceil(max d) touches is a candidate.  Unique, sorted by (z, y, x).  Returns the number of candidates and writes the first `cap` keys
+ *   (three int32 each); -1: NULL keys with count > 0, NULL xf, NULL out_keys with cap > 0, an invalid transform, a candidate outside the key range
+ *   [-2^20, 2^20).  A candidate too many is harmless: it resamples to nothing and takes no slot.
+ * kf_merge_brick_store_rigid: kf_read_brick_store's layout for the source map (count entries: keys, tsdf, weight, colour bytes or NULL).  Blocks.
+ *   Per candidate brick K, in fp64 on the host:  a = 8 K + 0.5 - t;  c_j = ((R[0][j] a_0 + R[1][j] a_1) + R[2][j] a_2) - 0.5;  ib = floor(c) (int32);
+ *     fb = (float)(c - ib), and an fb that rounds to 1.0f becomes ib + 1, 0.f.
+ *   Per voxel l in [0, 8)^3 of the brick, in fp32, one rounded operation per operation written here, Rf = (float)R:
+ *     u_j = ((Rf[0][j] lx + Rf[1][j] ly) + Rf[2][j] lz) + fb_j;  n_j = floorf(u_j);  f_j = u_j - n_j;  base corner i_j = ib_j + (int)n_j.
+ *   Corners: i + {0, 1}^3, the +1 neighbour on axis j used only when f_j > 0.  A corner is OBSERVED when the source holds its brick and its weight is > 0.
+ *   One used corner unobserved: the voxel is unobserved -- tsdf 0, weight 0, colour 0 -- and takes part in nothing.  Otherwise
+ *     tsdf:   lerp(a, b, f) = a + f * (b - a) along x, then y, then z; on an axis with f_j == 0 no lerp is applied: the value passes verbatim, -0.0 included
+ *     weight: the minimum of the used corners' weights (exact): a resampled voxel is never trusted more than its least observed contributor
+ *     colour: per channel the same lerps on the (float) bytes, then (unsigned char)fminf(255.f, v + 0.5f)
+ *   Hence R = I with an integral t copies every voxel verbatim (every f is 0), a t of whole bricks is kf_merge_brick_store with that offset_brick wherever
+ *   the source's unobserved voxels hold tsdf 0 and colour 0, and a signed permutation matrix with an integral t re-indexes voxels exactly.
+ *   The resampled brick b then meets the held brick a under kf_merge_brick_store's rule, word for word: a brick with no resampled weight > 0 takes no slot
+ *   and changes none; a key not held claims a slot and is written as kf_write_brick_store writes it (dropped when the store is full); a key held is
+ *   merged per voxel with the held TRUE weight and its deferred-weight word becomes 0; with `color` NULL on a context with a colour plane a fresh slot's
+ *   colour is 0 and a held one's stays; a key inside the current window is shadowed (kf_refill_window).
+ *   Unlike the chunked write the whole source goes to the device at once -- the three planes, an open-addressing table over its keys (kf_brick_key_hash,
+ *   the store's probe rule), key / ib / fb per candidate --, in temporary allocations freed before the call returns: a destination brick draws on up to 27
+ *   source bricks, so chunks would need halos.
+ *   Refused with nothing touched -- KF_ERR_ARG: a NULL context; with count > 0, NULL keys, tsdf, weight or xf, an invalid transform, a key component out of
+ *   range, a key twice, a candidate brick outside the key range (count == 0 does nothing and looks at no array).  KF_ERR_STATE: no store reserved; `color`
+ *   on a context without a colour plane.  KF_ERR_ALLOC: the temporaries do not fit. */
+int64_t kf_rigid_brick_keys(uint32_t count, const int32_t* keys, const double xf[12], int32_t* out_keys, int64_t cap);
+int kf_merge_brick_store_rigid(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
+                               const double xf[12]);
 
 /* The map mesh: marching cubes over the brick store and the window together (no reference counterpart: the reference's one cube is its map).
  * kf_marching_cubes_at: kf_marching_cubes_region in a VIRTUAL window.  Emits exactly the triangles -- the same bytes in the same order, appended to the
