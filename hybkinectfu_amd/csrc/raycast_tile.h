@@ -106,8 +106,10 @@ __device__ __forceinline__ bool gradient_for_point_either(int shared, bool odd_w
 // a walk is 1-12 additions at the stock increment (4.5 voxels) and the chain costs three instructions per step (-DKF_RAY_ADVANCE_CLOSED for the A/B)
 #ifdef KF_RAY_ADVANCE_CLOSED
 #define RC_ADVANCE kf_ray_advance
-#else
+#elif defined(RC_TRIP_OFF) && (RC_TRIP_OFF & 16)
 #define RC_ADVANCE kf_ray_advance_plain
+#else
+#define RC_ADVANCE kf_ray_advance_plain2                   /* the same chain, two additions per loop round (kf_internal.h) */
 #endif
 #define RAYCAST_THREADS 512
 #ifndef RC_GRAD_BATCH
@@ -130,9 +132,28 @@ __device__ __forceinline__ bool rc_bit(const unsigned* words, unsigned i) { retu
 // sample's tsdf is fetched on demand), so a ray's range may be marched in pieces by different lanes: the first crossing of the ray
 // is the first piece's that has one.
 struct RcRay { float3 org, dir, inv_dir; };
-__device__ __forceinline__ void rc_march(const RaycastArgs& a, const RC_VOL& v, const unsigned* s_macro, const unsigned* s_super, const unsigned* s_meso, const unsigned* s_neg, bool neg_in_lds, const RcRay& ray,
-                                         const KfRecip& rS, float t_end, float& t, float& t_prev, bool& have_last, float& last_sdf,
-                                         float& t_cross, float& t_cross_prev, int& n_iter, int& n_samp, int& n_macro) {
+// The loop is compiled once per way of forming a voxel coordinate -- a wave-uniform fact -- and chosen by rc_march with one branch outside it (tested
+// inside the loop, the size's power-of-two test was two taken scalar branches per axis and trip, and again in the lazy previous-sample fetch):
+// SCALE   how `worldPos * resolution / size` (tsdfVolume.h:50-56) is formed.  RC_SCALE_DIV: the quotient (kf_div).  RC_SCALE_MUL2: the size is a power of
+//         two, so the quotient is an exact scaling -- the same bits from the product (pos * res) * (1 / size).  RC_SCALE_MUL1: the resolution is a power of two
+//         as well and res >= size: pos * (res / size), one multiplication.  Same bits again: with res = 2^a, size = 2^b, a >= b, the first product of the
+//         two-step form is pos * 2^a EXACTLY (scaling up never drops a bit, of a subnormal pos neither, and |pos| * 2^a is far from overflow), and its second
+//         product rounds the real number pos * 2^(a - b) -- which is representable, being pos scaled up by 2^(a - b) >= 1 -- hence to itself: what the one
+//         multiplication gives.  With res < size the net scaling is DOWN and a tiny pos may round: that case keeps the two products, whatever they give.
+//         RC_SCALE_ANY: decided inside the loop, as before the loop was instantiated (A/B builds only).
+// RC_SCALE_DIV and RC_SCALE_MUL2 are the arithmetic the march has always had, statement for statement.
+enum { RC_SCALE_ANY = -1, RC_SCALE_DIV = 0, RC_SCALE_MUL2 = 1, RC_SCALE_MUL1 = 2 };
+// A/B builds (tools/build_variant.sh <name> -DRC_TRIP_OFF=<bits>) take single steps back to the earlier instruction stream: 1 the one-multiplication scaling,
+// 2 the median-of-three clamps, 16 the two-step walk, 32 the instantiation itself (which the first needs).  Every combination computes the same bits.
+// (profiles/raycast_march_trip.txt: what each step measured, and the steps that were measured and taken out again.)
+#ifndef RC_TRIP_OFF
+#define RC_TRIP_OFF 0
+#endif
+__device__ __forceinline__ int rc_clamp_voxel(int g, int R) { return (RC_TRIP_OFF & 2) ? max(0, min(g, R - 1)) : kf_clamp0(g, R - 1); }
+template <int SCALE>
+__device__ __forceinline__ void rc_march_loop(const RaycastArgs& a, const RC_VOL& v, const unsigned* s_macro, const unsigned* s_super, const unsigned* s_meso, const unsigned* s_neg, bool neg_in_lds, const RcRay& ray,
+                                              const KfRecip& rS, float t_end, float& t, float& t_prev, bool& have_last, float& last_sdf,
+                                              float& t_cross, float& t_cross_prev, int& n_iter, int& n_samp, int& n_macro) {
   const float3 org = ray.org, dir = ray.dir;
   const int R = v.res;
   const float rf = (float)R;
@@ -147,15 +168,21 @@ __device__ __forceinline__ void rc_march(const RaycastArgs& a, const RC_VOL& v, 
   const float3 per_vox = kf3(v.cell * fabsf(ray.inv_dir.x), v.cell * fabsf(ray.inv_dir.y), v.cell * fabsf(ray.inv_dir.z));
   // `worldPos * resolution / size` (tsdfVolume.h:50-56): for a power-of-two size the quotient is an exact scaling -- the same bits from a product
   const float inv_size = 1.0f / v.size;
-  const bool pow2 = (__float_as_uint(v.size) & 0x007FFFFFu) == 0u;
+  const float res_by_size = rf * inv_size;                                  // RC_SCALE_MUL1: a power of two >= 1, exact
+  const bool pow2 = (__float_as_uint(v.size) & 0x007FFFFFu) == 0u;          // RC_SCALE_ANY
+  // one coordinate's voxel number, unrounded; the lazy previous-sample fetch below forms it the same way
+  auto to_voxels = [&](float p) -> float {
+    if (SCALE == RC_SCALE_MUL1) return p * res_by_size;
+    if (SCALE == RC_SCALE_MUL2) return (p * rf) * inv_size;
+    if (SCALE == RC_SCALE_DIV) return kf_div(p * rf, rS);
+    return pow2 ? (p * rf) * inv_size : kf_div(p * rf, rS);
+  };
   while (t < t_end) {
     ++n_iter;
     const float3 pos = kf_add(org, kf_scale(dir, t));
     // the sample's own voxel -- tsdfvolume::getVoxel(world) tsdfVolume.h:81-97: nearest voxel, index clamped
-    const float qx = pow2 ? (pos.x * rf) * inv_size : kf_div(pos.x * rf, rS), qy = pow2 ? (pos.y * rf) * inv_size : kf_div(pos.y * rf, rS),
-                qz = pow2 ? (pos.z * rf) * inv_size : kf_div(pos.z * rf, rS);
-    int gx = kf_f2i(qx), gy = kf_f2i(qy), gz = kf_f2i(qz);
-    gx = max(0, min(gx, R - 1)); gy = max(0, min(gy, R - 1)); gz = max(0, min(gz, R - 1));
+    const float qx = to_voxels(pos.x), qy = to_voxels(pos.y), qz = to_voxels(pos.z);
+    const int gx = rc_clamp_voxel(kf_f2i(qx), R), gy = rc_clamp_voxel(kf_f2i(qy), R), gz = rc_clamp_voxel(kf_f2i(qz), R);
     // level 1: a 32^3-voxel macro cell without any negative voxel -> none of the samples inside it can be the negative
     // side of a crossing: walk to its far side.  The cell is the VOXEL's macro cell (g >> 5), like the brick level below:
     // picking it from the position with a different rounding could disagree with the voxel index at a cell face and skip
@@ -206,9 +233,7 @@ __device__ __forceinline__ void rc_march(const RaycastArgs& a, const RC_VOL& v, 
     if (sdf < 0.0f) {
       if (!have_last) {                                                    // the previous sample's tsdf was never fetched: fetch it now
         const float3 last_pos = kf_add(org, kf_scale(dir, t_prev));        // recomputed exactly as the march computed it
-        int lx = kf_f2i(pow2 ? (last_pos.x * rf) * inv_size : kf_div(last_pos.x * rf, rS)), ly = kf_f2i(pow2 ? (last_pos.y * rf) * inv_size : kf_div(last_pos.y * rf, rS)),
-            lz = kf_f2i(pow2 ? (last_pos.z * rf) * inv_size : kf_div(last_pos.z * rf, rS));
-        lx = max(0, min(lx, R - 1)); ly = max(0, min(ly, R - 1)); lz = max(0, min(lz, R - 1));
+        const int lx = rc_clamp_voxel(kf_f2i(to_voxels(last_pos.x)), R), ly = rc_clamp_voxel(kf_f2i(to_voxels(last_pos.y)), R), lz = rc_clamp_voxel(kf_f2i(to_voxels(last_pos.z)), R);
         last_sdf = (lz >= zs0 && lz < zs1) ? RC_TSDF_AT(v, lx, ly, lz) : 0.f;
         have_last = true;
       }
@@ -217,6 +242,19 @@ __device__ __forceinline__ void rc_march(const RaycastArgs& a, const RC_VOL& v, 
     last_sdf = sdf; have_last = true; t_prev = t;
     t += a.inc;
   }
+}
+// the instantiation of a launch: every quantity is a kernel argument, so the branches are uniform and taken once per ray, outside the loop
+__device__ __forceinline__ void rc_march(const RaycastArgs& a, const RC_VOL& v, const unsigned* s_macro, const unsigned* s_super, const unsigned* s_meso, const unsigned* s_neg, bool neg_in_lds, const RcRay& ray,
+                                         const KfRecip& rS, float t_end, float& t, float& t_prev, bool& have_last, float& last_sdf,
+                                         float& t_cross, float& t_cross_prev, int& n_iter, int& n_samp, int& n_macro) {
+#define RC_MARCH_AS(SCALE) rc_march_loop<SCALE>(a, v, s_macro, s_super, s_meso, s_neg, neg_in_lds, ray, rS, t_end, t, t_prev, have_last, last_sdf, t_cross, t_cross_prev, n_iter, n_samp, n_macro)
+  if (RC_TRIP_OFF & 32) { RC_MARCH_AS(RC_SCALE_ANY); return; }
+  const bool size_pow2 = (__float_as_uint(v.size) & 0x007FFFFFu) == 0u;
+  const bool one_mul = !(RC_TRIP_OFF & 1) && size_pow2 && (v.res & (v.res - 1)) == 0 && (float)v.res >= v.size;
+  if (one_mul) RC_MARCH_AS(RC_SCALE_MUL1);
+  else if (size_pow2) RC_MARCH_AS(RC_SCALE_MUL2);
+  else RC_MARCH_AS(RC_SCALE_DIV);
+#undef RC_MARCH_AS
 }
 
 // the ray of pixel (x, y) -- raycastKernel :136-150.  One function for the march and for k_slab_rays_unpack, which rebuilds a vertex from
