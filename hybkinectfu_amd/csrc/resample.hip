@@ -8,17 +8,14 @@
 #include "store_merge.h"
 #include "brick_keys_unique.h"
 #include "rigid_keys.h"
+#include "resample_shared.h"
 #include <stdint.h>
 #include <new>
 #include <vector>
 
-// the source map on the device: the three planes in kf_read_brick_store's layout, and its table as a KfBrickStore of which store_find reads tkey, tslot, mask
-// and max_bricks (= the number of entries) only
-struct KfResampleSource { const float* tsdf; const float* weight; const unsigned char* color; };
 // one resampled voxel; c: the colour packed as the slot holds it (x | y << 8 | z << 16)
 struct KfResampled { float t, w; unsigned c; };
 
-__device__ __forceinline__ float lerp1(float a, float b, float f) { return a + f * (b - a); }
 // eight corner values (index: dx | dy << 1 | dz << 2) along x, then y, then z; an axis whose fraction is 0 passes its value on untouched.  (A corner that is
 // not used holds 0 and meets only lerps that are not applied.)
 __device__ __forceinline__ float lerp3(const float (&v)[8], float fx, float fy, float fz) {
@@ -75,9 +72,6 @@ __device__ __forceinline__ KfResampled resample_voxel(const KfResampleSource& sr
   }
   return r;
 }
-
-// min(0, 7 r): the least a column entry adds to u over the brick's l in [0, 8)
-__device__ __forceinline__ float least7(float r) { return fminf(0.f, 7.f * r); }
 
 // Resample and merge for kf_merge_brick_store_rigid.  One workgroup iteration per candidate destination brick, 256 lanes x 2 x-adjacent voxels (the slot's
 // float4).  ckeys / cib / cfb: per candidate its key, and the source position of its voxel (0, 0, 0) as an integer and a fraction (rigid_keys.h).  r<i><j>:
@@ -154,18 +148,6 @@ __global__ void __launch_bounds__(256) k_store_resample_merge(KfBrickStore st, K
 extern "C" int64_t kf_rigid_brick_keys(uint32_t count, const int32_t* keys, const double xf[12], int32_t* out_keys, int64_t cap) {
   try { return kf_rigid_keys(count, keys, xf, out_keys, cap); } catch (const std::bad_alloc&) { return -1; }   // (no exception crosses the C boundary)
 }
-
-// the temporary device allocations of one call, freed on every way out
-struct KfResampleTemp {
-  void* p[8] = {};
-  int n = 0;
-  bool get(void** out, size_t bytes) {
-    if (hipMalloc(out, bytes ? bytes : 1) != hipSuccess) { (void)hipGetLastError(); *out = nullptr; return false; }
-    p[n++] = *out;
-    return true;
-  }
-  ~KfResampleTemp() { for (int i = 0; i < n; ++i) hipFree(p[i]); }
-};
 
 extern "C" int kf_merge_brick_store_rigid(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
                                           const double xf[12]) {

@@ -177,6 +177,17 @@ int hkf_app_merge_map_rigid(const char* path, const float m[16]) {
   memcpy(t.entries, m, 64);
   return g_app->mergeMap(path, t) ? 1 : 0;
 }
+// HybKinectfu::alignMap: guess and found row-major 4x4 in metres, report a kf_align_report (may be NULL).  1 converged, 0 refused, failed or not converged
+// (found and report are then written only when the alignment ran), -1 without an application
+int hkf_app_align_map(const char* path, const float guess[16], float found[16], void* report) {
+  if (!g_app) return -1;
+  if (!path || !guess || !found) return 0;
+  Mat44 g, f;
+  memcpy(g.entries, guess, 64); memcpy(f.entries, guess, 64);
+  const bool ok = g_app->alignMap(path, g, f, (kf_align_report*)report);
+  memcpy(found, f.entries, 64);
+  return ok ? 1 : 0;
+}
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
 int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {
   HkfMapHeader h;

@@ -597,29 +597,9 @@ bool HybKinectfu::mergeMap(const std::string& path, const int offsetBricks[3]) {
   if (!mergeShow()) return false;
   return st == HKF_MAP_OK;
 }
-bool HybKinectfu::mergeMap(const std::string& path, const Mat44& srcToDst) {
-  if (!_inited) return false;
-  AppParams* p = AppParams::instance();
-  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
-  kf_ctx* ctx = dm->ctx();
-  lastTracked();
-  // 1. the file checked, the volume this instance's; the transform in voxels: the cell is the fp32 quotient the volume uses
-  HkfMapHeader h;
-  const int is = hkf_map_info(path.c_str(), &h);
-  if (!merge_file_is_ours(path, is, h)) return false;
-  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
-  double xf[12];
-  for (int i = 0; i < 3; ++i) {
-    for (int j = 0; j < 3; ++j) xf[4 * i + j] = (double)srcToDst.entries[4 * i + j];
-    xf[4 * i + 3] = (double)srcToDst.entries[4 * i + 3] / (double)cell;
-  }
-  const bool color = h.has_color != 0;
-  if (h.n_bricks > 0xFFFFFFFFull) return false;
-  // 2. the whole file in host memory (a destination brick draws on up to 27 of its bricks: no chunks), and its candidate bricks: still nothing touched
-  std::vector<int32_t> keys;
-  std::vector<float> t, w;
-  std::vector<uint8_t> col;
-  int64_t candidates = -1;
+// the whole file in host memory (a destination brick draws on up to 27 of its bricks: no chunks); `color`: the colour bytes too.  Touches no device state.
+static bool read_whole_map(const char* who, const std::string& path, const HkfMapHeader& h, bool color, std::vector<int32_t>& keys, std::vector<float>& t,
+                           std::vector<float>& w, std::vector<uint8_t>& col) {
   try {
     keys.reserve((size_t)h.n_bricks * 3); t.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX); w.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX);
     if (color) col.reserve((size_t)h.n_bricks * HKF_MAP_BRICK_VOX * 3);
@@ -631,10 +611,41 @@ bool HybKinectfu::mergeMap(const std::string& path, const Mat44& srcToDst) {
       return true;
     });
     if (st != HKF_MAP_OK || keys.size() != (size_t)h.n_bricks * 3 || (color && col.size() != t.size() * 3)) {
-      fprintf(stderr, "mergeMap: reading %s failed (%d); nothing merged\n", path.c_str(), st);
+      fprintf(stderr, "%s: reading %s failed (%d); nothing touched\n", who, path.c_str(), st);
       return false;
     }
   } catch (const std::bad_alloc&) { return false; }
+  return true;
+}
+// a matrix in metres, as poses are, as the C ABI's [R | t] in voxels: the cell is the fp32 quotient the volume uses
+static void rigid_in_voxels(const Mat44& m, double xf[12]) {
+  const AppParams* p = AppParams::instance();
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) xf[4 * i + j] = (double)m.entries[4 * i + j];
+    xf[4 * i + 3] = (double)m.entries[4 * i + 3] / (double)cell;
+  }
+}
+bool HybKinectfu::mergeMap(const std::string& path, const Mat44& srcToDst) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  lastTracked();
+  // 1. the file checked, the volume this instance's; the transform in voxels: the cell is the fp32 quotient the volume uses
+  HkfMapHeader h;
+  const int is = hkf_map_info(path.c_str(), &h);
+  if (!merge_file_is_ours(path, is, h)) return false;
+  double xf[12];
+  rigid_in_voxels(srcToDst, xf);
+  const bool color = h.has_color != 0;
+  if (h.n_bricks > 0xFFFFFFFFull) return false;
+  // 2. the whole file in host memory, and its candidate bricks: still nothing touched
+  std::vector<int32_t> keys;
+  std::vector<float> t, w;
+  std::vector<uint8_t> col;
+  int64_t candidates = -1;
+  if (!read_whole_map("mergeMap", path, h, color, keys, t, w, col)) return false;
   candidates = kf_rigid_brick_keys((uint32_t)h.n_bricks, keys.data(), xf, nullptr, 0);
   if (candidates < 0) {
     fprintf(stderr, "mergeMap: %s refused: the matrix is no rigid transform, or it moves a brick out of the key range\n", path.c_str());
@@ -645,6 +656,46 @@ bool HybKinectfu::mergeMap(const std::string& path, const Mat44& srcToDst) {
   const int ms = dm->check(kf_merge_brick_store_rigid(ctx, (uint32_t)h.n_bricks, keys.data(), t.data(), w.data(), color ? col.data() : nullptr, xf));
   if (!mergeShow()) return false;
   return ms == 0;
+}
+bool HybKinectfu::alignMap(const std::string& path, const Mat44& guess, Mat44& found, kf_align_report* report) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  lastTracked();
+  // 1. mergeMap's checks: the file, the volume this instance's, the guess a rigid transform that keeps every brick in the key range; nothing touched before
+  HkfMapHeader h;
+  const int is = hkf_map_info(path.c_str(), &h);
+  if (!merge_file_is_ours(path, is, h)) return false;
+  double xf[12];
+  rigid_in_voxels(guess, xf);
+  if (h.n_bricks > 0xFFFFFFFFull) return false;
+  std::vector<int32_t> keys;
+  std::vector<float> t, w;
+  std::vector<uint8_t> col;
+  if (!read_whole_map("alignMap", path, h, false, keys, t, w, col)) return false;
+  if (kf_rigid_brick_keys((uint32_t)h.n_bricks, keys.data(), xf, nullptr, 0) < 0) {
+    fprintf(stderr, "alignMap: %s refused: the guess is no rigid transform, or it moves a brick out of the key range\n", path.c_str());
+    return false;
+  }
+  // 2. the window captured: the store alone is this session's map (a store that was never reserved is reserved, as mergeMap does); no room is made
+  if (!mergeMakeRoom(p->_switch_params.useRGBData, 0)) return false;
+  // 3. rotations about the middle of the map; 4. one call.  eps 0: the steps go down to what the rule resolves
+  int32_t lo[3], hi[3];
+  if (dm->check(kf_brick_store_bounds(ctx, lo, hi))) return false;
+  kf_align_params ap = {30u, 1000u, 0.0, 0.0, {4.0 * ((double)lo[0] + hi[0]), 4.0 * ((double)lo[1] + hi[1]), 4.0 * ((double)lo[2] + hi[2])}};
+  kf_align_report rep;
+  if (dm->check(kf_align_brick_store(ctx, (uint32_t)h.n_bricks, keys.data(), t.data(), w.data(), xf, &ap, &rep))) return false;
+  if (report) *report = rep;
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  found = Mat44();
+  for (int i = 0; i < 16; ++i) found.entries[i] = (i % 5 == 0) ? 1.f : 0.f;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) found.entries[4 * i + j] = (float)xf[4 * i + j];
+    found.entries[4 * i + 3] = (float)(xf[4 * i + 3] * (double)cell);
+  }
+  if (rep.verdict != KF_ALIGN_CONVERGED) fprintf(stderr, "alignMap: %s: no convergence (verdict %u after %u steps, %.0f pairs)\n", path.c_str(), rep.verdict, rep.iterations, rep.sums[28]);
+  return rep.verdict == KF_ALIGN_CONVERGED;
 }
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();

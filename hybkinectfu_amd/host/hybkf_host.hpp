@@ -299,7 +299,7 @@ public:
   bool loadMap(const std::string& path);
   // mergeMap: fuses the map file into this session's map, voxel by voxel (kf_merge_brick_store: the weighted running average, exact in fp32, so merging
   // A into B and B into A give the same bricks).  offsetBricks (nullptr: zero) translates the file's keys by whole bricks into this session's world
-  // frame; finding that offset, and offsets that are no whole bricks, are the caller's business.  The file is checked as loadMap checks it, and every
+  // frame; offsets that are no whole bricks go through the other mergeMap, and alignMap finds its transform.  The file is checked as loadMap checks it, and every
   // translated key must lie in the key range: refused (false) with nothing touched otherwise.  Then: the window is captured into the store (false when a
   // brick did not fit), the store is grown to held + the file's bricks where its capacity is below that (read out, reserved, written back: its dropped and
   // restored counts start again), the file's bricks are merged, the window is re-read from the store (kf_refill_window) and the model maps are raycast
@@ -314,6 +314,14 @@ public:
   // also for a matrix that is no rigid transform (kf_rigid_brick_keys' rule) or that moves a brick out of the key range.  A file of another cell size is
   // refused like any other volume that is not this instance's.
   bool mergeMap(const std::string& path, const Mat44& srcToDst);
+  // alignMap: finds the srcToDst that mergeMap(path, srcToDst) needs, refined from `guess` (both in metres, as poses are) by Gauss-Newton on the SDF-to-SDF
+  // error between this session's map and the file's (kf_align_brick_store).  A refinement, not a search: the guess must lie within about the truncation
+  // band of the answer (some 10 degrees and a few voxels on a box-like scene).  mergeMap's file and parameter checks, refused (false) with nothing touched;
+  // then the window is captured into the store (a store that was never reserved is reserved; false when a brick did not fit), rotations are taken about
+  // the middle of kf_brick_store_bounds' box, and one call runs at most 30 steps with at least 1000 pairs, down to the rule's resolution.  It merges
+  // nothing: window, pose, model maps and frame id stay.  `found`: the transform of the last successful evaluation, in metres (the rotation rounded to
+  // fp32); true only when the verdict is KF_ALIGN_CONVERGED.  report (may be nullptr): the call's report.
+  bool alignMap(const std::string& path, const Mat44& guess, Mat44& found, kf_align_report* report);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();

@@ -61,6 +61,7 @@ public:
   bool loadMap(const std::string&) { return false; }
   bool mergeMap(const std::string&, const int*) { return false; }
   bool mergeMap(const std::string&, const Mat44&) { return false; }
+  bool alignMap(const std::string&, const Mat44&, Mat44&, kf_align_report*) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

@@ -215,6 +215,16 @@ class App:
             raise K.KfError("hkf_app_merge_map_rigid: no application")
         return bool(r)
 
+    def align_map(self, path, guess):
+        """HybKinectfu::alignMap: the 4x4 (metres, as poses are) that lays the file's map onto this session's, refined from `guess`; a refinement, not a
+        search.  Captures the window, merges nothing.  Returns (converged, the matrix found, the lib.AlignReport): pass the matrix to merge_map_rigid"""
+        g = np.ascontiguousarray(guess, np.float32).reshape(16)
+        found, rep = np.zeros(16, np.float32), K.AlignReport()
+        r = self.h.hkf_app_align_map(os.fsencode(path), g.ctypes.data_as(C.c_void_p), found.ctypes.data_as(C.c_void_p), C.byref(rep))
+        if r < 0:
+            raise K.KfError("hkf_app_align_map: no application")
+        return bool(r), found.reshape(4, 4), rep
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -347,6 +357,13 @@ class SlabsApp:
         """always False, nothing touched, as merge_map"""
         m = np.ascontiguousarray(mat, np.float32).reshape(16)
         return self.h.hkf_slabs_merge_map_rigid(os.fsencode(path), m.ctypes.data_as(C.c_void_p)) > 0
+
+    def align_map(self, path, guess):
+        """always (False, the guess, None), nothing touched, as merge_map"""
+        g = np.ascontiguousarray(guess, np.float32).reshape(16)
+        found = g.copy()
+        self.h.hkf_slabs_align_map(os.fsencode(path), g.ctypes.data_as(C.c_void_p), found.ctypes.data_as(C.c_void_p), None)
+        return False, found.reshape(4, 4), None
 
     def close(self):
         self.h.hkf_slabs_shutdown()

@@ -123,6 +123,7 @@ SYMBOLS = [
     "kf_brick_store_reserve", "kf_brick_store_count", "kf_brick_store_clear", "kf_read_brick_store", "kf_brick_store_bounds",
     "kf_write_brick_store", "kf_brick_store_capture", "kf_place_window",
     "kf_merge_brick_store", "kf_refill_window", "kf_merge_brick_store_rigid", "kf_rigid_brick_keys",
+    "kf_align_brick_store", "kf_align_step",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -175,6 +176,9 @@ def load():
         _lib.kf_merge_brick_store_rigid.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double)]
         _lib.kf_rigid_brick_keys.argtypes = [C.c_uint32, C.c_void_p, C.POINTER(C.c_double), C.c_void_p, C.c_int64]
         _lib.kf_rigid_brick_keys.restype = C.c_int64
+        _lib.kf_align_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(AlignParams),
+                                              C.POINTER(AlignReport)]
+        _lib.kf_align_step.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -223,6 +227,32 @@ def rigid_brick_keys(keys, xf):
     if n:
         lib.kf_rigid_brick_keys(len(keys), _p(keys), x, _p(out), n)
     return out
+
+
+ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_FEW_PAIRS, ALIGN_SINGULAR = 0, 1, 2, 3   # kf_align_report.verdict
+
+
+class AlignParams(C.Structure):
+    _fields_ = [("max_iter", C.c_uint32), ("min_pairs", C.c_uint32), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("centre", C.c_double * 3)]
+
+
+class AlignReport(C.Structure):
+    _fields_ = [("iterations", C.c_uint32), ("verdict", C.c_uint32), ("sums", C.c_double * 29), ("rms", C.c_double), ("step", C.c_double * 6)]
+
+
+def align_params(centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
+    return AlignParams(int(max_iter), int(min_pairs), float(eps_rot), float(eps_trans), (C.c_double * 3)(*[float(x) for x in centre]))
+
+
+def align_step(sums, centre, xf):
+    """one Gauss-Newton step from the 29 sums: (the updated 3x4 transform, the step (omega, v)), or None when the solve refuses (kf_align_step)"""
+    lib = load()
+    s = (C.c_double * 29)(*np.asarray(sums, np.float64).reshape(29).tolist())
+    c = (C.c_double * 3)(*np.asarray(centre, np.float64).reshape(3).tolist())
+    x, step = rigid_xf(xf), (C.c_double * 6)()
+    if lib.kf_align_step(s, c, x, step) != 0:
+        return None
+    return np.array(x[:], np.float64).reshape(3, 4), np.array(step[:], np.float64)
 
 
 def _chk(st, what):
@@ -810,6 +840,19 @@ class Context:
         c = np.ascontiguousarray(color, np.uint8) if color is not None else None
         assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
         _chk(self.lib.kf_merge_brick_store_rigid(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None, rigid_xf(xf)), "kf_merge_brick_store_rigid")
+
+    def align_brick_store(self, keys, tsdf, weight, xf, centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
+        """the rigid transform that lays the map (keys, tsdf, weight) onto this store, refined from the guess xf = [R | t] (3x4, source world -> this
+        store's world, t in voxels) by Gauss-Newton on the SDF-to-SDF error; rotations are taken about `centre` (voxels).  Returns (the transform found,
+        the AlignReport); max_iter = 0 only evaluates the sums at xf.  Nothing is merged and nothing changes (kf_align_brick_store)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        n = len(keys)
+        t, w = np.ascontiguousarray(tsdf, np.float32), np.ascontiguousarray(weight, np.float32)
+        assert t.size == n * 512 and w.size == n * 512
+        x, rep = rigid_xf(xf), AlignReport()
+        _chk(self.lib.kf_align_brick_store(self.h, n, _p(keys), _p(t), _p(w), x, C.byref(align_params(centre, max_iter, min_pairs, eps_rot, eps_trans)),
+                                           C.byref(rep)), "kf_align_brick_store")
+        return np.array(x[:], np.float64).reshape(3, 4), rep
 
     def refill_window(self):
         """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never

@@ -659,6 +659,64 @@ int64_t kf_rigid_brick_keys(uint32_t count, const int32_t* keys, const double xf
 int kf_merge_brick_store_rigid(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
                                const double xf[12]);
 
+/* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
+ * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
+ * voxels a start 10 degrees and about 5 voxels off still converges; a start much further off finds too few pairs or a wrong minimum.  Coarse-to-fine search
+ * and global relocalisation are not offered.
+ * The destination is the brick store as held (read only): a key inside the current window is shadowed by the window's copy, so call
+ * kf_brick_store_capture first.  The source is an incoming map in kf_read_brick_store's layout (count entries: keys, tsdf, weight).  xf is the rigid
+ * merge's [R | t]: row-major 3x4, source world -> destination world, t in voxels, VALID as defined above.  Colour plays no part.
+ * One evaluation: for every held slot with key K and every voxel l in [0, 8)^3 of it --
+ *   Held side: with the STORED pair (td, wd) the voxel takes part only when wd > 0 and fabsf(td) < 1.f.  The slot's deferred-weight word is not looked
+ *     at: a quarter of a brick whose weights are still deferred holds tsdf 1.0 throughout, which the band excludes.
+ *   Source position, the rigid merge's arithmetic: ib, fb per brick by its fp64 formula (a = 8 K + 0.5 - t; c_j = ((R[0][j] a_0 + R[1][j] a_1) +
+ *     R[2][j] a_2) - 0.5; ib = floor(c); fb = (float)(c - ib), an fb of 1.0f becoming ib + 1, 0.f; a brick whose ib does not fit 31 bits takes no part);
+ *     in fp32, Rf = (float)R, one rounded operation per operation written here:
+ *     u_j = ((Rf[0][j] lx + Rf[1][j] ly) + Rf[2][j] lz) + fb_j;  n_j = floorf(u_j);  f_j = u_j - n_j;  base corner i_j = ib_j + (int)n_j.
+ *   Corners: all eight i + {0, 1}^3 are read, whatever f is.  Each must be held by the source with weight > 0 and fabsf(tsdf) < 1.f, otherwise the voxel
+ *     takes no part: a corner at the truncation value has no gradient to give.  v[dx | dy << 1 | dz << 2] their tsdf values.
+ *   Value, lerp(a, b, f) = a + f * (b - a) always applied:  a_k = lerp(v[2k], v[2k+1], f_x), k = 0..3;  b_0 = lerp(a_0, a_1, f_y), b_1 = lerp(a_2, a_3, f_y);
+ *     phi = lerp(b_0, b_1, f_z).
+ *   Gradient in source voxels, from the same eight values:  dx_k = v[2k+1] - v[2k];  gx = lerp(lerp(dx_0, dx_1, f_y), lerp(dx_2, dx_3, f_y), f_z);
+ *     gy = lerp(a_1 - a_0, a_3 - a_2, f_z);  gz = b_1 - b_0.
+ *   Row:  gd_i = (Rf[i][0] gx + Rf[i][1] gy) + Rf[i][2] gz;  x_j = (float)(8 K_j + 0.5 - centre_j) + l_j, the bracket in fp64;
+ *     J = (x_1 gd_2 - x_2 gd_1, x_2 gd_0 - x_0 gd_2, x_0 gd_1 - x_1 gd_0, gd_0, gd_1, gd_2), every product and difference rounded once;  e = phi - td.
+ *   Sums, 29 doubles:  [0, 21) the upper triangle of sum J_a J_b row by row ((0,0), (0,1) .. (0,5), (1,1) .. (5,5));  [21, 27) sum J_a e;  [27] sum e e;
+ *     [28] the number of voxels that took part, counted in integers.  Every product is formed in fp64 from its fp32 factors, hence exact, and added in fp64
+ *     in an order that depends on the keys held alone (the slots are visited by ascending packed key, whichever slot a brick claimed): no atomic on a
+ *     float, so the same map in the store and the same source give the same 29 doubles bit for bit on every run and in every context.
+ * kf_align_step (no context, host only): one step from the sums.  Solves (sum J J^T) xi = sum J e by Cholesky, xi = (omega, v): omega a rotation vector
+ *   in radians about `centre`, v in voxels.  Updates xf <- T(centre) exp(xi) T(-centre) xf: with E = exp(omega^) and V = I + (1 - cos th) / th^2 omega^ +
+ *   (th - sin th) / th^3 omega^2, th = |omega|,  R <- E R and t <- E (t - centre) + centre + V v.  All in fp64.  Returns 0 and writes xf and step[6] = xi;
+ *   non-zero with both untouched for a NULL pointer, a pivot <= 0 (the sums do not determine all six unknowns) or a result that is not finite.
+ * kf_align_brick_store: uploads the source once (the two planes and an open-addressing table over its keys, in temporary allocations freed before the
+ *   call returns), then repeats: evaluate the sums at xf; stop with KF_ALIGN_FEW_PAIRS when fewer than max(min_pairs, 1) voxels took part; stop with
+ *   KF_ALIGN_ITER_LIMIT when max_iter steps are done; take a kf_align_step, stopping with KF_ALIGN_SINGULAR when it refuses; stop with KF_ALIGN_CONVERGED
+ *   when the step has |omega| <= eps_rot and |v| <= eps_trans (the stepped transform is the result; it is not evaluated again).  An eps_rot below
+ *   KF_ALIGN_EPS_ROT_MIN (2^-23 rad: one unit in the last place of an entry of Rf) or an eps_trans below KF_ALIGN_EPS_TRANS_MIN (2^-18 voxels: the
+ *   granularity of a position u, a few units in the last place of a value in [8, 16)) is raised to it.  The rule evaluates Rf and fb, not R and t: below
+ *   that resolution the sums change by rounding alone, and the steps of an fp64 Gauss-Newton loop, which would fall to 1e-13, here stay at some 1e-9 rad
+ *   and 1e-8 voxels for ever (measured on the analytic box of the tests), four to five orders below the error of the result itself.  xf is in / out: the guess
+ *   goes in, the result comes out.  On FEW_PAIRS and SINGULAR xf is the last transform that was evaluated with enough pairs (the guess, if none).
+ *   max_iter == 0 evaluates the sums at xf, reports them (KF_ALIGN_ITER_LIMIT) and leaves xf alone.  centre, in voxels (voxel g has its centre at g + 1/2), is
+ *   the point rotations are taken about: the middle of the map keeps sum J J^T well conditioned.  The report: the steps taken, the verdict, the LAST
+ *   evaluation's sums and rms = sqrt(sums[27] / sums[28]) (0 without a pair), the last step taken (zeros if none).  Blocks.
+ *   The call changes nothing: the store (slots, table, counts, deferred-weight words), the window, the pose, the model maps and the triangle buffer stay
+ *   bit for bit.  Refused with nothing touched, xf and the report included -- KF_ERR_ARG: a NULL context, xf, params or report; with count > 0, NULL keys,
+ *   tsdf or weight; an invalid transform; a key component out of range, a key twice; an eps that is negative or not finite, a centre that is not finite; a
+ *   z-slab context.  KF_ERR_STATE: no store reserved.  KF_ERR_ALLOC: the temporaries do not fit. */
+#define KF_ALIGN_EPS_ROT_MIN 1.1920928955078125e-07     /* 2^-23 rad */
+#define KF_ALIGN_EPS_TRANS_MIN 3.814697265625e-06       /* 2^-18 voxels */
+#define KF_ALIGN_CONVERGED 0
+#define KF_ALIGN_ITER_LIMIT 1
+#define KF_ALIGN_FEW_PAIRS 2
+#define KF_ALIGN_SINGULAR 3
+typedef struct kf_align_params { uint32_t max_iter, min_pairs; double eps_rot, eps_trans; double centre[3]; } kf_align_params;
+typedef struct kf_align_report { uint32_t iterations, verdict; double sums[29]; double rms; double step[6]; } kf_align_report;
+int kf_align_step(const double sums[29], const double centre[3], double xf[12], double step[6]);
+int kf_align_brick_store(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, double xf[12],
+                         const kf_align_params* params, kf_align_report* report);
+
 /* The map mesh: marching cubes over the brick store and the window together (no reference counterpart: the reference's one cube is its map).
  * kf_marching_cubes_at: kf_marching_cubes_region in a VIRTUAL window.  Emits exactly the triangles -- the same bytes in the same order, appended to the
  *   triangle buffer and clamped the same way -- that kf_marching_cubes_region(ctx, has_color, threshold, lo, hi, flags) would emit after
