@@ -563,34 +563,8 @@ __device__ __forceinline__ bool icp_finish(const TrackArgs& a, float4 vg, float4
   return true;
 }
 
-// 512 lanes x up to ICP_PX (3) pixels per workgroup: 200 workgroups at VGA level 0 (few partials to fold, no register spills).
-#define ICP_THREADS 512
-#ifndef ICP_PX
-#define ICP_PX 3
-#endif
-// Pixels per lane (px_l) and publishing workgroups (grid_l) of a pyramid level with npx pixels, under a launch geometry of loop_grid
-// workgroups (= the workgroups level 0 needs at ICP_PX pixels per lane).  Two things pull: fewer pixels per lane shorten the pixel
-// phase (a coarse step is mostly latency), but every workgroup that holds pixels is one more publisher the step has to wait for (all
-// 256 CUs publishing at every level: +36 us per frame).  Measured at VGA on 200 workgroups, tracking stage in us for (level 0, 1, 2)
-// pixels per lane, with the fold's two polls in flight: (3,3,1) 162.4, (3,2,2) 161.9, (3,2,1) 159.4, (3,1,1) 156.3 (with one poll in
-// flight (3,2,1) was ahead: 172.6 vs 175.5).  Rule: the fewest pixels per lane the launch can hold.  Host and device, both launch forms.
-__host__ __device__ static inline void icp_level_geometry(int npx, int loop_grid, int level, int& px_l, int& grid_l) {
-  px_l = ICP_PX;
-#ifndef KF_ICP_FIXED_PX
-  for (int p = 1; p < ICP_PX; ++p) if ((npx + ICP_THREADS * p - 1) / (ICP_THREADS * p) <= loop_grid) { px_l = p; break; }
-#ifdef KF_ICP_PX_L0                                                              // tuning overrides (tools/build_variant.sh)
-  if (level == 0) px_l = KF_ICP_PX_L0;
-#endif
-#ifdef KF_ICP_PX_L1
-  if (level == 1) px_l = KF_ICP_PX_L1;
-#endif
-#ifdef KF_ICP_PX_L2
-  if (level == 2) px_l = KF_ICP_PX_L2;
-#endif
-#endif
-  (void)level;
-  grid_l = (npx + ICP_THREADS * px_l - 1) / (ICP_THREADS * px_l);
-}
+// ICP_THREADS, ICP_PX, icp_level_geometry (pixels per lane and publishers of a level) and the fold's slot rule: shared with the host's test program
+#include "icp_fold_slots.h"
 // index of this lane's j-th pixel: pixels are dealt to the grid_l workgroups in 64-pixel chunks, round robin -- every workgroup sees
 // the same mix of surface and background, so they all reach the exchange of partial sums at about the same time (contiguous blocks
 // did not)
@@ -714,88 +688,140 @@ struct IcpLoopArgs : TrackLoopArgs {
 // legitimate wait is tens of microseconds; the clock is read every 64th poll (~1-1.5 us each).  Giving up costs latency, not the frame: one
 // workgroup then finishes the frame's Gauss-Newton loop alone (track_loop_end below), with the same bits.
 #define ICP_WAIT_LIMIT 2000000ull
-#define ICP_FOLD_BATCH 13
 #ifndef KF_ICP_POLL_PIPE
-#define KF_ICP_POLL_PIPE 2        // s_sleep between the two polls kept in flight (0 is not a value: -DKF_ICP_POLL_SINGLE selects the one-poll loop)
+#define KF_ICP_POLL_PIPE 2        // s_sleep between two polls (anything from 0 to 8 measures alike; -DKF_ICP_POLL_SINGLE selects the older one-poll loop)
+#endif
+#ifndef KF_ICP_POLL_DEPTH
+#define KF_ICP_POLL_DEPTH 1       // polls (sets of a batch's words) a lane keeps in flight
+#endif
+#ifndef KF_ICP_POLL_DEPTH_SMALL
+#define KF_ICP_POLL_DEPTH_SMALL KF_ICP_POLL_DEPTH      // the same where a set is at most 4 words (tuning: profiles/icp_fold_shapes.txt)
+#endif
+#ifdef KF_ICP_POLL_SINGLE
+#undef ICP_FOLD_LADDER
+#define ICP_FOLD_LADDER(X)        // the one-poll loop (and the experiments that live in it) always polls ICP_FOLD_BATCH slots
 #endif
 // Partial sums of the persistent loop travel as 64-bit (value, tag) words: the tag is the launch's sequence number plus the
 // Gauss-Newton step, every step has its own slot array, and a word is published by ONE 8-byte write-through store -- so a
 // reader needs no barrier and no flag: it polls the words it is about to add until their tags are current.  The adds run
 // in a fixed order (workgroup-major within a part, then the parts): every workgroup of the loop arrives at the same bits.  The
 // per-step launch form (k_icp_step) deals pixels to workgroups differently, so the two forms agree to tolerance, not bitwise.
+//
+// One batch of one lane: the words of the publishers w0, w0 + parts, ... (NS of them, icp_fold_batch_slots) of sum k are polled until all their tags are
+// current, then added to s in ascending order.  What a poll costs is what it loads: every workgroup of the loop reads every publisher's 27 words, 43 KB per
+// poll and CU at VGA level 0 and 8.6 MB over the chip, through the same fabric the publishers' stores have to cross.  Hence (profiles/icp_fold_shapes.txt,
+// tracking stage at C2 in us):
+//  * a batch polls no more slots than its level has publishers for -- the slots left out were + 0.f on a sum that starts at +0.f and cannot become -0.f,
+//    the same bits (13 slots in every batch 120.1, {3, 10, 13} 114.9, {2, 4, 7, 10, 13} 116.4);
+//  * ONE poll in flight, and none once the set is current.  A second one does not find a publication sooner, it delays it: 114.9 with one, 142.3 with
+//    two really in flight (level 0: everyone folded 4.3 instead of 2.8 us after the first publish), 116.7 with two for the sets of 3 words alone;
+//    a sweep that is still on its way when the fold is through costs 6 more.
+//    (The loop this one replaces asked for two and, behind a per-lane exit, got one and a half: the compiler waited for the younger set before it
+//    re-issued the older one, and moved both between registers every turn -- 128.9.)
+template <int NS>
+__device__ __forceinline__ float fold_batch_tagged(const unsigned long long* slots, int n_wg, int w0, int parts, int k, unsigned tag, float s, int* s_abort,
+                                                   int exp_mode, const unsigned* rescue_tag, unsigned tag_base, unsigned long long& t_wait0) {
+  unsigned spins = 0;
+#ifndef KF_ICP_POLL_SINGLE
+  // D sets of the batch's words in flight (D = 1 unless a tuning build asks for more): the oldest is looked at while the younger ones are on their way; the
+  // sets take turns in place -- the loop is unrolled by the depth, and no set is ever copied into another's registers.
+  constexpr int D = NS <= 4 ? KF_ICP_POLL_DEPTH_SMALL : KF_ICP_POLL_DEPTH;
+  // the batch's addresses are fixed before the loop and a lane without a publisher for slot j polls its own FIRST word once more
+  // (not one shared word: the slots of a ragged last row would all hammer one publisher's line; the value is dropped below): no branch around a load, no
+  // exec-mask juggling per slot -- the poll iteration was 265 instructions, i.e. the loop noticed a publication up to 0.4 us late
+  unsigned long long u[D][NS];
+  const unsigned long long* src[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) { const int w = w0 + j * parts; src[j] = slots + (size_t)((w < n_wg ? w : w0) * 32 + k); }
+#pragma unroll
+  for (int d = 0; d < D; ++d) {
+    if (d) __builtin_amdgcn_s_sleep(KF_ICP_POLL_PIPE);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) u[d][j] = __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  // The wave leaves as one, when a set is current in all its lanes: a word that is current stays so (a slot is written once per launch and step), and a
+  // lane that is through would wait for its neighbours anyway.  The loop has ONE exit, at its foot, and the set that is found current is copied out where
+  // it is found.  With more than one set in flight nothing in the loop issues a poll under a condition either, and the turn is played to its end (its
+  // last polls land in registers nobody reads): behind a per-lane exit, an exit per set or a poll under a condition the compiler cannot tell how many
+  // loads are in flight where a set is looked at -- it waits for all of them and moves whole sets between registers.
+  float v[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) v[j] = 0.f;
+  bool done = false;                                                            // the same in every lane of the wave
+  do {
+    // never spin forever: looked at once per turn of the sets, i.e. every 64 polls as before
+    if (++spins == 64u / D) {
+      spins = 0u;
+      // (somebody else of this launch already gave up and one workgroup is finishing the frame alone: nothing more will be published)
+      bool give_up = rescue_tag && (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(rescue_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == tag_base;
+      if (!give_up) {
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long t0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(t_wait0 >> 32)) << 32) |
+                                      (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t_wait0);
+        if (t0 == 0ull) t_wait0 = now; else give_up = now - t0 > ICP_WAIT_LIMIT;
+      }
+      if (give_up) { *s_abort = 1; done = true; }                               // (the fold is void: its caller looks at s_abort first)
+    }
+#pragma unroll
+    for (int d = 0; d < D; ++d) {                                               // set d is the oldest in flight
+      unsigned stale = 0u;
+#pragma unroll
+      for (int j = 0; j < NS; ++j) stale |= (unsigned)(u[d][j] >> 32) ^ tag;
+      if (!done && __ballot(stale != 0u) == 0ull) {                             // current: its values are the ones added
+#pragma unroll
+        for (int j = 0; j < NS; ++j) v[j] = __uint_as_float((unsigned)u[d][j]);
+        done = true;
+      }
+      if (D > 1 || !done) {
+        if (!done) __builtin_amdgcn_s_sleep(KF_ICP_POLL_PIPE);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) u[d][j] = __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
+    }
+  } while (!done);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) s += (w0 + j * parts < n_wg) ? v[j] : 0.f;
+  return s;
+#else
+  float v[NS];
+  for (;;) {
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int w = w0 + j * parts;
+      v[j] = 0.f;
+      if (w < n_wg && !(exp_mode == 3 && w >= 16 && k != 0)) {     // (experiment 3: wait for every workgroup, move 1/27 of the words)
+        const unsigned long long u = __hip_atomic_load(&slots[w * 32 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v[j] = __uint_as_float((unsigned)u);
+        ok = ok && (unsigned)(u >> 32) == tag;
+      }
+    }
+    if (ok) break;
+    __builtin_amdgcn_s_sleep(2);
+    if ((++spins & 63u) == 0u) {                                             // never spin forever
+      const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+      if (t_wait0 == 0ull) t_wait0 = now; else if (now - t_wait0 > ICP_WAIT_LIMIT) { *s_abort = 1; break; }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < NS; ++j) s += v[j];
+  return s;
+#endif
+}
 __device__ __forceinline__ void fold_partials_tagged(const unsigned long long* slots, int n_wg, unsigned tag, float* s_tot, int* s_abort, int exp_mode = 0,
                                                      const unsigned* rescue_tag = nullptr, unsigned tag_base = 0u) {
   const int k = threadIdx.x & 31, part = threadIdx.x >> 5, parts = blockDim.x >> 5;
   float s = 0.f;
   unsigned long long t_wait0 = 0ull;
   if (k < 27) {
-    for (int w0 = part; w0 < n_wg; w0 += ICP_FOLD_BATCH * parts) {
-      float v[ICP_FOLD_BATCH];
-      unsigned spins = 0;
-#ifndef KF_ICP_POLL_SINGLE
-      // several polls in flight: a poll costs a full memory round trip, and words that become current just after a poll has been issued
-      // are otherwise only seen one round trip + one sleep later; the oldest set is checked while the younger one is on its way
-      // (tracking stage 172.5 -> 157.5 us; three or four sets in flight spill registers: 222 / 369 us)
-#ifndef KF_ICP_POLL_DEPTH
-#define KF_ICP_POLL_DEPTH 2
-#endif
-      // the batch's addresses are fixed before the loop and a lane without a publisher for slot j polls its own FIRST word once more
-      // (not one shared word: 170 of a coarse level's 208 slots are of this kind and would all hammer one publisher's line; the value is dropped below): no branch around a load, no exec-mask juggling per slot --
-      // the poll iteration was 265 instructions, i.e. the loop noticed a publication up to 0.4 us late
-      unsigned long long u[KF_ICP_POLL_DEPTH][ICP_FOLD_BATCH];
-      const unsigned long long* src[ICP_FOLD_BATCH];
-#pragma unroll
-      for (int j = 0; j < ICP_FOLD_BATCH; ++j) { const int w = w0 + j * parts; src[j] = slots + (size_t)((w < n_wg ? w : w0) * 32 + k); }
-#pragma unroll
-      for (int d = 0; d < KF_ICP_POLL_DEPTH; ++d) {
-        if (d) __builtin_amdgcn_s_sleep(KF_ICP_POLL_PIPE);
-#pragma unroll
-        for (int j = 0; j < ICP_FOLD_BATCH; ++j) u[d][j] = __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-      for (;;) {
-        unsigned stale = 0u;
-#pragma unroll
-        for (int j = 0; j < ICP_FOLD_BATCH; ++j) stale |= (unsigned)(u[0][j] >> 32) ^ tag;
-        if (stale == 0u) break;
-        if ((++spins & 63u) == 0u) {
-          // (somebody else of this launch already gave up and one workgroup is finishing the frame alone: nothing more will be published)
-          if (rescue_tag && __hip_atomic_load(rescue_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == tag_base) { *s_abort = 1; break; }
-          const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-          if (t_wait0 == 0ull) t_wait0 = now; else if (now - t_wait0 > ICP_WAIT_LIMIT) { *s_abort = 1; break; }
-        }
-#pragma unroll
-        for (int d = 0; d + 1 < KF_ICP_POLL_DEPTH; ++d)
-#pragma unroll
-          for (int j = 0; j < ICP_FOLD_BATCH; ++j) u[d][j] = u[d + 1][j];
-        __builtin_amdgcn_s_sleep(KF_ICP_POLL_PIPE);
-#pragma unroll
-        for (int j = 0; j < ICP_FOLD_BATCH; ++j) u[KF_ICP_POLL_DEPTH - 1][j] = __hip_atomic_load(src[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      }
-#pragma unroll
-      for (int j = 0; j < ICP_FOLD_BATCH; ++j) v[j] = (w0 + j * parts < n_wg) ? __uint_as_float((unsigned)u[0][j]) : 0.f;
-#else
-      for (;;) {
-        bool ok = true;
-#pragma unroll
-        for (int j = 0; j < ICP_FOLD_BATCH; ++j) {
-          const int w = w0 + j * parts;
-          v[j] = 0.f;
-          if (w < n_wg && !(exp_mode == 3 && w >= 16 && k != 0)) {     // (experiment 3: wait for every workgroup, move 1/27 of the words)
-            const unsigned long long u = __hip_atomic_load(&slots[w * 32 + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            v[j] = __uint_as_float((unsigned)u);
-            ok = ok && (unsigned)(u >> 32) == tag;
-          }
-        }
-        if (ok) break;
-        __builtin_amdgcn_s_sleep(2);
-        if ((++spins & 63u) == 0u) {                                             // never spin forever
-          const unsigned long long now = __builtin_amdgcn_s_memrealtime();
-          if (t_wait0 == 0ull) t_wait0 = now; else if (now - t_wait0 > ICP_WAIT_LIMIT) { *s_abort = 1; break; }
-        }
-      }
-#endif
-#pragma unroll
-      for (int j = 0; j < ICP_FOLD_BATCH; ++j) s += v[j];
+    int base = 0;                                                               // the batch's first publisher: the same in every lane
+    for (int w0 = part; w0 < n_wg; w0 += ICP_FOLD_BATCH * parts, base += ICP_FOLD_BATCH * parts) {
+      // the poll's form is chosen here, by a uniform branch outside the poll loop
+      const int ns = icp_fold_batch_slots(n_wg, base, parts);
+#define ICP_FOLD_FORM(n) if (ns == (n)) s = fold_batch_tagged<n>(slots, n_wg, w0, parts, k, tag, s, s_abort, exp_mode, rescue_tag, tag_base, t_wait0); else
+      ICP_FOLD_LADDER(ICP_FOLD_FORM)
+#undef ICP_FOLD_FORM
+      s = fold_batch_tagged<ICP_FOLD_BATCH>(slots, n_wg, w0, parts, k, tag, s, s_abort, exp_mode, rescue_tag, tag_base, t_wait0);
     }
   }
   s_tot[part * 32 + k] = s;

@@ -32,7 +32,7 @@ if os.environ.get("KF_ICP_EXP") == "8":
     buf = np.zeros(19 * 1024, np.uint64)
     ctx.lib.kf_exp_read_icp_slots(ctx.h, buf.ctypes.data_as(C.c_void_p), C.c_size_t(24 * 1024 * 32), C.c_size_t(buf.size))
     b = buf.reshape(19, 512, 2).astype(np.int64)
-    grids = [13] * 4 + [50] * 5 + [200] * 10
+    grids = [38] * 4 + [150] * 5 + [200] * 10          # publishers per step at VGA (icp_level_geometry: 1 / 1 / 3 pixels per lane at levels 2 / 1 / 0)
     for s_, g in enumerate(grids):
         pub, fold = b[s_, :g, 0], b[s_, :g, 1]
         t0 = pub.min()
