@@ -1,6 +1,7 @@
-// icp_fold_slots.h -- the two counting rules of the persistent tracking loops (track.hip) that the host shares with the device: how many workgroups publish
-// partial sums at a pyramid level (icp_level_geometry), and how many tagged words a lane of the fold polls per batch (icp_fold_batch_slots).  Plain C++
-// apart from the __host__ __device__ marks: tests/icp_fold_slots_main.cpp compiles this header alone and runs it under sanitizers.  No reference counterpart.
+// icp_fold_slots.h -- the counting rules of the persistent tracking loops (track.hip) that the host shares with the device: how many workgroups publish
+// partial sums at a pyramid level (icp_level_geometry), how many tagged words a lane of the fold polls per batch (icp_fold_batch_slots), and which lane polls
+// which pair of words (icp_fold_pair_lane and its neighbours).  Plain C++ apart from the __host__ __device__ marks: tests/icp_fold_slots_main.cpp and
+// tests/icp_pair_slots_main.cpp compile this header alone and run it under sanitizers.  No reference counterpart.
 #pragma once
 
 #ifndef __host__
@@ -62,3 +63,25 @@ __host__ __device__ static inline int icp_fold_batch_slots(int n_wg, int base, i
 #undef ICP_FOLD_RUNG
   return ICP_FOLD_BATCH;
 }
+
+// The pair form of the fold (the ICP loops): the sums 2m and 2m + 1 of a publisher lie in one aligned 16-byte unit of its slot row (words 2m, 2m + 1 of 32),
+// which a lane of the fold polls with ONE load.  14 pairs cover the 27 sums; the second half of pair 13 is word 27, padding: never added.  The fold's lanes:
+// 16 per part (one DPP row), the first 14 of them one pair each, parts * 16 lanes in all -- the first four of a 512-lane workgroup's eight waves; the other
+// waves poll nothing.  Which publishers a part adds, and in which order, is the rule above, unchanged.
+#define ICP_SUMS 27
+#define ICP_FOLD_PAIRS ((ICP_SUMS + 1) / 2)
+__host__ __device__ static inline int icp_pair_of_sum(int k) { return k >> 1; }
+// does sum `half` (0 / 1) of pair m exist -- or is it the padding word?
+__host__ __device__ static inline bool icp_pair_half_is_sum(int m, int half) { return 2 * m + half < ICP_SUMS; }
+// lane t of the workgroup -> (part, pair); false: the lane polls nothing
+__host__ __device__ static inline bool icp_fold_pair_lane(int t, int parts, int& part, int& m) {
+  part = t >> 4; m = t & 15;
+  return part < parts && m < ICP_FOLD_PAIRS;
+}
+// byte offset of pair m of publisher w in a step's slot array (32 eight-byte words per publisher)
+__host__ __device__ static inline unsigned icp_pair_byte_offset(int w, int m) { return (unsigned)(w * 32 + 2 * m) * 8u; }
+// the pair store (a build variant, -DKF_ICP_STORE16; the product stores single words): the lane that stores pair m after icp_wg_reduce (sum k ends up in lane
+// 4 k + 3: the holder of the pair's second sum, which fetches the first from four lanes below and stores the padding half as {0, tag}) -- and the pair a lane
+// stores, or -1
+__host__ __device__ static inline int icp_pair_store_lane(int m) { return 8 * m + 7; }
+__host__ __device__ static inline int icp_pair_stored_by(int t) { return ((t & 7) == 7 && (t >> 3) < ICP_FOLD_PAIRS) ? (t >> 3) : -1; }

@@ -718,6 +718,91 @@ struct IcpLoopArgs : TrackLoopArgs {
 //    a sweep that is still on its way when the fold is through costs 6 more.
 //    (The loop this one replaces asked for two and, behind a per-lane exit, got one and a half: the compiler waited for the younger set before it
 //    re-issued the older one, and moved both between registers every turn -- 128.9.)
+//
+// PAIRS (icp_fold_slots.h).  The sums 2m and 2m + 1 of a publisher are one aligned 16-byte unit {value, tag, value, tag} of its slot row, and a lane of the
+// ICP loops' fold polls such a unit with ONE 16-byte sc1 load (8-byte sc1 loads move their bytes at 0.54-0.70 x the rate of 16-byte ones), checks both tags
+// and adds two chains: 14 lanes per part instead of 27, half the load instructions per poll.  Each half stays a granule of its own -- its tag sits next to
+// its value, written by one 8-byte store, and a reader trusts a half by that tag alone -- so nothing rests on the 16 bytes being read as one: a half that is
+// stale, or left from an earlier launch, fails its tag and is polled again.  Word 27, the second half of pair 13, is padding: nobody writes it and its
+// tag is not looked at.  The loads are raw buffer loads with aux 16 (sc1) on a descriptor over one step's slot array.
+// Measured (profiles/icp_pair_exchange.txt, tracking stage at C2 in us): single words 114.4, 16-byte polls 109.8, 16-byte polls AND one 16-byte store per
+// pair 111.2, the 16-byte store alone 114.6 -- the publishers keep their 8-byte stores (-DKF_ICP_STORE16: the pair store; -DKF_ICP_POLL8: single-word polls).
+// The SDF loop keeps single words on both sides: the pair poll costs it 16 more bytes of scratch at 256 VGPRs and 3.5 us of its stage.
+typedef unsigned kf_v4u __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t icp_slot_rsrc(const unsigned long long* step_slots) {      // (step_slots: wave-uniform)
+  return __builtin_amdgcn_make_buffer_rsrc((void*)step_slots, 0, KF_ICP_LOOP_MAX_WG * 32 * (int)sizeof(unsigned long long), 0x00020000);
+}
+// Publisher w's 27 sums after icp_wg_reduce / sdf_wg_reduce -- lane 4 k + 3 holds sum k in `sw`, the lanes from 108 on 0.f -- go out as tagged words, one
+// write-through store each.  Every lane calls.
+__device__ __forceinline__ void icp_publish_tagged(unsigned long long* step_slots, int w, unsigned tag, float sw) {
+#ifdef KF_ICP_STORE16
+  // variant: the holder of a pair's second sum fetches the first from four lanes below (same DPP row, same wave) and stores both, the padding half as {0, tag}
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, __float_as_int(sw), 0x114, 0xf, 0xf, true);     // row_shr:4
+  const int m = icp_pair_stored_by((int)threadIdx.x);
+  if (m >= 0) {
+    const kf_v4u q = {lo, tag, __float_as_uint(sw), tag};
+    __builtin_amdgcn_raw_buffer_store_b128(q, icp_slot_rsrc(step_slots), (int)icp_pair_byte_offset(w, m), 0, 16);
+  }
+#else
+  if (threadIdx.x < ICP_SUMS * 4 && (threadIdx.x & 3) == 3)
+    __hip_atomic_store(step_slots + w * 32 + (threadIdx.x >> 2), ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(sw), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#endif
+}
+// One batch of one lane of the pair fold: the 16-byte units of pair m of the publishers w0, w0 + parts, ... (NS of them) are polled until both tags of every
+// unit are current, then added to the two chains s0 (sum 2m) and s1 (sum 2m + 1) in ascending order -- the operands and the order of fold_batch_tagged's
+// chains for k = 2m and 2m + 1.  One poll in flight, one exit at the foot taken by the wave as a whole, the give-up test uniform: as below.
+// (Two sub-lanes sharing a lane's units, the running sums handed from one to the other: built and measured slower, 113.0 against 110.7 -- not kept.)
+template <int NS>
+__device__ __forceinline__ void fold_batch_pairs(__amdgpu_buffer_rsrc_t rsrc, int n_wg, int w0, int parts, int m, unsigned tag, float& s0, float& s1, int* s_abort,
+                                                 const unsigned* rescue_tag, unsigned tag_base, unsigned long long& t_wait0) {
+  unsigned spins = 0;
+  kf_v4u u[NS];
+  int off[NS];
+  // (a unit without a publisher -- the ragged last row: the lane's own first unit once more, the value dropped below; no branch around a load)
+#pragma unroll
+  for (int j = 0; j < NS; ++j) { const int w = w0 + j * parts; off[j] = (int)icp_pair_byte_offset(w < n_wg ? w : w0, m); }
+#pragma unroll
+  for (int j = 0; j < NS; ++j) u[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[j], 0, 16);
+#ifdef KF_ICP_STORE16
+  const unsigned pad = ~0u;
+#else
+  const unsigned pad = icp_pair_half_is_sum(m, 1) ? ~0u : 0u;                   // the padding word is never written: its tag is not looked at
+#endif
+  float v0[NS], v1[NS];
+#pragma unroll
+  for (int j = 0; j < NS; ++j) { v0[j] = 0.f; v1[j] = 0.f; }
+  bool done = false;                                                            // the same in every lane of the wave
+  do {
+    if (++spins == 64u) {                                                       // never spin forever
+      spins = 0u;
+      // (somebody else of this launch already gave up and one workgroup is finishing the frame alone: nothing more will be published)
+      bool give_up = rescue_tag && (unsigned)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(rescue_tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == tag_base;
+      if (!give_up) {
+        const unsigned long long now = __builtin_amdgcn_s_memrealtime();
+        const unsigned long long t0 = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(t_wait0 >> 32)) << 32) |
+                                      (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)t_wait0);
+        if (t0 == 0ull) t_wait0 = now; else give_up = now - t0 > ICP_WAIT_LIMIT;
+      }
+      if (give_up) { *s_abort = 1; done = true; }                               // (the fold is void: its caller looks at s_abort first)
+    }
+    unsigned stale = 0u;
+#pragma unroll
+    for (int j = 0; j < NS; ++j) stale |= (u[j].y ^ tag) | ((u[j].w ^ tag) & pad);
+    if (!done && __ballot(stale != 0u) == 0ull) {                               // current: its values are the ones added
+#pragma unroll
+      for (int j = 0; j < NS; ++j) { v0[j] = __uint_as_float(u[j].x); v1[j] = __uint_as_float(u[j].z); }
+      done = true;
+    }
+    if (!done) {
+      __builtin_amdgcn_s_sleep(KF_ICP_POLL_PIPE);
+      asm volatile("" ::: "memory");                                            // a poll is a new look at memory, every turn
+#pragma unroll
+      for (int j = 0; j < NS; ++j) u[j] = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off[j], 0, 16);
+    }
+  } while (!done);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) { const bool real = w0 + j * parts < n_wg; s0 += real ? v0[j] : 0.f; s1 += real ? v1[j] : 0.f; }
+}
 template <int NS>
 __device__ __forceinline__ float fold_batch_tagged(const unsigned long long* slots, int n_wg, int w0, int parts, int k, unsigned tag, float s, int* s_abort,
                                                    int exp_mode, const unsigned* rescue_tag, unsigned tag_base, unsigned long long& t_wait0) {
@@ -808,11 +893,39 @@ __device__ __forceinline__ float fold_batch_tagged(const unsigned long long* slo
   return s;
 #endif
 }
+// PAIRS: the fold's lanes poll 16-byte units (fold_batch_pairs: 14 lanes per part, in the workgroup's first parts / 4 waves; the other waves go straight to
+// the barrier) -- or single words (fold_batch_tagged: 27 lanes per part, every wave).  The same adds in the same order either way.
+#ifdef KF_ICP_POLL8
+#define ICP_FOLD_PAIRS_DEFAULT false
+#else
+#define ICP_FOLD_PAIRS_DEFAULT true
+#endif
+template <bool PAIRS = ICP_FOLD_PAIRS_DEFAULT>
 __device__ __forceinline__ void fold_partials_tagged(const unsigned long long* slots, int n_wg, unsigned tag, float* s_tot, int* s_abort, int exp_mode = 0,
                                                      const unsigned* rescue_tag = nullptr, unsigned tag_base = 0u) {
-  const int k = threadIdx.x & 31, part = threadIdx.x >> 5, parts = blockDim.x >> 5;
-  float s = 0.f;
+  const int parts = blockDim.x >> 5;
   unsigned long long t_wait0 = 0ull;
+  if constexpr (PAIRS) {
+    int part, m;
+    if (icp_fold_pair_lane((int)threadIdx.x, parts, part, m)) {
+      const __amdgpu_buffer_rsrc_t rsrc = icp_slot_rsrc(slots);
+      float s0 = 0.f, s1 = 0.f;
+      int base = 0;                                                             // the batch's first publisher: the same in every lane
+      for (int w0 = part; w0 < n_wg; w0 += ICP_FOLD_BATCH * parts, base += ICP_FOLD_BATCH * parts) {
+        const int ns = icp_fold_batch_slots(n_wg, base, parts);                 // the poll's form: a uniform branch outside the poll loop
+#define ICP_FOLD_FORM(n) if (ns == (n)) fold_batch_pairs<n>(rsrc, n_wg, w0, parts, m, tag, s0, s1, s_abort, rescue_tag, tag_base, t_wait0); else
+        ICP_FOLD_LADDER(ICP_FOLD_FORM)
+#undef ICP_FOLD_FORM
+        fold_batch_pairs<ICP_FOLD_BATCH>(rsrc, n_wg, w0, parts, m, tag, s0, s1, s_abort, rescue_tag, tag_base, t_wait0);
+      }
+      s_tot[part * 32 + 2 * m] = s0;
+      if (icp_pair_half_is_sum(m, 1)) s_tot[part * 32 + 2 * m + 1] = s1;     // (the padding half's chain goes nowhere)
+    }
+    fold_combine_parts(s_tot, parts);     // the parts' sums, in the order the per-step fold uses too
+    return;
+  }
+  const int k = threadIdx.x & 31, part = threadIdx.x >> 5;
+  float s = 0.f;
   if (k < 27) {
     int base = 0;                                                               // the batch's first publisher: the same in every lane
     for (int w0 = part; w0 < n_wg; w0 += ICP_FOLD_BATCH * parts, base += ICP_FOLD_BATCH * parts) {
@@ -867,7 +980,7 @@ __device__ __forceinline__ unsigned track_commit_decide(KfTrackState* st, unsign
 //    -- the step the others took -- and the workgroup ends with them: the verdict if it is workgroup 0, its own share of the tail.
 // `apply`: the tracker's update from s_tot (STEP_*, behind a workgroup barrier), leaving the running transform in *s_cur; s_tinv: 16 floats of LDS the loop
 // no longer needs (the committed pose's inverse goes there).  Every lane calls.
-template <class Apply>
+template <bool PAIRS = ICP_FOLD_PAIRS_DEFAULT, class Apply>
 __device__ __forceinline__ int track_loop_end(const TrackLoopArgs& L, unsigned commit_seen0, bool solo, LoopOutcome o, float* s_tot, int* s_abort,
                                               float* const& s_cur, Apply& apply, float* s_tinv) {
   KfTrackState* st = L.track;
@@ -875,7 +988,7 @@ __device__ __forceinline__ int track_loop_end(const TrackLoopArgs& L, unsigned c
   __shared__ unsigned s_cull[17];
   for (;;) {
     if (o.code == STEP_PENDING) {
-      fold_partials_tagged(L.slots + (size_t)o.fold * KF_ICP_LOOP_MAX_WG * 32, o.n_pub, L.tag_base + (unsigned)o.fold, s_tot, s_abort, 0,
+      fold_partials_tagged<PAIRS>(L.slots + (size_t)o.fold * KF_ICP_LOOP_MAX_WG * 32, o.n_pub, L.tag_base + (unsigned)o.fold, s_tot, s_abort, 0,
                            solo ? nullptr : &st->rescue_tag, L.tag_base);
       o.timed_out = *s_abort != 0;
     }
@@ -964,9 +1077,8 @@ __device__ __forceinline__ void icp_publish(const IcpLoopArgs& L, const TrackArg
     const bool holder = icp_wg_reduce(acc, s_wave, k, sw);
     if (holder) gsum = (w == g) ? sw : gsum + sw;
     __syncthreads();                                                           // s_wave is reused by the next turn
-    if (holder && w + L.n_loop >= grid_l)                                      // the last turn: publish
-      __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + g * 32 + k,
-                         ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(gsum), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (w + L.n_loop >= grid_l)                                                // the last turn: publish (gsum: 0.f in every lane that holds no sum)
+      icp_publish_tagged(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32, g, L.tag_base + (unsigned)step, gsum);
   }
 }
 
@@ -1067,10 +1179,8 @@ __device__ __forceinline__ LoopOutcome icp_loop_steps(const IcpLoopArgs& L, Trac
 #endif
           // workgroup partial, stored write-through (sc1) for the other CUs
           int k; float sw;
-          if (icp_wg_reduce(acc, s_wave, k, sw))
-            __hip_atomic_store(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32 + blockIdx.x * 32 + k,
-                               ((unsigned long long)(L.tag_base + (unsigned)step) << 32) | (unsigned long long)__float_as_uint(sw),
-                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          icp_wg_reduce(acc, s_wave, k, sw);
+          icp_publish_tagged(L.slots + (size_t)step * KF_ICP_LOOP_MAX_WG * 32, (int)blockIdx.x, L.tag_base + (unsigned)step, sw);
         }
         KF_STAMP(4);
         KF_STAMP(5);
@@ -1339,6 +1449,9 @@ __device__ __forceinline__ bool sdf_wg_reduce(float acc[27], float* s_wave, int&
   }
   return false;
 }
+#ifndef SDF_FOLD_PAIRS
+#define SDF_FOLD_PAIRS false
+#endif
 template <typename AD>
 __global__ void __launch_bounds__(SDF_THREADS) k_sdf_loop(SdfLoopArgs L) {
   __shared__ float s_m[7][16];
@@ -1389,19 +1502,18 @@ __global__ void __launch_bounds__(SDF_THREADS) k_sdf_loop(SdfLoopArgs L) {
           sdf_accumulate_pixel<AD>(L.vol, S, s_m, L.cam, i, d, w_h, v_h, rS, rcell, L.slab_pixels != 0, acc);
         }
         int k; float sw;
-        if (sdf_wg_reduce<SDF_THREADS>(acc, s_wave, k, sw))
-          __hip_atomic_store(L.slots + (size_t)it * KF_ICP_LOOP_MAX_WG * 32 + w * 32 + k,
-                             ((unsigned long long)(L.tag_base + (unsigned)it) << 32) | (unsigned long long)__float_as_uint(sw), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        sdf_wg_reduce<SDF_THREADS>(acc, s_wave, k, sw);
+        icp_publish_tagged(L.slots + (size_t)it * KF_ICP_LOOP_MAX_WG * 32, w, L.tag_base + (unsigned)it, sw);
         __syncthreads();                                                   // s_wave is reused by the next turn
       }
-      fold_partials_tagged(L.slots + (size_t)it * KF_ICP_LOOP_MAX_WG * 32, grid_l, L.tag_base + (unsigned)it, s_tot, &s_abort, 0, solo ? nullptr : &st->rescue_tag, L.tag_base);
+      fold_partials_tagged<SDF_FOLD_PAIRS>(L.slots + (size_t)it * KF_ICP_LOOP_MAX_WG * 32, grid_l, L.tag_base + (unsigned)it, s_tot, &s_abort, 0, solo ? nullptr : &st->rescue_tag, L.tag_base);
       o.fold = it;
       if (s_abort) { o.timed_out = true; break; }
       o.code = apply();
       if (o.code != STEP_APPLIED) break;
       ++o.applied;
     }
-    if (track_loop_end(L, commit_seen0, solo, o, s_tot, &s_abort, s_cur, apply, s_m[1]) != LOOP_SOLO) return;
+    if (track_loop_end<SDF_FOLD_PAIRS>(L, commit_seen0, solo, o, s_tot, &s_abort, s_cur, apply, s_m[1]) != LOOP_SOLO) return;
     solo = true; first = 0; stride = 1;
   }
 }
