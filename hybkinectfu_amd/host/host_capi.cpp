@@ -163,6 +163,8 @@ int hkf_app_brick_store_count(uint64_t out3[3]) {
 // Returns 0 or the reader's HKF_MAP_ERR_* (negative).
 int hkf_app_save_map(const char* path) { if (!g_app) return -1; return path && g_app->saveMap(path) ? 1 : 0; }
 int hkf_app_load_map(const char* path) { if (!g_app) return -1; return path && g_app->loadMap(path) ? 1 : 0; }
+// HybKinectfu::loadMapCoarser: a file of 2, 4 or 8 times this instance's resolution, halved on the device while it is loaded.  Same answers as hkf_app_load_map
+int hkf_app_load_map_coarser(const char* path) { if (!g_app) return -1; return path && g_app->loadMapCoarser(path) ? 1 : 0; }
 // HybKinectfu::mergeMap, the offset in whole bricks: 1 merged, 0 refused or failed, -1 without an application
 int hkf_app_merge_map(const char* path, int ox, int oy, int oz) {
   if (!g_app) return -1;

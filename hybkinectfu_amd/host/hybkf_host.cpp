@@ -697,6 +697,71 @@ bool HybKinectfu::alignMap(const std::string& path, const Mat44& guess, Mat44& f
   if (rep.verdict != KF_ALIGN_CONVERGED) fprintf(stderr, "alignMap: %s: no convergence (verdict %u after %u steps, %.0f pairs)\n", path.c_str(), rep.verdict, rep.iterations, rep.sums[28]);
   return rep.verdict == KF_ALIGN_CONVERGED;
 }
+bool HybKinectfu::loadMapCoarser(const std::string& path) {
+  if (!_inited) return false;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  lastTracked();                                                // as loadMap: a frame still in flight settles first
+  // 1. the file checked as a whole; the volume this instance's but for a resolution 2^L times as fine, L in [1, 3]: nothing is touched before
+  HkfMapHeader h;
+  memset(&h, 0, sizeof(h));
+  const int is = hkf_map_info(path.c_str(), &h);
+  const uint32_t res = p->_volume_params.nResolution;
+  if (is == HKF_MAP_OK && h.resolution == res) return loadMap(path);
+  unsigned levels = 0;
+  for (unsigned l = 1; l <= 3; ++l) if (h.resolution == (uint64_t)res << l) levels = l;
+  if (is != HKF_MAP_OK || levels == 0 || memcmp(&h.size_m, &p->_volume_params.fVolumeMeterSize, 4) != 0 ||
+      memcmp(&h.max_weight, &p->_volume_params.fWeightMax, 4) != 0 || (h.has_color != 0) != p->_switch_params.useRGBData || h.n_bricks > 0xFFFFFFFFull) {
+    fprintf(stderr, "loadMapCoarser: %s refused (%d)%s\n", path.c_str(), is, is == HKF_MAP_OK ? ": its volume is not this instance's at 2, 4 or 8 times the resolution" : "");
+    return false;
+  }
+  const bool color = h.has_color != 0;
+  std::vector<int32_t> keys;
+  std::vector<float> t, w;
+  std::vector<uint8_t> col;
+  if (!read_whole_map("loadMapCoarser", path, h, color, keys, t, w, col)) return false;
+  // 2. from here on a failure leaves an EMPTY map, as loadMap's does.  Level by level through the store: reserved (which clears it) for the level's coarse
+  // keys, the finer map merged halved into it, and for the next level read out again
+  bool ok = 0 == dm->check(kf_reset_volume(ctx));
+  for (unsigned l = 0; ok && l < levels; ++l) {
+    const uint32_t n = (uint32_t)(keys.size() / 3);
+    const int64_t coarse = kf_halved_brick_keys(n, keys.data(), nullptr, 0);
+    ok = coarse >= 0;
+    if (!ok) break;
+    const uint64_t want = (uint64_t)coarse > p->_volume_params.nBrickStoreBricks ? (uint64_t)coarse : p->_volume_params.nBrickStoreBricks;
+    ok = setBrickStore((unsigned)(want ? want : 1u)) &&        // (a store of one brick for an empty map: kf_place_window needs a store)
+         0 == dm->check(kf_merge_brick_store_halved(ctx, n, keys.data(), t.data(), w.data(), color ? col.data() : nullptr));
+    if (!ok || l + 1 == levels) break;
+    uint32_t held = 0;
+    ok = 0 == dm->check(kf_brick_store_count(ctx, &held, nullptr, nullptr));
+    if (!ok) break;
+    try {
+      keys.resize((size_t)held * 3); t.resize((size_t)held * HKF_MAP_BRICK_VOX); w.resize((size_t)held * HKF_MAP_BRICK_VOX);
+      if (color) col.resize((size_t)held * HKF_MAP_BRICK_VOX * 3);
+    } catch (const std::bad_alloc&) { ok = false; break; }
+    ok = !held || 0 == dm->check(kf_read_brick_store(ctx, 0, held, keys.data(), t.data(), w.data(), color ? col.data() : nullptr));
+  }
+  // 3. the window where the file's stood, on the coarse lattice: 8 * floor(origin / 2^L / 8) per axis
+  int32_t o[3];
+  const int64_t step = (int64_t)8 << levels;
+  for (int k = 0; k < 3; ++k) {
+    const int64_t v = h.origin_vox[k];
+    o[k] = (int32_t)(8 * (v >= 0 ? v / step : -((-v + step - 1) / step)));
+  }
+  if (!ok || dm->check(kf_place_window(ctx, o[0], o[1], o[2]))) { dm->check(kf_reset_volume(ctx)); return false; }
+  // 4. the file's pose in the new window's coordinates: fp64, rounded to fp32 once
+  Mat44 pose; memcpy(pose.entries, h.pose, 64);
+  const double s_file = (double)h.size_m / (double)h.resolution, s_ctx = (double)h.size_m / (double)res;
+  for (int k = 0; k < 3; ++k) pose.entries[4 * k + 3] = (float)(((double)pose.entries[4 * k + 3] + (double)h.origin_vox[k] * s_file) - (double)o[k] * s_ctx);
+  _camera_pose_finder->setCameraPose(pose);
+  _frame_id = h.frame_id; _last_tracked = true; _pending = false;
+  const bool resident = _camera_pose_finder->deviceResident();
+  const kf_mat44 kp = to_kf(pose);
+  kf_raycast_params rp = {p->_raycast_params.fRayIncrement};  // loadMap's raycast
+  return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rp, &p->_depth_camera_params,
+                                          p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
+}
 bool HybKinectfu::recentre() {
   const AppParams* p = AppParams::instance();
   int32_t d[3];

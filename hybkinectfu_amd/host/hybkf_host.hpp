@@ -297,6 +297,15 @@ public:
   // raw context.  A finder that keeps its pose on the host does not see such a move: placing the window behind this class's back is not supported there.
   bool saveMap(const std::string& path);
   bool loadMap(const std::string& path);
+  // loadMapCoarser: loadMap for a file recorded at 2^L times this instance's resolution, L in [1, 3], with the same size, max weight and colour flag: the
+  // map is halved L times on the device (kf_merge_brick_store_halved: the mean tsdf of the observed children, their least weight, their mean colour).
+  // L == 0 is loadMap; any other file is refused (false) with nothing touched.  The whole file is read into host memory; then the volume is reset and, level
+  // by level, the store is reserved at max(its capacity, the level's coarse bricks: kf_halved_brick_keys), the finer map is merged halved into it and, for
+  // the next level, read out again.  The window is placed at 8 * floor(origin_file / 2^L / 8) per axis (floor also for a negative origin).  The pose is the
+  // file's with its translation moved into the new window's coordinates, in fp64 and rounded to fp32 once:
+  //   t_k = (float)(((double)t_file_k + origin_file_k * (double)size / (double)resolution_file) - origin_new_k * (double)size / (double)resolution)
+  // Frame id, the raycast and what a failure leaves are loadMap's.
+  bool loadMapCoarser(const std::string& path);
   // mergeMap: fuses the map file into this session's map, voxel by voxel (kf_merge_brick_store: the weighted running average, exact in fp32, so merging
   // A into B and B into A give the same bricks).  offsetBricks (nullptr: zero) translates the file's keys by whole bricks into this session's world
   // frame; offsets that are no whole bricks go through the other mergeMap, and alignMap finds its transform.  The file is checked as loadMap checks it, and every

@@ -59,6 +59,7 @@ public:
   // HybKinectfu's map on disk is built on the brick store, a single-GPU feature: a slab group has no store to save from or load into.  Always false.
   bool saveMap(const std::string&) { return false; }
   bool loadMap(const std::string&) { return false; }
+  bool loadMapCoarser(const std::string&) { return false; }
   bool mergeMap(const std::string&, const int*) { return false; }
   bool mergeMap(const std::string&, const Mat44&) { return false; }
   bool alignMap(const std::string&, const Mat44&, Mat44&, kf_align_report*) { return false; }

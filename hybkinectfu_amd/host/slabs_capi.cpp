@@ -134,5 +134,6 @@ int hkf_slabs_load_map(const char* path) { if (!g_slabs) return -1; return path 
 int hkf_slabs_merge_map(const char*, int, int, int) { return -1; }
 int hkf_slabs_merge_map_rigid(const char*, const float*) { return -1; }
 int hkf_slabs_align_map(const char*, const float*, float*, void*) { return -1; }
+int hkf_slabs_load_map_coarser(const char*) { return -1; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

@@ -196,6 +196,15 @@ class App:
             raise K.KfError("hkf_app_load_map: no application")
         return bool(r)
 
+    def load_map_coarser(self, path):
+        """HybKinectfu::loadMapCoarser: load_map for a file of 2, 4 or 8 times this application's resolution (same size, max weight and colour): the map is
+        halved on the device, once per factor of two, the window placed at 8 * floor(origin / factor / 8) and the pose moved into its coordinates.  A file of
+        this application's resolution is loaded as load_map loads it.  False, with nothing touched: any other file"""
+        r = self.h.hkf_app_load_map_coarser(os.fsencode(path))
+        if r < 0:
+            raise K.KfError("hkf_app_load_map_coarser: no application")
+        return bool(r)
+
     def merge_map(self, path, offset=(0, 0, 0)):
         """HybKinectfu::mergeMap: the file's map fused into this session's voxel by voxel (the weighted running average), its keys translated by
         `offset` whole bricks; the window shows the result and the next process_frame is tracked against it.  Pose and frame id stay.  False, with
@@ -348,6 +357,10 @@ class SlabsApp:
     def load_map(self, path):
         """HybKinectfuSlabs::loadMap: always False, nothing touched"""
         return self.h.hkf_slabs_load_map(os.fsencode(path)) > 0
+
+    def load_map_coarser(self, path):
+        """always False, nothing touched, as load_map"""
+        return self.h.hkf_slabs_load_map_coarser(os.fsencode(path)) > 0
 
     def merge_map(self, path, offset=(0, 0, 0)):
         """always False, nothing touched: merging maps is built on the brick store, which a slab group does not have"""

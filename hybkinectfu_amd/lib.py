@@ -124,6 +124,7 @@ SYMBOLS = [
     "kf_write_brick_store", "kf_brick_store_capture", "kf_place_window",
     "kf_merge_brick_store", "kf_refill_window", "kf_merge_brick_store_rigid", "kf_rigid_brick_keys",
     "kf_align_brick_store", "kf_align_step",
+    "kf_merge_brick_store_halved", "kf_halved_brick_keys",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -179,6 +180,9 @@ def load():
         _lib.kf_align_brick_store.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.POINTER(AlignParams),
                                               C.POINTER(AlignReport)]
         _lib.kf_align_step.argtypes = [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        _lib.kf_merge_brick_store_halved.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        _lib.kf_halved_brick_keys.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64]
+        _lib.kf_halved_brick_keys.restype = C.c_int64
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -226,6 +230,20 @@ def rigid_brick_keys(keys, xf):
     out = np.zeros((n, 3), np.int32)
     if n:
         lib.kf_rigid_brick_keys(len(keys), _p(keys), x, _p(out), n)
+    return out
+
+
+def halved_brick_keys(keys):
+    """the coarse bricks (n, 3), unique and sorted by (z, y, x), of a map with brick keys `keys` at half its resolution: key >> 1 per component
+    (kf_halved_brick_keys)"""
+    lib = load()
+    keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+    n = lib.kf_halved_brick_keys(len(keys), _p(keys), None, 0)
+    if n < 0:
+        raise KfError("kf_halved_brick_keys: a key component outside the key range")
+    out = np.zeros((n, 3), np.int32)
+    if n:
+        lib.kf_halved_brick_keys(len(keys), _p(keys), _p(out), n)
     return out
 
 
@@ -840,6 +858,17 @@ class Context:
         c = np.ascontiguousarray(color, np.uint8) if color is not None else None
         assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
         _chk(self.lib.kf_merge_brick_store_rigid(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None, rigid_xf(xf)), "kf_merge_brick_store_rigid")
+
+    def merge_brick_store_halved(self, keys, tsdf, weight, color=None):
+        """merge_brick_store's arrays, read as a map of HALF this store's voxel size: every coarse voxel is formed from its eight children -- the mean
+        tsdf of the observed ones, their least weight, their mean colour, unobserved where none is observed --; then merged by the same rule
+        (kf_merge_brick_store_halved)"""
+        keys = np.ascontiguousarray(keys, np.int32).reshape(-1, 3)
+        n = len(keys)
+        t, w = np.ascontiguousarray(tsdf, np.float32), np.ascontiguousarray(weight, np.float32)
+        c = np.ascontiguousarray(color, np.uint8) if color is not None else None
+        assert t.size == n * 512 and w.size == n * 512 and (c is None or c.size == n * 1536)
+        _chk(self.lib.kf_merge_brick_store_halved(self.h, n, _p(keys), _p(t), _p(w), _p(c) if c is not None else None), "kf_merge_brick_store_halved")
 
     def align_brick_store(self, keys, tsdf, weight, xf, centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
         """the rigid transform that lays the map (keys, tsdf, weight) onto this store, refined from the guess xf = [R | t] (3x4, source world -> this

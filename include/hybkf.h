@@ -659,6 +659,35 @@ int64_t kf_rigid_brick_keys(uint32_t count, const int32_t* keys, const double xf
 int kf_merge_brick_store_rigid(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color,
                                const double xf[12]);
 
+/* Halving a map's resolution: an incoming (source) map at voxel size s becomes a map at voxel size 2 s, which is merged into the store as above.  The TSDF
+ * is stored normalised by the metric truncation distance, so the halved map is a valid TSDF for a context of the same size, the same truncation and half the
+ * resolution; the call itself never looks at the context's resolution.  Coordinates are world voxel indices: coarse voxel g covers the eight fine voxels
+ * 2 g + d, d in {0, 1}^3, and its centre (2 g + 1) s is the mean of their centres.  Hence coarse brick K draws on the source bricks 2 K + {0, 1}^3.
+ * kf_halved_brick_keys (no context, host only): the coarse bricks of a source map, K_j >> 1 per component with the arithmetic shift (-1 gives -1, -3 gives
+ *   -2).  Unique, sorted by (z, y, x).  Returns their number and writes the first `cap` keys (three int32 each); -1: NULL keys with count > 0, NULL out_keys
+ *   with cap > 0, a key component outside [-2^20, 2^20).
+ * kf_merge_brick_store_halved: kf_read_brick_store's layout for the source map (count entries: keys, tsdf, weight, colour bytes or NULL).  Blocks.
+ *   Per coarse voxel, its children indexed i = dx | dy << 1 | dz << 2.  A child is OBSERVED when the source holds its brick and its weight is > 0.
+ *   n = the number of observed children.  n == 0: the voxel is unobserved -- tsdf 0, weight 0, colour 0.  Otherwise, in fp32, one rounded operation per
+ *   operation written here, the division correctly rounded, c_i = the child's tsdf, or 0.f when the child is unobserved:
+ *     tsdf:   sum = ((c0 + c1) + (c2 + c3)) + ((c4 + c5) + (c6 + c7));  tsdf = sum / (float)n
+ *     weight: the minimum of the observed children's weights (exact): a halved voxel is never trusted more than its least observed child
+ *     colour: per channel (2 * S + n) / (2 * n) in integers, S = the sum of the observed children's bytes (their mean, rounded half up)
+ *   Hence eight observed children of one value v give v exactly when 8 v does not overflow, -0.0 included, and eight observed values that are linear in the
+ *   position, with every partial sum exact, give the same linear function at the coarse centre.
+ *   The halved brick b then meets the held brick a under kf_merge_brick_store's rule, word for word: a brick with no halved weight > 0 takes no slot and
+ *   changes none; a key not held claims a slot and is written as kf_write_brick_store writes it (dropped when the store is full); a key held is merged per
+ *   voxel with the held TRUE weight and its deferred-weight word becomes 0; with `color` NULL on a context with a colour plane a fresh slot's colour is 0 and
+ *   a held one's stays; a key inside the current window is shadowed (kf_refill_window).
+ *   As the rigid merge, the whole source goes to the device at once -- the three planes, an open-addressing table over its keys, the coarse keys --, in
+ *   temporary allocations freed before the call returns: a coarse brick draws on up to 8 source bricks, so the call cannot be chunked.  The window, the pose,
+ *   the model maps and the triangle buffer stay bit for bit.
+ *   Refused with nothing touched -- KF_ERR_ARG: a NULL context; a z-slab context; with count > 0, NULL keys, tsdf or weight, a key component out of range,
+ *   a key twice (count == 0 does nothing and looks at no array).  KF_ERR_STATE: no store reserved; `color` on a context without a colour plane.
+ *   KF_ERR_ALLOC: the temporaries do not fit. */
+int64_t kf_halved_brick_keys(uint32_t count, const int32_t* keys, int32_t* out_keys, int64_t cap);
+int kf_merge_brick_store_halved(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color);
+
 /* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
  * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
  * voxels a start 10 degrees and about 5 voxels off still converges; a start much further off finds too few pairs or a wrong minimum.  Coarse-to-fine search
