@@ -22,6 +22,7 @@
 //             vertex's list ordered by face index -> one lane per vertex adds its faces' unit normals in that order.
 // Every output is a function of the soup's order alone, never of slot positions, arrival order or scheduling.
 #include "kf_internal.h"
+#include "weld_mesh.h"
 #include "scan.h"
 #include <limits.h>
 #include <string.h>
@@ -31,25 +32,6 @@
 enum { WELD_UNDECIDED = 0, WELD_IN = 1, WELD_OUT = 2 };
 // device words: [0] cells still undecided after the round, [1] distinct cells, [2] output vertices, [3] output faces, [4] a lookup found no cell (never)
 enum { WW_UNDECIDED = 0, WW_CELLS = 1, WW_NV = 2, WW_NF = 3, WW_ERR = 4, WW_WORDS = 8 };
-
-struct KfWeld {
-  // scratch, sized by the triangle count
-  size_t cap_tris; unsigned table_cap;
-  unsigned* table;                 // [table_cap] soup-vertex index per cell; afterwards [face_cap] face index per index triple
-  unsigned* vslot;                 // [3 cap_tris] the slot of every soup vertex's cell; afterwards the slot of every face's triple
-  unsigned char* state[2];         // [table_cap] WELD_* per slot, double-buffered across rounds
-  unsigned char* lonely;           // [table_cap] the cell has no neighbour cell at all (round 0)
-  unsigned* vrank;                 // [3 cap_tris + 1] flag, then output vertex id, per soup vertex
-  unsigned* lookup;                // [3 cap_tris] output vertex id per soup vertex = the remapped faces
-  unsigned* frank;                 // [cap_tris + 1] flag, then output face id, per triangle
-  unsigned* partials;              // scan partials
-  unsigned* words;                 // [WW_WORDS]
-  // the indexed mesh (+ what the normals need), sized by the output counts
-  size_t cap_v, cap_f; int cap_color;
-  float* out_v; float* out_n; float* out_c; unsigned* vstart; unsigned* cursor;      // [3 cap_v] x 2, [4 cap_v], [cap_v + 1], [cap_v]
-  unsigned* out_f; unsigned* flist; float* fnorm;                                   // [3 cap_f] x 3
-  unsigned n_v, n_f, n_rounds; int has_color, valid;
-};
 
 // ---- device arithmetic -------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ const float* weld_pos(const kf_triangle* tris, unsigned v) {
@@ -268,16 +250,6 @@ __global__ void __launch_bounds__(256) k_weld_normals(unsigned n_vertices, const
 }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
-static void weld_free_list(void*** ptrs, int n) { for (int i = 0; i < n; ++i) { if (*ptrs[i]) hipFree(*ptrs[i]); *ptrs[i] = nullptr; } }
-// all or nothing: what the list held is freed first; on failure every pointer of it is null again
-static int weld_alloc_list(void*** ptrs, const size_t* sizes, int n) {
-  weld_free_list(ptrs, n);
-  for (int i = 0; i < n; ++i) {
-    if (sizes[i] == 0) continue;
-    if (hipMalloc(ptrs[i], sizes[i]) != hipSuccess) { (void)hipGetLastError(); *ptrs[i] = nullptr; weld_free_list(ptrs, n); return KF_ERR_ALLOC; }
-  }
-  return 0;
-}
 static void weld_free_scratch(KfWeld* w) {
   void** p[] = {(void**)&w->table, (void**)&w->vslot, (void**)&w->state[0], (void**)&w->state[1], (void**)&w->lonely, (void**)&w->vrank, (void**)&w->lookup,
                 (void**)&w->frank, (void**)&w->partials, (void**)&w->words};
@@ -291,18 +263,8 @@ static void weld_free_mesh(KfWeld* w) {
 }
 void kf_weld_free(kf_ctx* c) {
   if (!c->weld) return;
-  weld_free_scratch(c->weld); weld_free_mesh(c->weld);
+  weld_free_scratch(c->weld); weld_free_mesh(c->weld); kf_mesh_parts_free(c->weld);
   delete c->weld; c->weld = nullptr;
-}
-static int weld_read_words(kf_ctx* c, const unsigned* dev, unsigned* out, int n) {
-  KF_CHECK(hipMemcpyAsync(c->host_pinned, dev, n * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-  KF_CHECK(hipStreamSynchronize(c->stream));
-  memcpy(out, c->host_pinned, n * sizeof(unsigned));
-  return 0;
-}
-static unsigned weld_grid(const kf_ctx* c, size_t n) {
-  const size_t wgs = (n + 255) / 256, walk = (size_t)(c->num_cus > 0 ? c->num_cus : 256) * 8u;
-  return (unsigned)(wgs < 1 ? 1 : (wgs < walk ? wgs : walk));
 }
 
 extern "C" int kf_write_triangles(kf_ctx* c, const kf_triangle* src, uint32_t first, uint32_t count) {
@@ -325,7 +287,7 @@ extern "C" int kf_weld_mesh(kf_ctx* c, int has_color, float thresh) {
   if (n_tris > 0xFFFFFFFFu / 3u) return KF_ERR_ARG;
   if (!c->weld) { c->weld = new (std::nothrow) KfWeld(); if (!c->weld) return KF_ERR_ALLOC; memset((void*)c->weld, 0, sizeof(KfWeld)); }
   KfWeld* w = c->weld;
-  w->valid = 0;
+  w->valid = 0; w->parts_valid = 0;
   if (n_tris == 0) { w->n_v = w->n_f = w->n_rounds = 0; w->has_color = has_color != 0; w->valid = 1; return 0; }
   const unsigned nv = 3u * n_tris;
   if (n_tris > w->cap_tris) {                                          // scratch: kept for the next weld, grown when a larger soup comes

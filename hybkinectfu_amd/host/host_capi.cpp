@@ -3,6 +3,7 @@
 #include "hybkf_host.hpp"
 #include "png_reader.hpp"
 #include "map_file.hpp"
+#include "mesh_parts.hpp"
 #include <string.h>
 
 static HybKinectfu* g_app = nullptr;
@@ -215,6 +216,8 @@ int hkf_app_save_mesh(const char* filename, unsigned* n_vertices, unsigned* n_fa
 }
 // MeshGeneratorMarchingcube::setDeviceWeld: the application's saveMesh welds on the device from now on (0: on the host again)
 int hkf_app_set_device_weld(int on) { if (!g_mesh) return -1; g_mesh->setDeviceWeld(on != 0); return 0; }
+// MeshGeneratorMarchingcube::setMinPartFaces: the application's saveMesh drops the mesh's small parts after the weld (0, 0: off again)
+int hkf_app_set_min_part_faces(unsigned n, int largest_only) { if (!g_mesh) return -1; g_mesh->setMinPartFaces(n, largest_only != 0); return 0; }
 
 // ---- GPU-free mesh post-processing on a caller-supplied triangle soup (kf_triangle layout) ---------------------------------------
 static MeshGeneratorMarchingcube* g_soup = nullptr;
@@ -239,6 +242,21 @@ int hkf_mesh_read(int which, float* vertices, float* normals, float* colors, uns
   if (normals) memcpy(normals, m->normals.data(), m->normals.size() * 4);
   if (colors) memcpy(colors, m->colors.data(), m->colors.size() * 4);
   if (faces) memcpy(faces, m->faces.data(), m->faces.size() * 4);
+  return 0;
+}
+// the parts of the mesh on one host thread (mesh_parts.hpp; the rule: include/hybkf.h): labels / part_faces n_vertices words each, either may be null
+int hkf_mesh_parts(int which, unsigned* labels, unsigned* part_faces) {
+  const MeshData* m = mesh_of(which); if (!m) return -1;
+  std::vector<unsigned> l, s;
+  meshParts(*m, l, s);
+  if (labels && !l.empty()) memcpy(labels, l.data(), l.size() * 4);
+  if (part_faces && !s.empty()) memcpy(part_faces, s.data(), s.size() * 4);
+  return 0;
+}
+// dropParts on the mesh itself
+int hkf_mesh_drop_parts(int which, unsigned min_faces, int largest_only) {
+  MeshData* m = which == 0 ? (g_soup ? &g_soup->mesh() : nullptr) : (g_mesh ? &g_mesh->mesh() : nullptr); if (!m) return -1;
+  dropParts(*m, min_faces, largest_only != 0);
   return 0;
 }
 int hkf_mesh_save(int which, const char* filename) { const MeshData* m = mesh_of(which); return m && m->saveToFile(filename) ? 1 : 0; }

@@ -3,6 +3,7 @@
 // src/utils/eigen_utils.cpp, src/MeshGeneratorMarchingcube.cpp, src/utils/mesh/meshData.{h,cpp}, src/utils/mesh/MeshIO.cpp.
 #include "hybkf_host.hpp"
 #include "map_file.hpp"
+#include "mesh_parts.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
@@ -1017,12 +1018,15 @@ void MeshGeneratorMarchingcube::weldMesh() {                    // :69-84
   _meshes.removeDuplicateFaces();
   _meshes.computeVertexNormals();
 }
-bool MeshGeneratorMarchingcube::weldOnDevice() {                // :69-86 as kf_weld_mesh; false (mesh untouched) when there is nothing to weld or the device refuses
+void MeshGeneratorMarchingcube::dropMeshParts() { if (dropsParts()) dropParts(_meshes, _min_part_faces, _largest_only); }
+bool MeshGeneratorMarchingcube::weldOnDevice() {               // :69-86 as kf_weld_mesh; false (mesh untouched) when there is nothing to weld or the device refuses
   CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
   if (!dm->ctx() || triangleCount() == 0) return false;
   const bool col = AppParams::instance()->_switch_params.useRGBData;
   uint32_t nv = 0, nf = 0;
-  if (kf_weld_mesh(dm->ctx(), col, 0.0001f) != 0 || kf_mesh_counts(dm->ctx(), &nv, &nf, nullptr) != 0) return false;
+  if (kf_weld_mesh(dm->ctx(), col, 0.0001f) != 0) return false;
+  if (dropsParts() && kf_mesh_drop_parts(dm->ctx(), _min_part_faces, _largest_only, nullptr, nullptr) != 0) return false;
+  if (kf_mesh_counts(dm->ctx(), &nv, &nf, nullptr) != 0) return false;
   MeshData m;
   m.vertices.resize((size_t)nv * 3); m.normals.resize((size_t)nv * 3); m.faces.resize((size_t)nf * 3);
   if (col) m.colors.resize((size_t)nv * 4);
@@ -1034,6 +1038,7 @@ bool MeshGeneratorMarchingcube::saveMesh(const std::string& filename) {   // :61
   if (!_device_weld || !weldOnDevice()) {
     if (!copyTrianglesToCPU()) return false;
     weldMesh();
+    dropMeshParts();
   }
   if (!_world) {                                                 // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
     int32_t o[3] = {0, 0, 0};

@@ -374,6 +374,7 @@ public:
   bool saveMesh(const std::string& filename) override;
   unsigned triangleCount();
   const MeshData& mesh() const { return _meshes; }
+  MeshData& mesh() { return _meshes; }
   // the two halves of copyTrianglesToCPU + saveMesh that need no device: usable on any triangle soup (CPU tests pin them
   // against the reference's own ml::MeshData, tests/golden/mesh_*.npz)
   void setTriangles(const kf_triangle* tris, unsigned n, bool with_color);   // :39-58
@@ -382,6 +383,12 @@ public:
   // Off by default; if the device weld fails, saveMesh welds on the host as before.
   void setDeviceWeld(bool on) { _device_weld = on; }
   bool deviceWeld() const { return _device_weld; }
+  // saveMesh drops, after the weld, every connected part of the mesh with fewer than n faces -- with largest_only all but the largest (the rule:
+  // include/hybkf.h, kf_mesh_drop_parts).  On the device (kf_mesh_drop_parts, before the read-back) under setDeviceWeld(true), on the host
+  // (mesh_parts.hpp) otherwise: the same file either way.  The default (0, false) is off: saveMesh writes the bytes it always wrote.
+  void setMinPartFaces(unsigned n, bool largest_only = false) { _min_part_faces = n; _largest_only = largest_only; }
+  bool dropsParts() const { return _min_part_faces > 0 || _largest_only; }
+  void dropMeshParts();                                                      // the host side of it, on the mesh as it stands (nothing when off)
   // AppParams::_volume_params.bMapMesh: with a brick store reserved, generateMesh clears the triangle buffer and meshes the whole map (kf_marching_cubes_map)
   void setMapMesh(bool on);
 protected:
@@ -389,5 +396,7 @@ protected:
   bool weldOnDevice();                                                       // :61-86 without the 72 bytes per triangle crossing to the host
   MeshData _meshes;
   bool _device_weld = false;
+  unsigned _min_part_faces = 0;
+  bool _largest_only = false;
   bool _world = false;            // the triangles of the last generateMesh are in world coordinates already (streaming on, or the map mesh): saveMesh adds no origin
 };

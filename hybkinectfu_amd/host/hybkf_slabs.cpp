@@ -174,6 +174,7 @@ bool HybKinectfuSlabs::saveMesh(const std::string& filename) {   // :61-96 on th
   if (!check(kf_group_read_triangles(_group, tris.data(), 0, n))) return false;
   _mesh.setTriangles(tris.data(), n, _color);
   _mesh.weldMesh();
+  _mesh.dropMeshParts();
   int o[3]; volumeOrigin(o);                                   // a moved volume: the file holds world coordinates (a zero origin leaves every byte)
   const int32_t o32[3] = {o[0], o[1], o[2]};
   hkf_world_positions(_mesh.data().vertices.data(), _mesh.data().vertices.size() / 3, o32, volume_cell());

@@ -38,6 +38,8 @@ public:
   void generateMesh();
   bool saveMesh(const std::string& filename);
   unsigned triangleCount();
+  // MeshGeneratorMarchingcube::setMinPartFaces: saveMesh drops the mesh's small parts after its (host) weld; (0, false) is off
+  void setMinPartFaces(unsigned n, bool largest_only = false) { _mesh.setMinPartFaces(n, largest_only); }
   const MeshData& mesh() const { return _mesh.mesh(); }
   // HybKinectfu::viewModelMaps through member 0: after a frame's merge every member holds the whole volume's model maps.  cols * rows * 4 bytes
   // (b, g, r, a); mode = KF_VIEW_*, KF_VIEW_COLOR on a colour group only.  Blocking.

@@ -79,6 +79,12 @@ class App:
         if self.h.hkf_app_set_device_weld(int(bool(on))) != 0:
             raise K.KfError("hkf_app_set_device_weld: no application")
 
+    def set_min_part_faces(self, n, largest_only=False):
+        """save_mesh drops, after the weld, the mesh's connected parts with fewer than n faces (largest_only: all but the largest); on the device
+        under set_device_weld, on the host otherwise, same file.  (0, False), the default, is off."""
+        if self.h.hkf_app_set_min_part_faces(C.c_uint32(int(n)), int(bool(largest_only))) != 0:
+            raise K.KfError("hkf_app_set_min_part_faces: no application")
+
     def render_view(self, mode, pose, cam):
         """HybKinectfu::renderView: `cam` = (cols, rows, cx, cy, fx, fy) from `pose` (None: the current camera pose), mode = lib.VIEW_*;
         returns (rows, cols, 4) uint8 (b, g, r, a).  Increment and planes are the application's."""
@@ -473,6 +479,24 @@ def mesh_from_soup(triangles, with_color=False):
 def mesh_save(which, filename):
     """which: 0 = the mesh of mesh_from_soup, 1 = the application's mesh (after App.save_mesh)"""
     return bool(load().hkf_mesh_save(which, filename.encode()))
+
+
+def mesh_parts(which):
+    """GPU-free: per vertex of the mesh `which` (label = smallest vertex index of its part, faces of its part), two (n_v,) u32 arrays"""
+    h = load()
+    nv, nf, nc = C.c_uint32(), C.c_uint32(), C.c_uint32()
+    if h.hkf_mesh_sizes(which, C.byref(nv), C.byref(nf), C.byref(nc)) != 0:
+        raise K.KfError("no mesh")
+    lab, cnt = np.empty(nv.value, np.uint32), np.empty(nv.value, np.uint32)
+    h.hkf_mesh_parts(which, lab.ctypes.data_as(C.c_void_p), cnt.ctypes.data_as(C.c_void_p))
+    return lab, cnt
+
+
+def mesh_drop_parts(which, min_faces=0, largest_only=False):
+    """GPU-free: drops the small parts of the mesh `which` on one host thread (the rule of kf_mesh_drop_parts) and returns the cleaned mesh"""
+    if load().hkf_mesh_drop_parts(which, C.c_uint32(int(min_faces)), int(bool(largest_only))) != 0:
+        raise K.KfError("no mesh")
+    return _mesh_read(which)
 
 
 def app_mesh():

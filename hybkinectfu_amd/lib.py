@@ -114,6 +114,7 @@ SYMBOLS = [
     "kf_upload_depth_mm_next", "kf_take_next_depth", "kf_cull_tail_counts", "kf_count_observed_voxels", "kf_get_fusion_counters",
     "kf_get_fusion_form", "kf_get_raycast_form",
     "kf_write_triangles", "kf_weld_mesh", "kf_mesh_counts", "kf_read_mesh", "kf_weld_release",
+    "kf_mesh_parts", "kf_read_mesh_parts", "kf_mesh_drop_parts",
     "kf_set_rgb_device", "kf_raycast_volume_slab_cross_spec_color", "kf_slab_ray_normals_color", "kf_set_model_maps_rays_color",
     "kf_render_view", "kf_render_view_at", "kf_view_model_maps", "kf_view_size", "kf_view_device", "kf_read_view",
     "kf_view_slab_cross", "kf_view_slab_normals", "kf_view_from_rays",
@@ -682,6 +683,26 @@ class Context:
         f = np.empty((nf, 3), np.uint32)
         _chk(self.lib.kf_read_mesh(self.h, _p(v), _p(n), _p(c) if with_color else None, _p(f)), "kf_read_mesh")
         return dict(vertices=v, normals=n, colors=c, faces=f)
+
+    def mesh_parts(self):
+        """(parts with a face, faces of the largest, orphans, labelling rounds) of the current mesh; include/hybkf.h has the rule"""
+        n, big, orph, nr = C.c_uint32(), C.c_uint32(), C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_mesh_parts(self.h, C.byref(n), C.byref(big), C.byref(orph), C.byref(nr)), "kf_mesh_parts")
+        return n.value, big.value, orph.value, nr.value
+
+    def read_mesh_parts(self):
+        """per vertex of the current mesh: (label = smallest vertex index of its part, faces of its part), two (n_v,) u32 arrays"""
+        nv = self.mesh_counts()[0]
+        lab, cnt = np.empty(nv, np.uint32), np.empty(nv, np.uint32)
+        _chk(self.lib.kf_read_mesh_parts(self.h, _p(lab), _p(cnt)), "kf_read_mesh_parts")
+        return lab, cnt
+
+    def mesh_drop_parts(self, min_faces=0, largest_only=False):
+        """drops the parts with fewer than max(min_faces, 1) faces (largest_only: all but the largest) from the mesh on the device;
+        returns (parts dropped, orphans dropped); mesh_counts / read_mesh report the cleaned mesh"""
+        pd, od = C.c_uint32(), C.c_uint32()
+        _chk(self.lib.kf_mesh_drop_parts(self.h, C.c_uint32(int(min_faces)), int(bool(largest_only)), C.byref(pd), C.byref(od)), "kf_mesh_drop_parts")
+        return pd.value, od.value
 
     def weld_release(self):
         _chk(self.lib.kf_weld_release(self.h), "kf_weld_release")

@@ -344,6 +344,38 @@ int kf_read_mesh(kf_ctx* ctx, float* vertices, float* normals, float* colors, ui
 /* frees the weld's scratch and mesh (MeshData::clear, src/utils/mesh/meshData.h:440); the next kf_weld_mesh allocates again */
 int kf_weld_release(kf_ctx* ctx);
 
+/* The parts of the mesh, and dropping the small ones on the device.  The reference has nothing for it (MeshData knows removeIsolatedVertices,
+ * src/utils/mesh/meshData.cpp:320-356, and no notion of a piece); every user of such a mesh removes the crumbs that sensor noise and half-observed
+ * bricks leave floating in free space, by face count or by keeping the largest piece.  The rule:
+ *   input mesh      the mesh of the last kf_weld_mesh: n_v vertices, n_f faces.
+ *   connectivity    two vertices are connected when one face names both; a PART is a connected set of vertices.
+ *   label           a part's label is the smallest vertex index in it.
+ *   face membership a face belongs to the part of its vertices (all three lie in one part by construction).
+ *   part size       part_faces(label) = the number of faces of the part.
+ *   orphans         a vertex that no face names is an orphan: a part of 0 faces (the weld leaves one where a vertex's only faces were degenerate).
+ *   keep            with min_faces and largest_only, a part is kept iff part_faces >= max(min_faces, 1); orphans never are.
+ *   largest only    with largest_only != 0 a part is additionally kept only if it has the greatest face count; a tie goes to the smallest label.
+ *                   Nothing is kept if no part reaches min_faces.
+ *   face order      kept faces stay in their order.
+ *   vertex order    kept vertices stay in ascending old index and are renumbered densely -- the soup's order, like everything the weld emits, and NOT
+ *                   the first-use order of removeIsolatedVertices.
+ *   attributes      positions, normals and colours of kept vertices are copied verbatim.  Normals are not recomputed: every face that names a kept vertex
+ *                   is kept, in the same relative order, so computeVertexNormals would add the same unit normals in the same order and give the same bits.
+ *   faces           are remapped to the new vertex indices.
+ * Every output is a function of the mesh alone, whatever the scheduling: integer atomics only, labelling in rounds with one 4-byte read-back each.
+ *
+ * kf_mesh_parts: labels the current mesh.  n_parts: parts with at least one face; largest_faces: the face count of the largest; n_orphans; n_rounds: the
+ *   rounds the labelling took (at most n_v).  Any pointer may be NULL.  Blocking.  KF_ERR_ARG on a NULL context, KF_ERR_STATE before a weld or after
+ *   kf_weld_release.  An empty mesh gives zeros.  The labels are kept until the next weld, drop or release.
+ * kf_read_mesh_parts: per vertex its part's label and its part's face count, n_v words each; either may be NULL.  Labels the mesh first if that was not done.
+ * kf_mesh_drop_parts: rewrites the mesh by the rule.  parts_dropped: parts with a face that went; orphans_dropped: orphans that went (all of them).
+ *   Afterwards kf_mesh_counts and kf_read_mesh report the cleaned mesh, n_rounds unchanged.  The soup is only read (kf_read_triangles is unchanged), a
+ *   second identical call changes nothing, and the next kf_weld_mesh gives the full mesh again.  The buffers are the context's, grown as the weld's are
+ *   and freed by kf_weld_release / kf_destroy. */
+int kf_mesh_parts(kf_ctx* ctx, uint32_t* n_parts, uint32_t* largest_faces, uint32_t* n_orphans, uint32_t* n_rounds);
+int kf_read_mesh_parts(kf_ctx* ctx, uint32_t* vertex_label, uint32_t* vertex_part_faces);
+int kf_mesh_drop_parts(kf_ctx* ctx, uint32_t min_faces, int largest_only, uint32_t* parts_dropped, uint32_t* orphans_dropped);
+
 /* Viewer frames.  The reference shows three pictures per frame (src/HybKinectfu.cpp:145-158): DataViewer::viewNormal on the new and the model
  * normals and DataViewer::viewColors on the raycast colours -- each a blocking clone(CPU) of a whole map and a loop on one host thread
  * (src/DataViewer.cpp:13-44).  Here the picture is made on the device, 4 bytes per pixel (b, g, r, a from the low byte up) in a context-owned image
