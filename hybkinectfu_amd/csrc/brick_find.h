@@ -3,8 +3,8 @@
 #include "kf_internal.h"
 #include "brick_key.h"
 
-// read-only: the slot of `key`, or KF_BRICK_NO_SLOT.  The probe ends at the first free entry: entries are never freed, so a key that was ever
-// inserted sits before it.
+// read-only: the slot of `key`, or KF_BRICK_NO_SLOT.  The probe ends at the first free entry: no entry is ever emptied in place (erase.hip rebuilds the whole table in launches of
+// its own), so a key the table holds sits before it.
 __device__ __forceinline__ unsigned store_find(const KfBrickStore& st, unsigned long long key) {
   unsigned h = kf_brick_key_hash(key, st.mask);
   for (unsigned p = 0; p <= st.mask; ++p, h = (h + 1u) & st.mask) {

@@ -10,7 +10,7 @@
 // two, so a look-up never meets a half-made entry.  Inside one eviction launch every key occurs once (the departing boxes are disjoint), hence a
 // key is either in the table since an earlier launch -- found by a plain read-only probe, its slot overwritten: the window's copy is the newer one --
 // or new: then the brick takes a slot first and claims a table entry second.  A brick that finds no free slot is counted as dropped and claims
-// nothing, so the table never holds a key without a slot and never fills up: a later look-up of a dropped key misses.  Nothing is ever deleted.
+// nothing, so the table never holds a key without a slot and never fills up: a later look-up of a dropped key misses.  No kernel here deletes: erase.hip does.
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"

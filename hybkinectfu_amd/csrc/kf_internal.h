@@ -140,7 +140,7 @@ __device__ __forceinline__ unsigned kf_new_voxels(bool count, bool u0, float w0,
 
 // The brick store (brickstore.hip; kf_brick_store_reserve ...): a sparse archive of the bricks that have left the moving window, keyed by world brick
 // coordinate (brick_key.h).  Slot i holds one brick verbatim -- its 4 KiB of (tsdf, weight), its 2 KiB of colour on a context with a colour plane, its
-// deferred-weight word -- and its key; slots are handed out in order and never freed, so [0, cnt->held) are the entries.  tkey / tslot: an open-addressing
+// deferred-weight word -- and its key; slots are handed out in order, so [0, cnt->held) are the entries (erase.hip, the only place that frees slots, fills the holes before it returns).  tkey / tslot: an open-addressing
 // hash table (linear probing, `mask + 1` entries, a power of two >= 2 * max_bricks; KF_BRICK_KEY_EMPTY marks a free entry) from key to slot.  An entry is
 // claimed only once its brick has a slot, so the table never holds more than max_bricks keys and every probe ends at a free entry.
 struct KfBrickStoreCounts { unsigned held, pad_; unsigned long long dropped, restored; };
@@ -271,6 +271,9 @@ struct kf_ctx {
   // the virtual window of kf_render_view_at (viewat.hip), the call's own scratch: one all-zero brick (4 KiB), 16 bytes per brick slot, the virtual skip tables
   // (kf_skip_table_words), the virtual has-negative bits (kf_negbit_words) and 16 floats of pose.  Allocated by the first call, freed with the volume's planes.
   void* view_at_scratch;
+  // kf_brick_store_erase_box / kf_brick_store_erase_weak (erase.hip): a few 32-bit words per slot of the store -- keep flags and their prefix, the list of holes,
+  // the scan's chunk sums, the result.  Allocated by the first erase for the store's capacity, allocated anew when that has changed, freed by kf_destroy.
+  void* erase_scratch; uint32_t erase_scratch_bricks;
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,
@@ -719,3 +722,4 @@ int kf_brick_store_restore(kf_ctx* ctx, const int s[3], const int32_t origin_vox
 int kf_brick_store_capture_enqueue(kf_ctx* ctx);   // kf_brick_store_capture past its checks (kf_place_window); asynchronous
 int kf_brick_store_reset(kf_ctx* ctx);   // no entries, counts zero (kf_brick_store_clear, kf_reset_volume); asynchronous
 void kf_brick_store_free(kf_ctx* ctx);   // for kf_destroy and kf_brick_store_reserve: the caller has synchronised the stream
+void kf_erase_scratch_free(kf_ctx* ctx); // (erase.hip) for kf_destroy: the caller has synchronised the stream

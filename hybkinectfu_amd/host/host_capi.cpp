@@ -3,6 +3,7 @@
 #include "hybkf_host.hpp"
 #include "png_reader.hpp"
 #include "map_file.hpp"
+#include "erase_box_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <string.h>
 
@@ -190,6 +191,28 @@ int hkf_app_align_map(const char* path, const float guess[16], float found[16], 
   const bool ok = g_app->alignMap(path, g, f, (kf_align_report*)report);
   memcpy(found, f.entries, 64);
   return ok ? 1 : 0;
+}
+// HybKinectfu::eraseMapBox (lo, hi: WORLD metres) and eraseMapWeak: 1 erased, 0 refused or failed, -1 without an application.  out2 (may be NULL): bricks removed,
+// observed voxels cleared (eraseMapWeak: out1, bricks removed).  hkf_erase_map_box_voxels needs no application: the voxel box of a box in metres
+int hkf_app_erase_map_box(const float lo_m[3], const float hi_m[3], int keep_inside, uint64_t out2[2]) {
+  if (!g_app) return -1;
+  if (!lo_m || !hi_m) return 0;
+  unsigned removed = 0; uint64_t cleared = 0;
+  const bool ok = g_app->eraseMapBox(lo_m, hi_m, keep_inside != 0, &removed, &cleared);
+  if (out2) { out2[0] = removed; out2[1] = cleared; }
+  return ok ? 1 : 0;
+}
+int hkf_app_erase_map_weak(float min_weight, uint64_t out1[1]) {
+  if (!g_app) return -1;
+  unsigned removed = 0;
+  const bool ok = g_app->eraseMapWeak(min_weight, &removed);
+  if (out1) out1[0] = removed;
+  return ok ? 1 : 0;
+}
+int hkf_erase_map_box_voxels(const float lo_m[3], const float hi_m[3], float cell, int32_t lo_vox[3], int32_t hi_vox[3]) {
+  if (!lo_m || !hi_m || !lo_vox || !hi_vox) return -1;
+  hkf_erase_box_voxels(lo_m, hi_m, cell, lo_vox, hi_vox);
+  return 0;
 }
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
 int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {

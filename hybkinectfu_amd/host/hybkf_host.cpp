@@ -3,6 +3,7 @@
 // src/utils/eigen_utils.cpp, src/MeshGeneratorMarchingcube.cpp, src/utils/mesh/meshData.{h,cpp}, src/utils/mesh/MeshIO.cpp.
 #include "hybkf_host.hpp"
 #include "map_file.hpp"
+#include "erase_box_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <math.h>
 #include <string.h>
@@ -697,6 +698,38 @@ bool HybKinectfu::alignMap(const std::string& path, const Mat44& guess, Mat44& f
   }
   if (rep.verdict != KF_ALIGN_CONVERGED) fprintf(stderr, "alignMap: %s: no convergence (verdict %u after %u steps, %.0f pairs)\n", path.c_str(), rep.verdict, rep.iterations, rep.sums[28]);
   return rep.verdict == KF_ALIGN_CONVERGED;
+}
+bool HybKinectfu::eraseMapBox(const float lo_m[3], const float hi_m[3], bool keepInside, unsigned* bricksRemoved, uint64_t* voxelsCleared) {
+  if (bricksRemoved) *bricksRemoved = 0;
+  if (voxelsCleared) *voxelsCleared = 0;
+  if (!_inited || !lo_m || !hi_m) return false;
+  for (int k = 0; k < 3; ++k) if (lo_m[k] != lo_m[k] || hi_m[k] != hi_m[k]) return false;   // NaN
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  int32_t lo[3], hi[3];
+  hkf_erase_box_voxels(lo_m, hi_m, cell, lo, hi);
+  lastTracked();                                                // a frame still in flight settles first: the raycast below uses this session's pose
+  if (!mergeMakeRoom(p->_switch_params.useRGBData, 0)) return false;      // the window captured: the store alone is this session's map
+  uint32_t removed = 0; uint64_t cleared = 0;
+  const int es = dm->check(kf_brick_store_erase_box(dm->ctx(), lo, hi, keepInside ? KF_ERASE_OUTSIDE : KF_ERASE_INSIDE, &removed, &cleared));
+  if (!mergeShow()) return false;                               // (also after a failed erase: window and store must not disagree)
+  if (bricksRemoved) *bricksRemoved = removed;
+  if (voxelsCleared) *voxelsCleared = cleared;
+  return es == 0;
+}
+bool HybKinectfu::eraseMapWeak(float minWeight, unsigned* bricksRemoved) {
+  if (bricksRemoved) *bricksRemoved = 0;
+  if (!_inited || minWeight != minWeight) return false;          // (NaN: kf_brick_store_erase_weak would refuse it after the capture)
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  lastTracked();
+  if (!mergeMakeRoom(p->_switch_params.useRGBData, 0)) return false;
+  uint32_t removed = 0;
+  const int es = dm->check(kf_brick_store_erase_weak(dm->ctx(), minWeight, &removed));
+  if (!mergeShow()) return false;
+  if (bricksRemoved) *bricksRemoved = removed;
+  return es == 0;
 }
 bool HybKinectfu::loadMapCoarser(const std::string& path) {
   if (!_inited) return false;

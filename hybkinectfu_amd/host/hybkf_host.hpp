@@ -331,6 +331,17 @@ public:
   // nothing: window, pose, model maps and frame id stay.  `found`: the transform of the last successful evaluation, in metres (the rotation rounded to
   // fp32); true only when the verdict is KF_ALIGN_CONVERGED.  report (may be nullptr): the call's report.
   bool alignMap(const std::string& path, const Mat44& guess, Mat44& found, kf_align_report* report);
+  // eraseMapBox: clears the voxels of this session's map whose centres lie inside the box (keepInside: outside it -- the map cropped to the box); bricks
+  // left with nothing observed leave the store and their slots are free again (kf_brick_store_erase_box).  The box is in WORLD metres, the first cube's
+  // coordinates -- those of the map mesh's vertices and of worldPose --, half-open: voxel g is in it iff lo_m <= (g + 1/2) * cell < hi_m on every axis
+  // (hkf_erase_box_voxels, erase_box_voxels.hpp; cell the fp32 quotient size / resolution).  A NaN corner is refused (false) with nothing touched.
+  // eraseMapWeak: removes every brick whose greatest weight is below minWeight (kf_brick_store_erase_weak); the others stay bit for bit.
+  // Both, in this order: a frame still in flight settles; the window is captured into the store (a store that was never reserved is reserved with room for
+  // every brick of the window; false with nothing erased when a brick did not fit); the erase; the window is re-read from the store (kf_refill_window) and
+  // the model maps are raycast as shiftVolume does, so the next processNewFrame is TRACKED against the erased model.  Pose and frame id stay.  Surface
+  // already streamed into the world soup (setStreamMesh) is not taken back.  bricksRemoved / voxelsCleared (may be nullptr): the call's counts.
+  bool eraseMapBox(const float lo_m[3], const float hi_m[3], bool keepInside, unsigned* bricksRemoved = nullptr, uint64_t* voxelsCleared = nullptr);
+  bool eraseMapWeak(float minWeight, unsigned* bricksRemoved = nullptr);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();

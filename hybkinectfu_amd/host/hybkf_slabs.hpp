@@ -65,6 +65,8 @@ public:
   bool mergeMap(const std::string&, const int*) { return false; }
   bool mergeMap(const std::string&, const Mat44&) { return false; }
   bool alignMap(const std::string&, const Mat44&, Mat44&, kf_align_report*) { return false; }
+  bool eraseMapBox(const float*, const float*, bool, unsigned* = nullptr, uint64_t* = nullptr) { return false; }
+  bool eraseMapWeak(float, unsigned* = nullptr) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

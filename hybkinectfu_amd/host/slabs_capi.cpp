@@ -135,5 +135,8 @@ int hkf_slabs_merge_map(const char*, int, int, int) { return -1; }
 int hkf_slabs_merge_map_rigid(const char*, const float*) { return -1; }
 int hkf_slabs_align_map(const char*, const float*, float*, void*) { return -1; }
 int hkf_slabs_load_map_coarser(const char*) { return -1; }
+// erasing from the map is built on the brick store too: always -1, nothing touched
+int hkf_slabs_erase_map_box(const float*, const float*, int, uint64_t*) { return -1; }
+int hkf_slabs_erase_map_weak(float, uint64_t*) { return -1; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

@@ -240,6 +240,29 @@ class App:
             raise K.KfError("hkf_app_align_map: no application")
         return bool(r), found.reshape(4, 4), rep
 
+    def erase_map_box(self, lo, hi, keep_inside=False):
+        """HybKinectfu::eraseMapBox: the voxels of this session's map whose centres lie in the box lo <= centre < hi (WORLD metres: the map mesh's
+        coordinates) are cleared -- with keep_inside those outside it, which crops the map --, emptied bricks leave the store; the window shows the
+        result and the next process_frame is tracked against it.  False, with nothing erased: a NaN corner, or a brick did not fit during the capture.
+        The counts of the last call: erase_counts"""
+        l, h = (C.c_float * 3)(*[float(x) for x in lo]), (C.c_float * 3)(*[float(x) for x in hi])
+        out = (C.c_uint64 * 2)()
+        r = self.h.hkf_app_erase_map_box(l, h, int(bool(keep_inside)), out)
+        if r < 0:
+            raise K.KfError("hkf_app_erase_map_box: no application")
+        self.erase_counts = (int(out[0]), int(out[1]))
+        return bool(r)
+
+    def erase_map_weak(self, min_weight):
+        """HybKinectfu::eraseMapWeak: every brick of this session's map whose greatest weight is below min_weight is removed, the others stay bit for bit;
+        capture, window and raycast as erase_map_box.  erase_counts: (bricks removed, 0)"""
+        out = (C.c_uint64 * 1)()
+        r = self.h.hkf_app_erase_map_weak(C.c_float(min_weight), out)
+        if r < 0:
+            raise K.KfError("hkf_app_erase_map_weak: no application")
+        self.erase_counts = (int(out[0]), 0)
+        return bool(r)
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -383,6 +406,15 @@ class SlabsApp:
         found = g.copy()
         self.h.hkf_slabs_align_map(os.fsencode(path), g.ctypes.data_as(C.c_void_p), found.ctypes.data_as(C.c_void_p), None)
         return False, found.reshape(4, 4), None
+
+    def erase_map_box(self, lo, hi, keep_inside=False):
+        """always False, nothing touched: erasing from the map is built on the brick store, which a slab group does not have"""
+        l, h = (C.c_float * 3)(*[float(x) for x in lo]), (C.c_float * 3)(*[float(x) for x in hi])
+        return self.h.hkf_slabs_erase_map_box(l, h, int(bool(keep_inside)), None) > 0
+
+    def erase_map_weak(self, min_weight):
+        """always False, nothing touched, as erase_map_box"""
+        return self.h.hkf_slabs_erase_map_weak(C.c_float(min_weight), None) > 0
 
     def close(self):
         self.h.hkf_slabs_shutdown()

@@ -126,6 +126,7 @@ SYMBOLS = [
     "kf_merge_brick_store", "kf_refill_window", "kf_merge_brick_store_rigid", "kf_rigid_brick_keys",
     "kf_align_brick_store", "kf_align_step",
     "kf_merge_brick_store_halved", "kf_halved_brick_keys",
+    "kf_brick_store_erase_box", "kf_brick_store_erase_weak",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -184,6 +185,8 @@ def load():
         _lib.kf_merge_brick_store_halved.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         _lib.kf_halved_brick_keys.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_int64]
         _lib.kf_halved_brick_keys.restype = C.c_int64
+        _lib.kf_brick_store_erase_box.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        _lib.kf_brick_store_erase_weak.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_uint32)]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -247,6 +250,8 @@ def halved_brick_keys(keys):
         lib.kf_halved_brick_keys(len(keys), _p(keys), _p(out), n)
     return out
 
+
+ERASE_INSIDE, ERASE_OUTSIDE = 0, 1                                    # kf_brick_store_erase_box: mode
 
 ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_FEW_PAIRS, ALIGN_SINGULAR = 0, 1, 2, 3   # kf_align_report.verdict
 
@@ -903,6 +908,22 @@ class Context:
         _chk(self.lib.kf_align_brick_store(self.h, n, _p(keys), _p(t), _p(w), x, C.byref(align_params(centre, max_iter, min_pairs, eps_rot, eps_trans)),
                                            C.byref(rep)), "kf_align_brick_store")
         return np.array(x[:], np.float64).reshape(3, 4), rep
+
+    def brick_store_erase_box(self, lo, hi, mode=ERASE_INSIDE):
+        """clears the voxels of the store inside the half-open box lo <= g < hi of world voxel indices (ERASE_OUTSIDE: outside it); bricks left with
+        nothing observed are removed and their slots are free again.  The store only: capture first and refill_window() afterwards to erase from the
+        map.  Returns (bricks removed, observed voxels cleared) (kf_brick_store_erase_box)"""
+        l, h = (C.c_int32 * 3)(*[int(x) for x in lo]), (C.c_int32 * 3)(*[int(x) for x in hi])
+        removed, cleared = C.c_uint32(), C.c_uint64()
+        _chk(self.lib.kf_brick_store_erase_box(self.h, l, h, int(mode), C.byref(removed), C.byref(cleared)), "kf_brick_store_erase_box")
+        return removed.value, cleared.value
+
+    def brick_store_erase_weak(self, min_weight):
+        """removes every brick of the store whose greatest true weight is below min_weight; the others stay bit for bit.  Returns the bricks removed
+        (kf_brick_store_erase_weak)"""
+        removed = C.c_uint32()
+        _chk(self.lib.kf_brick_store_erase_weak(self.h, float(min_weight), C.byref(removed)), "kf_brick_store_erase_weak")
+        return removed.value
 
     def refill_window(self):
         """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never

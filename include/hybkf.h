@@ -573,8 +573,8 @@ int kf_set_stream_out(kf_ctx* ctx, int on, int has_color, float threshold_marchi
  *   is free the brick is counted as dropped and a later look-up of its key misses.  A brick never observed takes no entry.  After the move every
  *   brick that has entered (destination brick b with b + d / 8 outside) is looked up, read-only: on a hit the entry is copied back -- tsdf, weight,
  *   colour and deferred-weight word, bit for bit -- and the brick's flags, its has-negative bit and the skip tables follow as for a moved brick, so
- *   a shift away and back is lossless and "shifted here" still equals "uploaded there".  A restored brick stays in the store (nothing is ever
- *   deleted); until it leaves again the window's copy is the only current one.  Still asynchronous, no allocation, no synchronisation: two more
+ *   a shift away and back is lossless and "shifted here" still equals "uploaded there".  A restored brick stays in the store (a shift never
+ *   deletes; only kf_brick_store_erase_box / _weak do); until it leaves again the window's copy is the only current one.  Still asynchronous, no allocation, no synchronisation: two more
  *   launches.  KF_ERR_ARG, with nothing touched and nothing enqueued, when a brick of the old or of the new window would have a world brick
  *   coordinate outside [-2^20, 2^20).  With stream-out on, a restored brick that leaves again is streamed again: the world soup is not de-duplicated.
  * kf_brick_store_reserve: (re)allocates the store for max_bricks bricks (4 KiB each, + 2 KiB with a colour plane, + a hash table of the next power of
@@ -719,6 +719,36 @@ int kf_merge_brick_store_rigid(kf_ctx* ctx, uint32_t count, const int32_t* keys,
  *   KF_ERR_ALLOC: the temporaries do not fit. */
 int64_t kf_halved_brick_keys(uint32_t count, const int32_t* keys, int32_t* out_keys, int64_t cap);
 int kf_merge_brick_store_halved(kf_ctx* ctx, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color);
+
+/* Erasing from the map: a box of voxels cleared in the store, or everything but the box; bricks that were hardly ever observed thrown out.  Emptied bricks
+ * leave the store and their slots are handed out again (no reference counterpart).  All on the device: no brick crosses the bus.
+ * Coordinates are world voxel indices: voxel g lies in the brick with key g >> 3 (arithmetic shift: negative coordinates floor) at in-brick position g & 7.
+ * The box is half-open, lo_vox <= g < hi_vox on every axis, and is clamped to the key range [-2^23, 2^23] first, so any int32 box is legal.  An axis with
+ * lo >= hi makes the box empty.
+ * kf_brick_store_erase_box: mode KF_ERASE_INSIDE clears every voxel inside the box, KF_ERASE_OUTSIDE every voxel outside it (the map cropped to the box).
+ *   A cleared voxel is (tsdf, weight) = (+0.0f, +0.0f) with colour bytes 0 0 0 0: what kf_reset_volume leaves.  Per held brick, from its key alone:
+ *     no voxel to clear:   the brick stays bit for bit, its deferred-weight word included;
+ *     all 512 to clear:    the brick is removed;
+ *     anything in between: the voxels are cleared, the others keep their tsdf, their colour and their TRUE weight (what kf_read_brick_store reports), and
+ *                          the brick's deferred-weight word becomes 0 whether or not an observed voxel was hit; a brick with no weight > 0 left is removed.
+ *   *bricks_removed: the bricks removed; *voxels_cleared: the cleared voxels whose true weight was > 0, those of removed bricks included.  Either may be NULL.
+ * kf_brick_store_erase_weak: removes every brick whose greatest TRUE weight is < min_weight; every other brick stays bit for bit.  min_weight <= 0
+ *   removes nothing.
+ * After either call the store is what it would be had it never held the removed bricks: `held` is the number of bricks kept and entries [0, held) are
+ *   dense (their order is unspecified, as ever, and changes), `dropped` and `restored` are unchanged, every kept key is found and every removed key misses,
+ *   a freed slot is handed out again, kf_brick_store_bounds shrinks accordingly.  The table is rebuilt, not patched: emptying an entry in place would cut the
+ *   probe chains that run through it.  The capacity stays (kf_brick_store_reserve).
+ *   The window is not touched: a key inside the current window is shadowed by the window's copy, as after kf_write_brick_store.  To erase from the MAP:
+ *   kf_brick_store_capture, the erase, kf_refill_window -- and a raycast before the next frame is tracked.  Triangles already streamed into the world soup
+ *   (kf_set_stream_out) are not taken back.
+ *   Blocking: one read of the counts sizes the launches, one read at the end returns the results.  The scratch (a few 32-bit words per slot) is the
+ *   context's, allocated by the first call.
+ *   Refused with nothing touched -- KF_ERR_ARG: a NULL context, a NULL lo_vox or hi_vox, a mode other than the two, a NaN min_weight, a z-slab context.
+ *   KF_ERR_STATE: no store reserved. */
+#define KF_ERASE_INSIDE 0
+#define KF_ERASE_OUTSIDE 1
+int kf_brick_store_erase_box(kf_ctx* ctx, const int32_t lo_vox[3], const int32_t hi_vox[3], int mode, uint32_t* bricks_removed, uint64_t* voxels_cleared);
+int kf_brick_store_erase_weak(kf_ctx* ctx, float min_weight, uint32_t* bricks_removed);
 
 /* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
  * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
