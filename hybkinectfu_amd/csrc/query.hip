@@ -1,0 +1,249 @@
+// query.hip -- querying the map where it lies: tsdf, gradient, weight and colour at N points (kf_map_sample), the first surface crossing of N rays
+// (kf_map_cast_rays).  The map is the window's bricks and, outside the window, the brick store's (map_lookup.h): no resolve table, no window move, no copy.
+// The march is the reference's (src/cuda/raycastingVolume.cu:79-117) restated over the map; the sample has no reference counterpart -- its value and
+// gradient are align_voxel's lines (align.hip), its colour v_interp_color's (vwindow.h).  The contract is written out above kf_map_sample in
+// include/hybkf.h, the argument in DESIGN.md 4e-8.  Both kernels only read the context: one lane per point / ray, 256-thread workgroups, grid-stride.
+#include "kf_internal.h"
+#include "brick_key.h"
+#include "brick_find.h"
+#include "resample_shared.h"
+#include "map_lookup.h"
+#include <stdint.h>
+#include <math.h>
+
+using namespace mapq;
+
+#define KF_QUERY_LIMIT 8388608.0       // 2^23: positions beyond +-this many voxels read unobserved (the key range, brick_key.h)
+#define KF_QUERY_MAX_STEPS (1u << 24)  // (float)k is exact up to here
+
+// one coordinate of a sample: u = p - 1/2 (voxel g has its centre at g + 1/2), base voxel floor(u), fraction (float)(u - floor(u)) -- the difference is exact
+// in fp64 (|u| < 2^24), so one rounding.  false: p is not finite or lies outside the key range.
+__device__ __forceinline__ bool query_split(double p, int& n, float& f) {
+  if (!(fabs(p) <= KF_QUERY_LIMIT)) return false;
+  const double u = p - 0.5, fl = floor(u);
+  n = (int)fl;
+  f = (float)(u - fl);
+  return true;
+}
+
+struct QuerySample { float tsdf, weight, gx, gy, gz; uchar4 color; };
+
+// The map at point (px, py, pz), world voxels.  All eight corners n + {0, 1}^3 are read (corner k: x from bit 0, y from bit 1, z from bit 2); false --
+// unobserved -- when one of them reads weight 0.  GRAD: the gradient too; COLOR: the colour too (0 on a map without a colour plane).
+template <bool GRAD, bool COLOR>
+__device__ __forceinline__ bool query_sample(const MapRef& m, double px, double py, double pz, MapBrick& b, QuerySample& s) {
+  int nx, ny, nz;
+  float fx, fy, fz;
+  if (!query_split(px, nx, fx) || !query_split(py, ny, fy) || !query_split(pz, nz, fz)) return false;
+  float v[8];
+  uchar4 col[8];
+  float wmin = 0.f;
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    unsigned off;
+    const float2 q = map_voxel(m, nx + (k & 1), ny + ((k >> 1) & 1), nz + (k >> 2), b, off);
+    v[k] = q.x;
+    wmin = k == 0 ? q.y : fminf(wmin, q.y);
+    ok = ok && q.y > 0.f;
+    if (COLOR) col[k] = q.y > 0.f ? map_voxel_color(b, off) : make_uchar4(0, 0, 0, 0);
+  }
+  if (!ok) return false;
+  // align_voxel's lines: the value x, then y, then z; the gradient from the same eight values
+  const float a0 = lerp1(v[0], v[1], fx), a1 = lerp1(v[2], v[3], fx), a2 = lerp1(v[4], v[5], fx), a3 = lerp1(v[6], v[7], fx);
+  const float b0 = lerp1(a0, a1, fy), b1 = lerp1(a2, a3, fy);
+  s.tsdf = lerp1(b0, b1, fz);
+  s.weight = wmin;
+  if (GRAD) {
+    const float d0 = v[1] - v[0], d1 = v[3] - v[2], d2 = v[5] - v[4], d3 = v[7] - v[6];
+    s.gx = lerp1(lerp1(d0, d1, fy), lerp1(d2, d3, fy), fz);
+    s.gy = lerp1(a1 - a0, a3 - a2, fz);
+    s.gz = b1 - b0;
+  }
+  if (COLOR) {
+    // v_interp_color's arithmetic and corner order: its corner j has x from bit 2, y from bit 1, z from bit 0
+    const float a = fx, bb = fy, c = fz, ia = 1 - a, ib = 1 - bb, ic = 1 - c;
+    float acc[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const uchar4 cj = col[(j >> 2) | (j & 2) | ((j & 1) << 2)];
+      const float wa = (j >> 2) ? a : ia, wb = ((j >> 1) & 1) ? bb : ib, wc = (j & 1) ? c : ic;
+      const float t0 = (float)cj.x * wa * wb * wc, t1 = (float)cj.y * wa * wb * wc, t2 = (float)cj.z * wa * wb * wc;
+      acc[0] = (j == 0) ? t0 : acc[0] + t0; acc[1] = (j == 0) ? t1 : acc[1] + t1; acc[2] = (j == 0) ? t2 : acc[2] + t2;
+    }
+    s.color = make_uchar4((unsigned char)acc[0], (unsigned char)acc[1], (unsigned char)acc[2], 0);
+  }
+  return true;
+}
+
+// the tsdf of the voxel the point lies in, floor(p): what the reference's getVoxel reads on the march.  0 where nobody observed.
+__device__ __forceinline__ float query_nearest(const MapRef& m, double px, double py, double pz, MapBrick& b) {
+  if (!(fabs(px) <= KF_QUERY_LIMIT) || !(fabs(py) <= KF_QUERY_LIMIT) || !(fabs(pz) <= KF_QUERY_LIMIT)) return 0.f;
+  unsigned off;
+  return map_voxel(m, (int)floor(px), (int)floor(py), (int)floor(pz), b, off).x;
+}
+
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_map_sample(MapRef m, unsigned n, const double* __restrict__ pos, float* __restrict__ out_tsdf, float* __restrict__ out_weight,
+                                                    float* __restrict__ out_grad, unsigned char* __restrict__ out_color) {
+  MapBrick b = map_brick_none();
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+    QuerySample s;
+    const bool ok = query_sample<true, COLOR>(m, pos[3 * i], pos[3 * i + 1], pos[3 * i + 2], b, s);
+    if (out_tsdf) out_tsdf[i] = ok ? s.tsdf : 0.f;
+    if (out_weight) out_weight[i] = ok ? s.weight : 0.f;
+    if (out_grad) { out_grad[3 * i] = ok ? s.gx : 0.f; out_grad[3 * i + 1] = ok ? s.gy : 0.f; out_grad[3 * i + 2] = ok ? s.gz : 0.f; }
+    if (out_color) {
+      const uchar4 c = (COLOR && ok) ? s.color : make_uchar4(0, 0, 0, 0);
+      out_color[4 * i] = c.x; out_color[4 * i + 1] = c.y; out_color[4 * i + 2] = c.z; out_color[4 * i + 3] = 0;
+    }
+  }
+}
+
+// One lane per ray.  Sample k at t_k = t_min + (float)k * step, per axis origin + (double)(t_k * dir): the product in fp32, the sum in fp64.  A sample in a
+// brick nobody holds is answered by the lane's cached "absent" with no load.  The crossing: the last nearest-voxel tsdf > 0 and this one < 0.
+template <bool COLOR>
+__global__ void __launch_bounds__(256) k_map_cast(MapRef m, unsigned n, const double* __restrict__ origin, const float* __restrict__ dir, const float* __restrict__ tmin,
+                                                  const float* __restrict__ tmax, float step, unsigned max_steps, unsigned char* __restrict__ out_status,
+                                                  float* __restrict__ out_t, float* __restrict__ out_normal, unsigned char* __restrict__ out_color,
+                                                  float* __restrict__ out_weight) {
+  MapBrick b = map_brick_none();
+  for (size_t i = (size_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (size_t)gridDim.x * 256u) {
+    const double ox = origin[3 * i], oy = origin[3 * i + 1], oz = origin[3 * i + 2];
+    const float dx = dir[3 * i], dy = dir[3 * i + 1], dz = dir[3 * i + 2];
+    const float t0 = tmin[i], t1 = tmax[i];
+    unsigned status = KF_RAY_MISS;
+    float hit_t = 0.f, nx = 0.f, ny = 0.f, nz = 0.f, hit_w = 0.f;
+    uchar4 hit_c = make_uchar4(0, 0, 0, 0);
+    float last = 0.f;
+    for (unsigned k = 0; k < max_steps; ++k) {
+      const float tk = t0 + (float)k * step;
+      if (!(tk < t1)) break;
+      const double px = ox + (double)(tk * dx), py = oy + (double)(tk * dy), pz = oz + (double)(tk * dz);
+      const float sdf = query_nearest(m, px, py, pz, b);
+      if (last > 0.f && sdf < 0.f) {
+        status = KF_RAY_BROKEN;
+        const float tl = t0 + (float)(k - 1u) * step;
+        QuerySample s0, s1, sh;
+        if (!query_sample<false, false>(m, px, py, pz, b, s1)) break;
+        if (!query_sample<false, false>(m, ox + (double)(tl * dx), oy + (double)(tl * dy), oz + (double)(tl * dz), b, s0)) break;
+        const float alpha = tk - step * s1.tsdf / (s1.tsdf - s0.tsdf);
+        if (!query_sample<true, COLOR>(m, ox + (double)(alpha * dx), oy + (double)(alpha * dy), oz + (double)(alpha * dz), b, sh)) break;
+        const float len = sqrtf((sh.gx * sh.gx + sh.gy * sh.gy) + sh.gz * sh.gz);    // (correctly rounded, like `/`: the compiler's default for HIP)
+        if (!(len >= 1e-8f)) break;
+        status = KF_RAY_HIT;
+        hit_t = alpha; nx = sh.gx / len; ny = sh.gy / len; nz = sh.gz / len; hit_w = sh.weight;
+        if (COLOR) hit_c = sh.color;
+        break;
+      }
+      last = sdf;
+    }
+    if (out_status) out_status[i] = (unsigned char)status;
+    if (out_t) out_t[i] = hit_t;
+    if (out_normal) { out_normal[3 * i] = nx; out_normal[3 * i + 1] = ny; out_normal[3 * i + 2] = nz; }
+    if (out_color) { out_color[4 * i] = hit_c.x; out_color[4 * i + 1] = hit_c.y; out_color[4 * i + 2] = hit_c.z; out_color[4 * i + 3] = 0; }
+    if (out_weight) out_weight[i] = hit_w;
+  }
+}
+
+static inline bool query_whole_volume(const kf_ctx* c) { return c->vol.bz0 == 0 && c->vol.bz1 == c->vol.nb; }   // a z-slab context holds part of a window and no store
+static MapRef query_map(const kf_ctx* c) {
+  MapRef m;
+  m.vol = c->vol; m.st = c->bstore;
+  for (int k = 0; k < 3; ++k) m.ob[k] = c->origin_vox[k] >> 3;      // (a multiple of 8; the shift floors)
+  return m;
+}
+static inline unsigned query_grid(uint32_t n) { const unsigned g = (n + 255u) / 256u; return g > 4096u ? 4096u : g; }
+
+extern "C" int kf_map_sample_device(kf_ctx* c, uint32_t n, const double* dev_pos, float* dev_tsdf, float* dev_weight, float* dev_grad, uint8_t* dev_color) {
+  if (!c || !dev_pos) return KF_ERR_ARG;
+  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (n == 0) return 0;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  const MapRef m = query_map(c);
+  if (c->vol.color && dev_color) hipLaunchKernelGGL(k_map_sample<true>, dim3(query_grid(n)), dim3(256), 0, c->stream, m, n, dev_pos, dev_tsdf, dev_weight, dev_grad, dev_color);
+  else hipLaunchKernelGGL(k_map_sample<false>, dim3(query_grid(n)), dim3(256), 0, c->stream, m, n, dev_pos, dev_tsdf, dev_weight, dev_grad, dev_color);
+  return (int)hipGetLastError();
+}
+
+static inline bool query_cast_args_ok(float step, uint32_t max_steps) { return isfinite(step) && step > 0.f && max_steps >= 1u && max_steps <= KF_QUERY_MAX_STEPS; }
+
+extern "C" int kf_map_cast_rays_device(kf_ctx* c, uint32_t n, const double* dev_origin, const float* dev_dir, const float* dev_tmin, const float* dev_tmax, float step,
+                                       uint32_t max_steps, uint8_t* dev_status, float* dev_t, float* dev_normal, uint8_t* dev_color, float* dev_weight) {
+  if (!c || !dev_origin || !dev_dir || !dev_tmin || !dev_tmax || !query_cast_args_ok(step, max_steps)) return KF_ERR_ARG;
+  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (n == 0) return 0;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  const MapRef m = query_map(c);
+  if (c->vol.color && dev_color)
+    hipLaunchKernelGGL(k_map_cast<true>, dim3(query_grid(n)), dim3(256), 0, c->stream, m, n, dev_origin, dev_dir, dev_tmin, dev_tmax, step, max_steps, dev_status, dev_t,
+                       dev_normal, dev_color, dev_weight);
+  else
+    hipLaunchKernelGGL(k_map_cast<false>, dim3(query_grid(n)), dim3(256), 0, c->stream, m, n, dev_origin, dev_dir, dev_tmin, dev_tmax, step, max_steps, dev_status, dev_t,
+                       dev_normal, dev_color, dev_weight);
+  return (int)hipGetLastError();
+}
+
+// the host forms: one temporary device allocation carved into the arrays (each part a multiple of 16 bytes), copies on the context's stream, one wait
+struct QueryTemp {
+  char* base = nullptr; size_t used = 0, cap = 0;
+  static size_t pad(size_t b) { return (b + 15) & ~(size_t)15; }
+  bool get(size_t bytes) { cap = bytes; if (hipMalloc((void**)&base, bytes) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; } return true; }
+  void* take(size_t bytes) { void* p = base + used; used += pad(bytes); return p; }
+  ~QueryTemp() { if (base) hipFree(base); }
+};
+
+extern "C" int kf_map_sample(kf_ctx* c, uint32_t n, const double* pos, float* tsdf, float* weight, float* grad, uint8_t* color) {
+  if (!c || !pos) return KF_ERR_ARG;
+  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (n == 0) return 0;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  const size_t N = n, b_pos = 24 * N, b_f = 4 * N, b_g = 12 * N, b_c = 4 * N;
+  QueryTemp tmp;
+  if (!tmp.get(QueryTemp::pad(b_pos) + 2 * QueryTemp::pad(b_f) + QueryTemp::pad(b_g) + QueryTemp::pad(b_c))) return KF_ERR_ALLOC;
+  double* d_pos = (double*)tmp.take(b_pos);
+  float* d_t = tsdf ? (float*)tmp.take(b_f) : nullptr;
+  float* d_w = weight ? (float*)tmp.take(b_f) : nullptr;
+  float* d_g = grad ? (float*)tmp.take(b_g) : nullptr;
+  uint8_t* d_c = color ? (uint8_t*)tmp.take(b_c) : nullptr;
+  KF_CHECK(hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, c->stream));
+  int st = kf_map_sample_device(c, n, d_pos, d_t, d_w, d_g, d_c);
+  if (!st && d_t) st = (int)hipMemcpyAsync(tsdf, d_t, b_f, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_w) st = (int)hipMemcpyAsync(weight, d_w, b_f, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_g) st = (int)hipMemcpyAsync(grad, d_g, b_g, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_c) st = (int)hipMemcpyAsync(color, d_c, b_c, hipMemcpyDeviceToHost, c->stream);
+  const int ss = (int)hipStreamSynchronize(c->stream);               // (also after a failure: the temporary is freed below)
+  return st ? st : ss;
+}
+
+extern "C" int kf_map_cast_rays(kf_ctx* c, uint32_t n, const double* origin, const float* dir, const float* tmin, const float* tmax, float step, uint32_t max_steps,
+                                uint8_t* status, float* t, float* normal, uint8_t* color, float* weight) {
+  if (!c || !origin || !dir || !tmin || !tmax || !query_cast_args_ok(step, max_steps)) return KF_ERR_ARG;
+  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (n == 0) return 0;
+  KF_CHECK(hipSetDevice(c->cfg.device));
+  const size_t N = n, b_o = 24 * N, b_d = 12 * N, b_f = 4 * N, b_s = N, b_c = 4 * N;
+  QueryTemp tmp;
+  if (!tmp.get(QueryTemp::pad(b_o) + 2 * QueryTemp::pad(b_d) + 4 * QueryTemp::pad(b_f) + QueryTemp::pad(b_s) + QueryTemp::pad(b_c))) return KF_ERR_ALLOC;
+  double* d_o = (double*)tmp.take(b_o);
+  float* d_d = (float*)tmp.take(b_d);
+  float* d_t0 = (float*)tmp.take(b_f);
+  float* d_t1 = (float*)tmp.take(b_f);
+  uint8_t* d_s = status ? (uint8_t*)tmp.take(b_s) : nullptr;
+  float* d_t = t ? (float*)tmp.take(b_f) : nullptr;
+  float* d_n = normal ? (float*)tmp.take(b_d) : nullptr;
+  uint8_t* d_c = color ? (uint8_t*)tmp.take(b_c) : nullptr;
+  float* d_w = weight ? (float*)tmp.take(b_f) : nullptr;
+  KF_CHECK(hipMemcpyAsync(d_o, origin, b_o, hipMemcpyHostToDevice, c->stream));
+  int st = (int)hipMemcpyAsync(d_d, dir, b_d, hipMemcpyHostToDevice, c->stream);
+  if (!st) st = (int)hipMemcpyAsync(d_t0, tmin, b_f, hipMemcpyHostToDevice, c->stream);
+  if (!st) st = (int)hipMemcpyAsync(d_t1, tmax, b_f, hipMemcpyHostToDevice, c->stream);
+  if (!st) st = kf_map_cast_rays_device(c, n, d_o, d_d, d_t0, d_t1, step, max_steps, d_s, d_t, d_n, d_c, d_w);
+  if (!st && d_s) st = (int)hipMemcpyAsync(status, d_s, b_s, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_t) st = (int)hipMemcpyAsync(t, d_t, b_f, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_n) st = (int)hipMemcpyAsync(normal, d_n, b_d, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_c) st = (int)hipMemcpyAsync(color, d_c, b_c, hipMemcpyDeviceToHost, c->stream);
+  if (!st && d_w) st = (int)hipMemcpyAsync(weight, d_w, b_f, hipMemcpyDeviceToHost, c->stream);
+  const int ss = (int)hipStreamSynchronize(c->stream);
+  return st ? st : ss;
+}

@@ -4,6 +4,7 @@
 #include "png_reader.hpp"
 #include "map_file.hpp"
 #include "erase_box_voxels.hpp"
+#include "map_query_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <string.h>
 
@@ -212,6 +213,22 @@ int hkf_app_erase_map_weak(float min_weight, uint64_t out1[1]) {
 int hkf_erase_map_box_voxels(const float lo_m[3], const float hi_m[3], float cell, int32_t lo_vox[3], int32_t hi_vox[3]) {
   if (!lo_m || !hi_m || !lo_vox || !hi_vox) return -1;
   hkf_erase_box_voxels(lo_m, hi_m, cell, lo_vox, hi_vox);
+  return 0;
+}
+// HybKinectfu::sampleMap / castMapRays (positions, t: WORLD metres): 1 done, 0 refused or failed, -1 without an application.  Any output may be NULL.
+// hkf_map_query_voxels needs no application: count3 coordinates in metres as fp64 voxel positions
+int hkf_app_sample_map(const double* world_m, uint32_t n, float* distance_m, float* weight, float* gradient, uint8_t* color) {
+  if (!g_app) return -1;
+  return g_app->sampleMap(world_m, n, distance_m, weight, gradient, color) ? 1 : 0;
+}
+int hkf_app_cast_map_rays(const double* origin_m, const float* dir, const float* t_min_m, const float* t_max_m, uint32_t n, uint8_t* status, float* t_m, float* normal,
+                          uint8_t* color, float* weight) {
+  if (!g_app) return -1;
+  return g_app->castMapRays(origin_m, dir, t_min_m, t_max_m, n, status, t_m, normal, color, weight) ? 1 : 0;
+}
+int hkf_map_query_voxels(const double* world_m, uint32_t count3, float cell, double* vox) {
+  if (!world_m || !vox) return -1;
+  hkf_query_voxels(world_m, count3, cell, vox);
   return 0;
 }
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }

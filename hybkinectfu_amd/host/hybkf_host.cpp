@@ -4,6 +4,7 @@
 #include "hybkf_host.hpp"
 #include "map_file.hpp"
 #include "erase_box_voxels.hpp"
+#include "map_query_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <math.h>
 #include <string.h>
@@ -730,6 +731,36 @@ bool HybKinectfu::eraseMapWeak(float minWeight, unsigned* bricksRemoved) {
   if (!mergeShow()) return false;
   if (bricksRemoved) *bricksRemoved = removed;
   return es == 0;
+}
+bool HybKinectfu::sampleMap(const double* world_m, size_t n, float* distance_m, float* weight, float* gradient, uint8_t* color) {
+  if (!_inited || !world_m || n > 0xFFFFFFFFull) return false;
+  if (n == 0) return true;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  const float trunc = p->_integrate_params.fSdfTruncation;
+  std::vector<double> vox(3 * n);
+  hkf_query_voxels(world_m, 3 * n, cell, vox.data());
+  if (dm->check(kf_map_sample(dm->ctx(), (uint32_t)n, vox.data(), distance_m, weight, gradient, color))) return false;
+  if (distance_m) for (size_t i = 0; i < n; ++i) distance_m[i] = distance_m[i] * trunc;
+  if (gradient) for (size_t i = 0; i < 3 * n; ++i) gradient[i] = gradient[i] * trunc / cell;
+  return true;
+}
+bool HybKinectfu::castMapRays(const double* origin_m, const float* dir, const float* t_min_m, const float* t_max_m, size_t n, uint8_t* status, float* t_m, float* normal,
+                              uint8_t* color, float* weight) {
+  if (!_inited || !origin_m || !dir || !t_min_m || !t_max_m || n > 0xFFFFFFFFull) return false;
+  if (n == 0) return true;
+  AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  std::vector<double> vox(3 * n);
+  hkf_query_voxels(origin_m, 3 * n, cell, vox.data());
+  std::vector<float> t0(n), t1(n);
+  for (size_t i = 0; i < n; ++i) { t0[i] = t_min_m[i] / cell; t1[i] = t_max_m[i] / cell; }
+  const float step = p->_raycast_params.fRayIncrement / cell;
+  if (dm->check(kf_map_cast_rays(dm->ctx(), (uint32_t)n, vox.data(), dir, t0.data(), t1.data(), step, 1u << 24, status, t_m, normal, color, weight))) return false;
+  if (t_m) for (size_t i = 0; i < n; ++i) t_m[i] = t_m[i] * cell;
+  return true;
 }
 bool HybKinectfu::loadMapCoarser(const std::string& path) {
   if (!_inited) return false;

@@ -342,6 +342,18 @@ public:
   // already streamed into the world soup (setStreamMesh) is not taken back.  bricksRemoved / voxelsCleared (may be nullptr): the call's counts.
   bool eraseMapBox(const float lo_m[3], const float hi_m[3], bool keepInside, unsigned* bricksRemoved = nullptr, uint64_t* voxelsCleared = nullptr);
   bool eraseMapWeak(float minWeight, unsigned* bricksRemoved = nullptr);
+  // sampleMap: the map at n points in WORLD metres (world_m: 3 n doubles, the first cube's coordinates -- those of the map mesh's vertices and of worldPose),
+  // read where it lies, window and store (kf_map_sample): the position in voxels is x / (double)cell (hkf_query_voxels, map_query_voxels.hpp; cell the
+  // fp32 quotient size / resolution).  distance_m: tsdf * fSdfTruncation, the signed distance in metres inside the truncation band (+-fSdfTruncation beyond
+  // it); weight: the least of the eight corners'; gradient (3 n): the distance's gradient, metres per metre, (grad * fSdfTruncation) / cell -- it points out of
+  // the surface; color (4 n bytes).  A point one of whose eight corners was never observed gives zeros.  Any output may be nullptr.
+  // castMapRays: the first surface crossing of n rays (kf_map_cast_rays): origins in world metres, dir (3 n) used as given (unit vectors: t is metres), t_min_m /
+  // t_max_m per ray in metres (divided by cell in fp32), the step fRayIncrement / cell; status (KF_RAY_MISS / _HIT / _BROKEN), t_m = t * cell, the unit normal,
+  // colour and weight of the hit; zeros where there is none.  Any output may be nullptr.
+  // Both only read: nothing of the session changes, no frame is waited for beyond the stream's order.  false: not initialised, a null input, the call failed.
+  bool sampleMap(const double* world_m, size_t n, float* distance_m, float* weight, float* gradient, uint8_t* color);
+  bool castMapRays(const double* origin_m, const float* dir, const float* t_min_m, const float* t_max_m, size_t n, uint8_t* status, float* t_m, float* normal, uint8_t* color,
+                   float* weight);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();

@@ -67,6 +67,8 @@ public:
   bool alignMap(const std::string&, const Mat44&, Mat44&, kf_align_report*) { return false; }
   bool eraseMapBox(const float*, const float*, bool, unsigned* = nullptr, uint64_t* = nullptr) { return false; }
   bool eraseMapWeak(float, unsigned* = nullptr) { return false; }
+  bool sampleMap(const double*, size_t, float*, float*, float*, uint8_t*) { return false; }
+  bool castMapRays(const double*, const float*, const float*, const float*, size_t, uint8_t*, float*, float*, uint8_t*, float*) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

@@ -263,6 +263,40 @@ class App:
         self.erase_counts = (int(out[0]), 0)
         return bool(r)
 
+    def sample_map(self, points):
+        """HybKinectfu::sampleMap: this session's map at points (n, 3) in WORLD metres (the map mesh's coordinates), read where it lies -- window and
+        store.  A dict of numpy arrays: distance (n,) in metres (tsdf * truncation), weight (n,), gradient (n, 3) of the distance per metre, color (n, 4);
+        zeros where one of the point's eight corners was never observed"""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        n = len(pts)
+        out = dict(distance=np.zeros(n, np.float32), weight=np.zeros(n, np.float32), gradient=np.zeros((n, 3), np.float32), color=np.zeros((n, 4), np.uint8))
+        r = self.h.hkf_app_sample_map(K._p(pts), C.c_uint32(n), K._p(out["distance"]), K._p(out["weight"]), K._p(out["gradient"]), K._p(out["color"]))
+        if r < 0:
+            raise K.KfError("hkf_app_sample_map: no application")
+        if r == 0:
+            raise K.KfError("hkf_app_sample_map failed")
+        return out
+
+    def cast_map_rays(self, origins, dirs, t_min, t_max):
+        """HybKinectfu::castMapRays: the first surface crossing of rays through this session's map: origins (n, 3) in WORLD metres, dirs (n, 3) used as
+        given (unit vectors: t is metres), t_min / t_max (n,) or scalars in metres; the march steps by the raycaster's increment.  A dict of numpy arrays:
+        status (n,) (K.RAY_MISS, K.RAY_HIT, K.RAY_BROKEN), t (n,) in metres, normal (n, 3), color (n, 4), weight (n,); zeros where status is not K.RAY_HIT"""
+        org = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+        n = len(org)
+        d = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        assert len(d) == n
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, np.float32), (n,)))
+        t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float32), (n,)))
+        out = dict(status=np.zeros(n, np.uint8), t=np.zeros(n, np.float32), normal=np.zeros((n, 3), np.float32), color=np.zeros((n, 4), np.uint8),
+                   weight=np.zeros(n, np.float32))
+        r = self.h.hkf_app_cast_map_rays(K._p(org), K._p(d), K._p(t0), K._p(t1), C.c_uint32(n), K._p(out["status"]), K._p(out["t"]), K._p(out["normal"]),
+                                         K._p(out["color"]), K._p(out["weight"]))
+        if r < 0:
+            raise K.KfError("hkf_app_cast_map_rays: no application")
+        if r == 0:
+            raise K.KfError("hkf_app_cast_map_rays failed")
+        return out
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -415,6 +449,18 @@ class SlabsApp:
     def erase_map_weak(self, min_weight):
         """always False, nothing touched, as erase_map_box"""
         return self.h.hkf_slabs_erase_map_weak(C.c_float(min_weight), None) > 0
+
+    def sample_map(self, points):
+        """always refused (K.KfError), nothing read: the map queries read window and brick store, which a slab group does not have"""
+        pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
+        r = self.h.hkf_slabs_sample_map(K._p(pts), C.c_uint32(len(pts)), None, None, None, None)
+        raise K.KfError("hkf_slabs_sample_map: slab groups have no map queries (%d)" % r)
+
+    def cast_map_rays(self, origins, dirs, t_min, t_max):
+        """always refused (K.KfError), as sample_map"""
+        org = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+        r = self.h.hkf_slabs_cast_map_rays(K._p(org), None, None, None, C.c_uint32(len(org)), None, None, None, None, None)
+        raise K.KfError("hkf_slabs_cast_map_rays: slab groups have no map queries (%d)" % r)
 
     def close(self):
         self.h.hkf_slabs_shutdown()

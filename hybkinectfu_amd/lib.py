@@ -127,6 +127,7 @@ SYMBOLS = [
     "kf_align_brick_store", "kf_align_step",
     "kf_merge_brick_store_halved", "kf_halved_brick_keys",
     "kf_brick_store_erase_box", "kf_brick_store_erase_weak",
+    "kf_map_sample", "kf_map_sample_device", "kf_map_cast_rays", "kf_map_cast_rays_device",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -187,6 +188,10 @@ def load():
         _lib.kf_halved_brick_keys.restype = C.c_int64
         _lib.kf_brick_store_erase_box.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
         _lib.kf_brick_store_erase_weak.argtypes = [C.c_void_p, C.c_float, C.POINTER(C.c_uint32)]
+        for f in (_lib.kf_map_sample, _lib.kf_map_sample_device):
+            f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
+        for f in (_lib.kf_map_cast_rays, _lib.kf_map_cast_rays_device):
+            f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_uint32] + [C.c_void_p] * 5
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -252,6 +257,7 @@ def halved_brick_keys(keys):
 
 
 ERASE_INSIDE, ERASE_OUTSIDE = 0, 1                                    # kf_brick_store_erase_box: mode
+RAY_MISS, RAY_HIT, RAY_BROKEN = 0, 1, 2                               # kf_map_cast_rays: status
 
 ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_FEW_PAIRS, ALIGN_SINGULAR = 0, 1, 2, 3   # kf_align_report.verdict
 
@@ -924,6 +930,47 @@ class Context:
         removed = C.c_uint32()
         _chk(self.lib.kf_brick_store_erase_weak(self.h, float(min_weight), C.byref(removed)), "kf_brick_store_erase_weak")
         return removed.value
+
+    def map_sample(self, pos, want=("tsdf", "weight", "grad", "color")):
+        """the map at points pos (n, 3), fp64, WORLD VOXEL units (voxel g's centre at g + 0.5), read where it lies -- window first, then the store: a dict
+        of tsdf (n,), weight (n,), grad (n, 3) in tsdf units per voxel and color (n, 4); an unobserved point (one of its eight corners has weight 0) is 0
+        everywhere.  want: which outputs to ask for, the others are passed as NULL (kf_map_sample)"""
+        pos = np.ascontiguousarray(pos, np.float64).reshape(-1, 3)
+        n = len(pos)
+        out = dict(tsdf=np.zeros(n, np.float32), weight=np.zeros(n, np.float32), grad=np.zeros((n, 3), np.float32), color=np.zeros((n, 4), np.uint8))
+        out = {k: v for k, v in out.items() if k in want}
+        a = [_p(out[k]) if k in out else None for k in ("tsdf", "weight", "grad", "color")]
+        _chk(self.lib.kf_map_sample(self.h, n, _p(pos), *a), "kf_map_sample")
+        return out
+
+    def map_sample_device(self, n, dev_pos, dev_tsdf=None, dev_weight=None, dev_grad=None, dev_color=None):
+        """map_sample with device pointers (integers or None), on the context's stream, non-blocking (kf_map_sample_device)"""
+        _chk(self.lib.kf_map_sample_device(self.h, int(n), *[C.c_void_p(x) if x else None for x in (dev_pos, dev_tsdf, dev_weight, dev_grad, dev_color)]),
+             "kf_map_sample_device")
+
+    def map_cast_rays(self, origin, dirs, t_min, t_max, step, max_steps=1 << 24, want=("status", "t", "normal", "color", "weight")):
+        """the first surface crossing of n rays through the map: origin (n, 3) fp64 in world voxels, dirs (n, 3) fp32 used as given, t_min / t_max (n,) or
+        scalars, samples every `step`, at most max_steps of them.  A dict of status (n,) u8 (RAY_MISS, RAY_HIT, RAY_BROKEN), t (n,), normal (n, 3), color
+        (n, 4), weight (n,); zeros where status is not RAY_HIT (kf_map_cast_rays)"""
+        origin = np.ascontiguousarray(origin, np.float64).reshape(-1, 3)
+        n = len(origin)
+        dirs = np.ascontiguousarray(dirs, np.float32).reshape(-1, 3)
+        t0 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_min, np.float32), (n,)))
+        t1 = np.ascontiguousarray(np.broadcast_to(np.asarray(t_max, np.float32), (n,)))
+        assert len(dirs) == n
+        out = dict(status=np.zeros(n, np.uint8), t=np.zeros(n, np.float32), normal=np.zeros((n, 3), np.float32), color=np.zeros((n, 4), np.uint8),
+                   weight=np.zeros(n, np.float32))
+        out = {k: v for k, v in out.items() if k in want}
+        a = [_p(out[k]) if k in out else None for k in ("status", "t", "normal", "color", "weight")]
+        _chk(self.lib.kf_map_cast_rays(self.h, n, _p(origin), _p(dirs), _p(t0), _p(t1), C.c_float(step), int(max_steps), *a), "kf_map_cast_rays")
+        return out
+
+    def map_cast_rays_device(self, n, dev_origin, dev_dir, dev_tmin, dev_tmax, step, max_steps, dev_status=None, dev_t=None, dev_normal=None,
+                             dev_color=None, dev_weight=None):
+        """map_cast_rays with device pointers (integers or None), on the context's stream, non-blocking (kf_map_cast_rays_device)"""
+        ptr = [C.c_void_p(x) if x else None for x in (dev_origin, dev_dir, dev_tmin, dev_tmax, dev_status, dev_t, dev_normal, dev_color, dev_weight)]
+        _chk(self.lib.kf_map_cast_rays_device(self.h, int(n), ptr[0], ptr[1], ptr[2], ptr[3], C.c_float(step), int(max_steps), *ptr[4:]),
+             "kf_map_cast_rays_device")
 
     def refill_window(self):
         """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never

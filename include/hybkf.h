@@ -750,6 +750,42 @@ int kf_merge_brick_store_halved(kf_ctx* ctx, uint32_t count, const int32_t* keys
 int kf_brick_store_erase_box(kf_ctx* ctx, const int32_t lo_vox[3], const int32_t hi_vox[3], int mode, uint32_t* bricks_removed, uint64_t* voxels_cleared);
 int kf_brick_store_erase_weak(kf_ctx* ctx, float min_weight, uint32_t* bricks_removed);
 
+/* Querying the map: distance, gradient, weight and colour at N points; the first surface crossing of N rays (no reference counterpart for the points; the
+ * march is the reference's, raycastingVolume.cu:79-117).  The map is read where it lies -- no resolve table, no window move, no copy -- and nothing of the
+ * context changes: volume, store, deferred-weight words, pose, model maps, scratch and every later frame are bit for bit what they would have been.
+ * The map as a function of a world voxel g (integers, any sign), which lies in world brick g >> 3: a brick inside the window (kf_volume_origin) is the
+ *   window's; else, with a store reserved that holds the key, the store's; else nobody holds it.  Weights are TRUE weights (the deferred-weight word applied,
+ *   what kf_download_volume and kf_read_brick_store report).  A voxel whose true weight is not > 0, or that nobody holds, reads (tsdf 0, weight 0, colour 0).
+ *   Without a store the window alone is the map.
+ * Positions are fp64 in WORLD VOXEL units, voxel g's centre at g + 0.5: the first cube's frame (a map mesh vertex or a world metre divided by the cell).
+ *   fp64, so that a map anywhere in the key range (+-2^23 voxels) is sampled with the same bits as the same map at the origin.
+ * kf_map_sample: per axis u = p - 0.5 (fp64), n = floor(u), f = (float)(u - n) (the difference is exact: one rounding).  The eight voxels n + {0, 1}^3 are
+ *   read, corner k with x from bit 0, y from bit 1, z from bit 2.  One of them reads weight 0: the point is unobserved, every output for it is 0.  Otherwise,
+ *   with lerp(a, b, f) = a + f * (b - a) in fp32, one rounding per operation:
+ *     a0..a3 = lerp(v[2i], v[2i+1], fx);  b0 = lerp(a0, a1, fy), b1 = lerp(a2, a3, fy);  tsdf = lerp(b0, b1, fz);
+ *     grad.x = lerp(lerp(v1-v0, v3-v2, fy), lerp(v5-v4, v7-v6, fy), fz);  grad.y = lerp(a1-a0, a3-a2, fz);  grad.z = b1 - b0   (tsdf units per voxel);
+ *     weight = the least of the eight;  colour = kf_render_view's interpolateColor: corner j (x from bit 2, y from bit 1, z from bit 0) adds
+ *     (float)c * wa * wb * wc in the order j = 0..7, wa = f or 1 - f, the sum truncated; byte 3 is 0.  Colour is 0 on a context without a colour plane.
+ *   There is no |tsdf| < 1 rule: the caller sees the value.  A position that is not finite or lies outside [-2^23, 2^23] reads unobserved.
+ * kf_map_cast_rays: ray i is origin (fp64, world voxels), dir (3 x fp32, used as given: t is in units of |dir| voxels), t_min and t_max.  Sample k is at
+ *   t_k = t_min + (float)k * step, per axis at origin + (double)(t_k * dir): the product in fp32, the sum in fp64.  s_k = the tsdf of the voxel floor(p).
+ *   last = 0; while t_k < t_max and k < max_steps: if last > 0 and s_k < 0 refine and stop, else last = s_k.  Refinement: ft, ftdt = kf_map_sample's tsdf at
+ *   samples k - 1 and k (either unobserved: BROKEN); alpha = t_k - step * ftdt / (ftdt - ft), the division correctly rounded; the hit is kf_map_sample at
+ *   origin + (double)(alpha * dir); len = sqrtf((gx * gx + gy * gy) + gz * gz); the hit unobserved or not len >= 1e-8f: BROKEN; else HIT with t = alpha,
+ *   normal = grad / len (towards growing tsdf: out of the surface), the hit's colour and weight.  status: KF_RAY_MISS, KF_RAY_HIT or KF_RAY_BROKEN (the
+ *   reference's `break` without output); a ray that is not a HIT writes zeros.
+ * The _device forms take device pointers, run on the context's stream and do not block; the others take host pointers: one temporary allocation, copies, and
+ *   they block.  Any output pointer may be NULL.  n == 0 does nothing.  pos / origin: 3 per item; grad / normal / dir: 3 per item; color: 4 bytes per item.
+ * Refused with nothing written -- KF_ERR_ARG: a NULL context, a NULL input array, step not finite or not > 0, max_steps 0 or > 2^24.  KF_ERR_STATE: a z-slab
+ *   context (slab groups have no store and hold part of a window each). */
+#define KF_RAY_MISS 0
+#define KF_RAY_HIT 1
+#define KF_RAY_BROKEN 2
+int kf_map_sample_device(kf_ctx* ctx, uint32_t n, const double* dev_pos, float* dev_tsdf, float* dev_weight, float* dev_grad, uint8_t* dev_color);
+int kf_map_sample(kf_ctx* ctx, uint32_t n, const double* pos, float* tsdf, float* weight, float* grad, uint8_t* color);
+int kf_map_cast_rays_device(kf_ctx* ctx, uint32_t n, const double* dev_origin, const float* dev_dir, const float* dev_tmin, const float* dev_tmax, float step, uint32_t max_steps, uint8_t* dev_status, float* dev_t, float* dev_normal, uint8_t* dev_color, float* dev_weight);
+int kf_map_cast_rays(kf_ctx* ctx, uint32_t n, const double* origin, const float* dir, const float* tmin, const float* tmax, float step, uint32_t max_steps, uint8_t* status, float* t, float* normal, uint8_t* color, float* weight);
+
 /* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
  * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
  * voxels a start 10 degrees and about 5 voxels off still converges; a start much further off finds too few pairs or a wrong minimum.  Coarse-to-fine search
