@@ -540,27 +540,35 @@ __device__ __forceinline__ void store_partial(float acc[27], float* partials_out
 // ---- ICP ------------------------------------------------------------------------------------------------------------
 // findCorrs (:17-60) + buildPointToPlaneSolverRows (:7-16), split so the ICP_PX pixels of a lane overlap their memory round trips:
 // stage A (icp_project) needs only the lane's own vertex/normal and yields the model-map index; stage B (icp_finish)
-// consumes the gathered model vertex/normal.
-__device__ __forceinline__ int icp_project(const TrackArgs& a, const float* cur, const float* linv, float4 iv, float4 in_,
-                                           float4& vg, float4& ng) {
-  if (kf_is_zero4(in_)) return -1;
+// consumes the gathered model vertex/normal.  Both are straight-line code: every gate is a boolean, there is no early exit.  A pixel
+// without a correspondence gets index 0 and `false`; its projection is computed all the same (vcp.z may be zero, tiny or negative:
+// kf_project's two `/` and the saturating conversion give a number for every input, NaN included, and the bounds test judges it).
+__device__ __forceinline__ bool icp_project(const TrackArgs& a, const float* cur, const float* linv, float4 iv, float4 in_,
+                                            float4& vg, float4& ng, int& mi) {
+  const bool own = !kf_is_zero4(in_);
   vg = kf_mat_vec(cur, iv);
   ng = kf_mat_vec(cur, in_);
   const float4 vcp = kf_mat_vec(linv, vg);
   const int2 sp = kf_project(kf3(vcp.x, vcp.y, vcp.z), a.cam);
-  if (sp.x < 0 || sp.x >= a.cam.cols || sp.y < 0 || sp.y >= a.cam.rows) return -1;
-  return sp.y * a.cam.cols + sp.x;
+  const bool in_x = (sp.x >= 0) & (sp.x < a.cam.cols), in_y = (sp.y >= 0) & (sp.y < a.cam.rows);
+  const bool ok = own & in_x & in_y;
+  mi = ok ? (int)((unsigned)sp.y * (unsigned)a.cam.cols + (unsigned)sp.x) : 0;   // (unsigned: a saturated row's product wraps and is dropped)
+  return ok;
 }
-__device__ __forceinline__ bool icp_finish(const TrackArgs& a, float4 vg, float4 ng, float4 vt, float4 nt, float row[7]) {
-  if (kf_is_zero4(nt)) return false;
+// the gates on the gathered model entry, as ONE predicate computed from nt and vt without a branch -- every loaded value has an unconditional
+// use, so no load can be moved under a condition -- each with the comparison sense of the reference: `x > t` rejects, a NaN passes
+__device__ __forceinline__ bool icp_finish(const TrackArgs& a, float4 vg, float4 ng, float4 vt, float4 nt) {
+  const bool has_n = !kf_is_zero4(nt);
   // `norm(p - q) > dist || norm(n_tgt x n_in) > sin` (CalPointToPlaneErrSolverParams.cu:52) on the squares: two square roots fewer per pixel
   const float3 dv = kf3(vt.x - vg.x, vt.y - vg.y, vt.z - vg.z), cr = kf_cross(kf3(nt.x, nt.y, nt.z), kf3(ng.x, ng.y, ng.z));
-  if (kf_dot(dv, dv) > a.th.dist_thres2 || kf_dot(cr, cr) > a.th.sin_thres2) return false;
+  const bool far = kf_dot(dv, dv) > a.th.dist_thres2, steep = kf_dot(cr, cr) > a.th.sin_thres2;
+  return has_n & !far & !steep;
+}
+__device__ __forceinline__ void icp_row(float4 vg, float4 vt, float4 nt, float row[7]) {
   const float3 p = kf3(vt.x, vt.y, vt.z), q = kf3(vg.x, vg.y, vg.z), n = kf3(nt.x, nt.y, nt.z);
   row[0] = q.y * n.z - q.z * n.y; row[1] = q.z * n.x - q.x * n.z; row[2] = q.x * n.y - q.y * n.x;
   row[3] = n.x; row[4] = n.y; row[5] = n.z;
   row[6] = kf_dot(n, kf_sub(p, q));
-  return true;
 }
 
 // ICP_THREADS, ICP_PX, icp_level_geometry (pixels per lane and publishers of a level) and the fold's slot rule: shared with the host's test program
@@ -572,32 +580,49 @@ __device__ __forceinline__ int icp_dealt_pixel_of(int j, int grid_l, int wg) {
   return (((int)(threadIdx.x >> 6) * grid_l + wg) + j * ((ICP_THREADS / 64) * grid_l)) * 64 + (int)(threadIdx.x & 63);
 }
 __device__ __forceinline__ int icp_dealt_pixel(int j, int grid_l) { return icp_dealt_pixel_of(j, grid_l, (int)blockIdx.x); }
-// one Gauss-Newton step's pixel phase for this lane's (up to ICP_PX) pixels: correspondences + the 27 products, fused accumulation
-__device__ __forceinline__ void icp_accumulate(const TrackArgs& a, const float* s_cur, const float* s_linv, const float4 iv[ICP_PX], const float4 in_[ICP_PX],
-                                               const float4* __restrict__ model_v, const float4* __restrict__ model_n, float acc[27]) {
-  float4 vg[ICP_PX], ng[ICP_PX], vt[ICP_PX], nt[ICP_PX]; int mi[ICP_PX];
+// The 27 sums of a lane, declared as `IcpSums sums; float* acc = sums.v;`.  The struct is the point: a plain local `float acc[27]` is turned into ONE
+// <27 x float> value before anything is inlined or unrolled (the back end's promotion of private arrays to vectors), it then lives in a 32-register
+// tuple, and every merge point of a branch copies or shifts the whole tuple -- 16-deep v_mov_b64 ladders, blocks of 27 re-zeroing moves, 163 moves in
+// the pixel phase.  A struct member is left alone and splits into 27 scalars, which an exec-masked region updates in place.
+struct IcpSums { float v[27]; };
+// one Gauss-Newton step's pixel phase for this lane's NPX pixels: correspondences + the 27 products, fused accumulation; acc is written, not added to.
+// Straight-line up to the products: NPX projections (the running transform is read from LDS once for all of them), then the 2 x NPX model-map
+// gathers, all of them ahead of the first wait -- a pixel without a correspondence reads entry 0 and drops it --, then each pixel's gates as one
+// boolean and its 27 fused multiply-adds under that one predicate, in place, pixels in the order j = 0, 1, 2.  What this form is written against (the
+// listing showed each): a load whose only uses are conditional gets sunk under the condition, and with it a wait of its own -- the first pixel's
+// normal, a wait, the zero test, then its vertex and a second wait: two dependent round trips per step; an early `continue` / `return false` around
+// the sums multiplies the merge points.  (profiles/icp_pixel_gates.txt)
+template <int NPX>
+__device__ __forceinline__ void icp_accumulate_px(const TrackArgs& a, const float* s_cur, const float* s_linv, const float4 iv[ICP_PX], const float4 in_[ICP_PX],
+                                                  const float4* __restrict__ model_v, const float4* __restrict__ model_n, float acc[27]) {
+  float4 vg[NPX], ng[NPX], vt[NPX], nt[NPX]; int mi[NPX]; bool ok[NPX];
 #pragma unroll
-  for (int j = 0; j < ICP_PX; ++j) mi[j] = icp_project(a, s_cur, s_linv, iv[j], in_[j], vg[j], ng[j]);
-  // the model-map gathers of all pixels go out together: no branch around them (a pixel without a correspondence reads entry 0 and
-  // is dropped below) -- behind a conditional load the compiler parks a register copy and with it a wait, and the ICP_PX gathers
-  // became ICP_PX dependent round trips per Gauss-Newton step
-#ifndef KF_ICP_COND_GATHER
+  for (int j = 0; j < NPX; ++j) ok[j] = icp_project(a, s_cur, s_linv, iv[j], in_[j], vg[j], ng[j], mi[j]);
 #pragma unroll
-  for (int j = 0; j < ICP_PX; ++j) { const int g = mi[j] >= 0 ? mi[j] : 0; nt[j] = model_n[g]; vt[j] = model_v[g]; }
-#else
+  for (int j = 0; j < NPX; ++j) { nt[j] = model_n[mi[j]]; vt[j] = model_v[mi[j]]; }
 #pragma unroll
-  for (int j = 0; j < ICP_PX; ++j) { nt[j] = make_float4(0.f, 0.f, 0.f, 0.f); vt[j] = nt[j]; if (mi[j] >= 0) { nt[j] = model_n[mi[j]]; vt[j] = model_v[mi[j]]; } }
-#endif
+  for (int j = 0; j < NPX; ++j) ok[j] = ok[j] & icp_finish(a, vg[j], ng[j], vt[j], nt[j]);
 #pragma unroll
-  for (int j = 0; j < ICP_PX; ++j) {
-    float row[7];
-    if (mi[j] < 0 || !icp_finish(a, vg[j], ng[j], vt[j], nt[j], row)) continue;
-    int s = 0;
+  for (int k = 0; k < 27; ++k) acc[k] = 0.f;
 #pragma unroll
-    for (int r = 0; r < 6; ++r)
+  for (int j = 0; j < NPX; ++j) {
+    if (ok[j]) {                                                           // a rejected pixel leaves every sum untouched (exec mask): its data may hold NaN / Inf
+      float row[7];
+      icp_row(vg[j], vt[j], nt[j], row);
+      int s = 0;
 #pragma unroll
-      for (int c = r; c < 7; ++c) { acc[s] = __builtin_fmaf(row[r], row[c], acc[s]); ++s; }   // :92-105 packing; fused multiply-add: half the instructions, the better rounding (the sums are tolerance-checked)
+      for (int r = 0; r < 6; ++r)
+#pragma unroll
+        for (int c = r; c < 7; ++c) { acc[s] = __builtin_fmaf(row[r], row[c], acc[s]); ++s; }   // :92-105 packing; fused multiply-add: half the instructions, the better rounding (the sums are tolerance-checked)
+    }
   }
+}
+// px_n: how many of the lane's ICP_PX pixels the level deals (wave-uniform: icp_level_geometry; the others are zeros, which every gate rejects).  The coarse
+// levels deal one: their steps run the one-pixel instantiation and neither project nor gather for the two empty slots.
+__device__ __forceinline__ void icp_accumulate(const TrackArgs& a, const float* s_cur, const float* s_linv, const float4 iv[ICP_PX], const float4 in_[ICP_PX],
+                                               const float4* __restrict__ model_v, const float4* __restrict__ model_n, float acc[27], int px_n) {
+  if (px_n == 1) icp_accumulate_px<1>(a, s_cur, s_linv, iv, in_, model_v, model_n, acc);
+  else icp_accumulate_px<ICP_PX>(a, s_cur, s_linv, iv, in_, model_v, model_n, acc);
 }
 // workgroup total of the 27 sums (512 lanes): 16-lane row totals by DPP, one LDS word per (sum, row), then 4 lanes per sum add 8 row
 // totals each and two DPP shifts combine the four partial chains (fixed order).  Returns true on the one lane that ends up holding
@@ -638,10 +663,8 @@ __global__ void __launch_bounds__(ICP_THREADS) k_icp_step(TrackArgs a) {
     if ((a.px_l == 0 || j < a.px_l) && i < npx) { iv[j] = a.new_v[i]; in_[j] = a.new_n[i]; }
   }
   if (!step_prologue(a, s_cur, s_linv, s_tot, &s_code)) return;
-  float acc[27];
-#pragma unroll
-  for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-  icp_accumulate(a, s_cur, s_linv, iv, in_, a.model_v, a.model_n, acc);
+  IcpSums sums; float* acc = sums.v;
+  icp_accumulate(a, s_cur, s_linv, iv, in_, a.model_v, a.model_n, acc, a.px_l > 0 ? a.px_l : ICP_PX);
   int k; float sw;
   if (icp_wg_reduce(acc, s_wave, k, sw)) a.partials[(size_t)(a.step & 1) * KF_ICP_MAX_WG * 32 + blockIdx.x * 32 + k] = sw;
 }
@@ -1069,10 +1092,8 @@ __device__ __forceinline__ void icp_publish(const IcpLoopArgs& L, const TrackArg
 #pragma unroll
     for (int j = 0; j < ICP_PX; ++j) { iv[j] = ivn[j]; in_[j] = inn[j]; }
     if (w + L.n_loop < grid_l) icp_load_pixels(L.new_v[l], L.new_n[l], w + L.n_loop, grid_l, px_l, npx, ivn, inn);
-    float acc[27];
-#pragma unroll
-    for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-    icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
+    IcpSums sums; float* acc = sums.v;
+    icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc, px_l);
     int k; float sw;
     const bool holder = icp_wg_reduce(acc, s_wave, k, sw);
     if (holder) gsum = (w == g) ? sw : gsum + sw;
@@ -1168,10 +1189,8 @@ __device__ __forceinline__ LoopOutcome icp_loop_steps(const IcpLoopArgs& L, Trac
         o.n_pub = grid_l < L.n_loop ? grid_l : L.n_loop;
       } else {
         if ((int)blockIdx.x < grid_l) {
-          float acc[27];
-#pragma unroll
-          for (int k = 0; k < 27; ++k) acc[k] = 0.f;
-          icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc);
+          IcpSums sums; float* acc = sums.v;
+          icp_accumulate(a, s_cur, s_linv, iv, in_, L.model_v[l], L.model_n[l], acc, px_l);
           KF_STAMP(3);
 #ifdef KF_EXPERIMENTS
           if (KF_EXP_MODE(L) == 9 && blockIdx.x == 5 && (threadIdx.x & 63) == 0)     // per-wave: pixel phase done (workgroup 5)
