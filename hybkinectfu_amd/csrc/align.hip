@@ -1,10 +1,10 @@
 // align.hip -- aligning two maps: the rigid transform a map merge needs, found by Gauss-Newton on the SDF-to-SDF error between the brick store and an
 // incoming map.  No reference counterpart.  The rule is written out above kf_align_brick_store in include/hybkf.h; one evaluation of the 29 sums is the
-// kernel below, the step from the sums to the next transform is align_step.h (host, fp64), the source's hash table and a brick's base corner are rigid_keys.h.
+// kernel below, the step from the sums to the next transform is align_step.h (host, fp64), the source keys' check and table and a brick's base corner are
+// rigid_keys.h, the source's upload, its 27 bricks around a held one and a corner's fetch are the rigid merge's (resample_shared.h).
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"
-#include "brick_keys_unique.h"
 #include "rigid_keys.h"
 #include "resample_shared.h"
 #include "align_step.h"
@@ -20,29 +20,19 @@ struct KfAlignXf { double m[12]; double c[3]; };
 
 // One held voxel in the band: td its tsdf, (ux, uy, uz) its source position relative to the brick's base corner (ibx, iby, ibz), (xx, xy, xz) its position
 // relative to the centre.  All eight corners floor(u) + {0, 1}^3 are read; one that the source does not hold, whose weight is not > 0 or whose |tsdf| is
-// not < 1 leaves the voxel out.  s_src: the 27 source slots of bricks (b0x.., b0y.., b0z..) + [0, 3)^3, as in k_store_resample_merge (a corner outside
-// them reads as not held: the caller's bound shows that none lies outside).  Adds the voxel's 28 exact products to acc in fp64 and 1 to n.
+// not < 1 leaves the voxel out.  s_src, (b0x, b0y, b0z): source_bricks27's.  Adds the voxel's 28 exact products to acc in fp64 and 1 to n.
 __device__ __forceinline__ void align_voxel(const KfResampleSource& src, const unsigned* s_src, float td, float ux, float uy, float uz, int ibx, int iby, int ibz,
                                             int b0x, int b0y, int b0z, float xx, float xy, float xz, float r00, float r01, float r02, float r10, float r11,
                                             float r12, float r20, float r21, float r22, double (&acc)[28], unsigned& n) {
-  const float nx = floorf(ux), ny = floorf(uy), nz = floorf(uz);
-  const float fx = ux - nx, fy = uy - ny, fz = uz - nz;
-  const int ix = ibx + (int)nx, iy = iby + (int)ny, iz = ibz + (int)nz;
+  float fx, fy, fz;
+  const int ix = source_split(ux, ibx, fx), iy = source_split(uy, iby, fy), iz = source_split(uz, ibz, fz);
   float v[8];
   bool ok = true;
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
-    const int x = ix + (k & 1), y = iy + ((k >> 1) & 1), z = iz + (k >> 2);
-    const unsigned tx = (unsigned)((x >> 3) - b0x), ty = (unsigned)((y >> 3) - b0y), tz = (unsigned)((z >> 3) - b0z);
-    const unsigned slot = (ok && tx < 3u && ty < 3u && tz < 3u) ? s_src[(tz * 3u + ty) * 3u + tx] : KF_BRICK_NO_SLOT;
-    float w = 0.f;
-    v[k] = 0.f;
-    if (slot != KF_BRICK_NO_SLOT) {
-      const size_t o = (size_t)slot * KF_BRICK_VOX + (size_t)(((z & 7) << 6) | ((y & 7) << 3) | (x & 7));
-      w = src.weight[o];
-      v[k] = src.tsdf[o];
-    }
-    ok = ok && w > 0.f && fabsf(v[k]) < 1.f;
+    const KfSourceCorner c = source_corner(src, s_src, ix + (k & 1), iy + ((k >> 1) & 1), iz + (k >> 2), b0x, b0y, b0z, ok);
+    v[k] = c.t;
+    ok = ok && c.w > 0.f && fabsf(c.t) < 1.f;
   }
   if (!ok) return;
   // the value: x, then y, then z; the gradient in source voxels from the same eight values
@@ -71,8 +61,7 @@ __device__ __forceinline__ void align_voxel(const KfResampleSource& src, const u
 // The sums of one evaluation for kf_align_brick_store.  One workgroup iteration per held slot, 256 lanes x 2 x-adjacent voxels (the slot's float4); the
 // slots are read only.  order: the held slots by ascending key, so which workgroup adds which brick, and when, depends on the keys held and not on the slots
 // they happened to claim.  Per slot: its key, the base corner ib / fb by kf_rigid_brick_base's formula in fp64 (the same operations in the same order, no
-// contraction: the host function's bits; a corner that does not fit 31 bits leaves the slot out), the 27 source slots looked up by the first 27 lanes as in
-// k_store_resample_merge (its bound on the source range of one brick applies word for word: the same u, the same corners).
+// contraction: the host function's bits; a corner that does not fit 31 bits leaves the slot out), the 27 source slots by source_bricks27.
 // One barrier per iteration: the lanes OR two bits into a flags word -- the source holds one of the 27; a held voxel lies in the band -- and the workgroup
 // goes on only with both.  The word is one of three in rotation (the one used two iterations later is cleared after this iteration's barrier, which every
 // lane has passed before it can write to it), the 27 slots one of two sets (a lane can write the other set while a slower one still reads this one, and
@@ -116,17 +105,8 @@ __global__ void __launch_bounds__(256) k_store_align_sums(KfBrickStore st, KfBri
     const float xbx = (float)(q0 - xf.c[0]), xby = (float)(q1 - xf.c[1]), xbz = (float)(q2 - xf.c[2]);
     const float4 h = reinterpret_cast<const float4*>(st.tw + (size_t)slot * KF_BRICK_VOX)[threadIdx.x];
     const bool in0 = h.y > 0.f && fabsf(h.x) < 1.f, in1 = h.w > 0.f && fabsf(h.z) < 1.f;
-    const int b0x = (ib[0] + (int)floorf(((least7(r00) + least7(r10)) + least7(r20)) + fb[0] - 0.01f)) >> 3;
-    const int b0y = (ib[1] + (int)floorf(((least7(r01) + least7(r11)) + least7(r21)) + fb[1] - 0.01f)) >> 3;
-    const int b0z = (ib[2] + (int)floorf(((least7(r02) + least7(r12)) + least7(r22)) + fb[2] - 0.01f)) >> 3;
-    bool any = false;
-    if (threadIdx.x < 27u) {
-      const int bx = b0x + (int)(threadIdx.x % 3u), by = b0y + (int)((threadIdx.x / 3u) % 3u), bz = b0z + (int)(threadIdx.x / 9u);
-      unsigned s = KF_BRICK_NO_SLOT;                                          // (a brick outside the key range has no key: packed, it would alias another)
-      if (fit && kf_brick_key_in_range(bx) && kf_brick_key_in_range(by) && kf_brick_key_in_range(bz)) s = store_find(stab, kf_brick_key_pack(bx, by, bz));
-      s_src[par][threadIdx.x] = s;
-      any = s != KF_BRICK_NO_SLOT;
-    }
+    int b0x, b0y, b0z;
+    const bool any = source_bricks27(stab, fit, ib[0], ib[1], ib[2], fb[0], fb[1], fb[2], r00, r01, r02, r10, r11, r12, r20, r21, r22, b0x, b0y, b0z, s_src[par]);
     const unsigned bits = (__ballot(any) ? 1u : 0u) | (__ballot(fit && (in0 || in1)) ? 2u : 0u);   // (wave-uniform)
     if ((threadIdx.x & 63u) == 0u && bits) atomicOr(&s_flag[tri], bits);
     __syncthreads();
@@ -187,13 +167,7 @@ extern "C" int kf_align_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
   std::vector<unsigned> order;
   uint32_t mask = 0, held = 0;
   try {                                                      // (no exception crosses the C boundary)
-    std::vector<unsigned long long> packed(count);
-    for (uint32_t i = 0; i < count; ++i) {
-      for (int k = 0; k < 3; ++k) if (!kf_brick_key_in_range(keys[3 * (size_t)i + k])) return KF_ERR_ARG;
-      packed[i] = kf_brick_key_pack(keys[3 * (size_t)i], keys[3 * (size_t)i + 1], keys[3 * (size_t)i + 2]);
-    }
-    if (!kf_brick_keys_unique(packed.data(), packed.size())) return KF_ERR_ARG;
-    mask = kf_rigid_source_table(count, keys, tkey, tslot);
+    if (!kf_source_keys_table(count, keys, tkey, tslot, mask)) return KF_ERR_ARG;
     rows.resize((size_t)KF_ALIGN_MAX_GROUPS * KF_ALIGN_SUMS);
   } catch (const std::bad_alloc&) { return KF_ERR_ALLOC; }
   KF_CHECK(hipSetDevice(c->cfg.device));
@@ -207,33 +181,20 @@ extern "C" int kf_align_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
     for (uint32_t i = 0; i < held; ++i) order[i] = i;
     std::sort(order.begin(), order.end(), [&](unsigned a, unsigned b) { return hkeys[a] < hkeys[b]; });
   }
-  const size_t vox = (size_t)count * KF_BRICK_VOX;
   KfResampleTemp tmp;
-  float *dt = nullptr, *dw = nullptr;
-  unsigned long long* dtkey = nullptr;
-  unsigned* dtslot = nullptr;
   double* drows = nullptr;
   unsigned* dorder = nullptr;
-  if (!tmp.get((void**)&dt, vox * sizeof(float)) || !tmp.get((void**)&dw, vox * sizeof(float)) ||
-      !tmp.get((void**)&dtkey, tkey.size() * sizeof(unsigned long long)) || !tmp.get((void**)&dtslot, tslot.size() * sizeof(unsigned)) ||
-      !tmp.get((void**)&drows, (size_t)KF_ALIGN_MAX_GROUPS * KF_ALIGN_SUMS * sizeof(double)) || !tmp.get((void**)&dorder, (size_t)held * sizeof(unsigned)))
+  KfBrickStore stab;
+  KfResampleSource src;
+  hipError_t e;
+  if (!tmp.get((void**)&drows, (size_t)KF_ALIGN_MAX_GROUPS * KF_ALIGN_SUMS * sizeof(double)) || !tmp.get((void**)&dorder, (size_t)held * sizeof(unsigned)) ||
+      !kf_source_map_upload(c, tmp, count, tsdf, weight, nullptr, tkey, tslot, mask, stab, src, e))   // the source goes up once, without its colour
     return KF_ERR_ALLOC;                                     // nothing touched
-  // the source goes up once
-  hipError_t e = hipSuccess;
-  if (count) {
-    e = hipMemcpyAsync(dt, tsdf, vox * sizeof(float), hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dw, weight, vox * sizeof(float), hipMemcpyHostToDevice, c->stream);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(dtkey, tkey.data(), tkey.size() * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(dtslot, tslot.data(), tslot.size() * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
   if (e == hipSuccess && held) e = hipMemcpyAsync(dorder, order.data(), (size_t)held * sizeof(unsigned), hipMemcpyHostToDevice, c->stream);
   {
     const hipError_t se = hipStreamSynchronize(c->stream);   // on success and on failure alike: nothing still reads the caller's arrays
     if (e != hipSuccess || se != hipSuccess) return (int)(e != hipSuccess ? e : se);
   }
-  KfBrickStore stab = KfBrickStore{};
-  stab.tkey = dtkey; stab.tslot = dtslot; stab.max_bricks = count; stab.mask = mask;
-  const KfResampleSource src = {dt, dw, nullptr};
   kf_align_report rep;
   memset(&rep, 0, sizeof(rep));
   double cur[12], good[12];

@@ -123,70 +123,29 @@ __global__ void __launch_bounds__(256) k_store_import(KfBrickStore st, unsigned 
     if (slot == KF_BRICK_NO_SLOT) continue;
     reinterpret_cast<float4*>(st.tw + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_float4(t.x, w.x, t.y, w.y);
     if (COLOR) {                                                              // the store has a colour plane; no colour given (kernel-uniform): zeros, never stale bytes
-      unsigned a = 0u, b = 0u, c = 0u;
-      if (color) {
-        const unsigned short* cs = reinterpret_cast<const unsigned short*>(color + 3 * o) + 3u * threadIdx.x;
-        a = cs[0]; b = cs[1]; c = cs[2];                                      // the bytes of two voxels: c0 c1 | c2 c0' | c1' c2'
-      }
-      reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_uint2(a | ((b & 255u) << 16), (b >> 8) | (c << 8));
+      unsigned c0, c1;
+      staged_colors(color, o, c0, c1);
+      reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_uint2(c0, c1);
     }
     if (threadIdx.x == 0) { st.pend[slot] = 0ull; st.key[slot] = key; }
   }
 }
 
-// (store_claim and the voxel rule of a merge -- merge_voxel, merge_color -- are shared with resample.hip: store_merge.h)
-// Merge for kf_merge_brick_store: k_store_import's shape and staging layout, the keys translated by (ox, oy, oz) bricks.  Thread 0 looks the key up; a key
-// the store does not hold claims a slot and is written as k_store_import writes it, bit for bit.  A held slot is read, merged voxel by voxel and written
-// back in place: each lane the two voxels it loaded, the held weight being the TRUE weight (the slot's deferred-weight word applied as k_store_export
-// applies it; a lane's two voxels lie in quarter threadIdx.x >> 6).  Every weight written is a true weight, so the word becomes 0.  Thread 0 reads the
-// word before the barrier and is the only one to write it, and every key occurs once per launch: no two workgroups, and no two lanes, meet in a slot.
+// Merge for kf_merge_brick_store: k_store_import's shape and staging layout, the keys translated by (ox, oy, oz) bricks; what a lane has loaded -- two voxels
+// and, where given, their colours -- meets the store under store_merge_pair (store_merge.h), which k_store_resample_merge and k_store_halve end in too.
 template <bool COLOR>
 __global__ void __launch_bounds__(256) k_store_merge(KfBrickStore st, unsigned count, const int32_t* __restrict__ keys, const float* __restrict__ tsdf,
                                                      const float* __restrict__ weight, const unsigned char* __restrict__ color, int ox, int oy, int oz,
                                                      float max_weight) {
-  __shared__ unsigned s_slot, s_fresh;
-  __shared__ unsigned long long s_pend;
+  __shared__ KfMergeShared sh;
   for (unsigned e = blockIdx.x; e < count; e += gridDim.x) {
     const size_t o = (size_t)e * KF_BRICK_VOX;
     const float2 t = reinterpret_cast<const float2*>(tsdf + o)[threadIdx.x];
     const float2 w = reinterpret_cast<const float2*>(weight + o)[threadIdx.x];
-    if (!__syncthreads_or(w.x > 0.f || w.y > 0.f)) continue;                  // (workgroup-uniform) never observed: takes no slot, changes no held one
-    const unsigned long long key = kf_brick_key_pack(keys[3 * e] + ox, keys[3 * e + 1] + oy, keys[3 * e + 2] + oz);
-    if (threadIdx.x == 0) {                                                   // everybody has read the last iteration's words: the barrier above
-      unsigned slot = store_find(st, key);
-      const bool fresh = slot == KF_BRICK_NO_SLOT;
-      if (fresh) slot = store_claim(st, key);
-      s_slot = slot; s_fresh = fresh ? 1u : 0u;
-      s_pend = fresh ? 0ull : st.pend[slot];
-    }
-    __syncthreads();
-    const unsigned slot = s_slot;
-    if (slot == KF_BRICK_NO_SLOT) continue;                                   // the store is full: counted as dropped
     unsigned cb0 = 0u, cb1 = 0u;                                              // the incoming colours of the lane's two voxels, packed
-    if (COLOR && color) {
-      const unsigned short* cs = reinterpret_cast<const unsigned short*>(color + 3 * o) + 3u * threadIdx.x;
-      const unsigned a = cs[0], b = cs[1], c = cs[2];                         // the bytes of two voxels: c0 c1 | c2 c0' | c1' c2'
-      cb0 = a | ((b & 255u) << 16); cb1 = (b >> 8) | (c << 8);
-    }
-    float4* tw = reinterpret_cast<float4*>(st.tw + (size_t)slot * KF_BRICK_VOX) + threadIdx.x;
-    if (s_fresh) {                                                            // (workgroup-uniform) k_store_import's write
-      *tw = make_float4(t.x, w.x, t.y, w.y);
-      if (COLOR) reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX)[threadIdx.x] = make_uint2(cb0, cb1);
-      if (threadIdx.x == 0) { st.pend[slot] = 0ull; st.key[slot] = key; }
-      continue;
-    }
-    const unsigned pq = (unsigned)(s_pend >> (16u * (threadIdx.x >> 6))) & 0xFFFFu;   // (wave-uniform)
-    const float4 h = *tw;
-    const float wa0 = kf_pend_weight(h.y, pq, max_weight), wa1 = kf_pend_weight(h.w, pq, max_weight);
-    const bool blend0 = w.x > 0.f && wa0 > 0.f, take0 = w.x > 0.f && !(wa0 > 0.f), blend1 = w.y > 0.f && wa1 > 0.f, take1 = w.y > 0.f && !(wa1 > 0.f);
-    const float2 r0 = merge_voxel(h.x, wa0, t.x, w.x, max_weight, take0, blend0), r1 = merge_voxel(h.z, wa1, t.y, w.y, max_weight, take1, blend1);
-    *tw = make_float4(r0.x, r0.y, r1.x, r1.y);
-    if (COLOR && color) {                                                     // no colour given (kernel-uniform): the held colour stays
-      uint2* cp = reinterpret_cast<uint2*>(st.color + (size_t)slot * KF_BRICK_VOX) + threadIdx.x;
-      const uint2 ca = *cp;
-      *cp = make_uint2(merge_color(ca.x, wa0, cb0, w.x, take0, blend0), merge_color(ca.y, wa1, cb1, w.y, take1, blend1));
-    }
-    if (threadIdx.x == 0) st.pend[slot] = 0ull;                               // (st.key[slot] stays)
+    if (COLOR) staged_colors(color, o, cb0, cb1);
+    const KfIncoming v0 = {t.x, w.x, cb0}, v1 = {t.y, w.y, cb1};
+    store_merge_pair<COLOR>(st, kf_brick_key_pack(keys[3 * e] + ox, keys[3 * e + 1] + oy, keys[3 * e + 2] + oz), v0, v1, color != nullptr, max_weight, sh);
   }
 }
 

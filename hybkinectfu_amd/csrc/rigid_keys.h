@@ -1,5 +1,6 @@
 // rigid_keys.h -- the host side of merging a map under a rigid transform (resample.hip, kf_merge_brick_store_rigid; no reference counterpart): is the
-// transform one, which destination bricks can a source map reach, and where does a destination brick's corner voxel lie in the source.  Plain host C++,
+// transform one, which destination bricks can a source map reach, and where does a destination brick's corner voxel lie in the source; and what every entry
+// point that reads a source map through a table of its own (resample.hip, halve.hip, align.hip) asks of the map's keys: kf_source_keys_table.  Plain host C++,
 // fp64: the library and the stand-alone test program (tests/map_resample_main.cpp) both include it.
 //
 // xf is a row-major 3x4 [R | t]: source world -> destination world, in voxels.  World voxel g has its centre at g + 1/2, so a source position s (voxel
@@ -10,6 +11,7 @@
 #include <algorithm>
 #include <vector>
 #include "brick_key.h"
+#include "brick_keys_unique.h"
 
 #define KF_RIGID_ORTHO_TOL 1e-5      // max |R^T R - I|: a rotation stored in fp32 is orthonormal to a few 1e-7; the rest is room for an accumulated pose
 
@@ -95,6 +97,20 @@ static inline uint32_t kf_rigid_source_table(uint32_t count, const int32_t* keys
     tkey[h] = key; tslot[h] = e;
   }
   return mask;
+}
+// What every entry point that takes a source map asks of its keys before anything is touched (kf_merge_brick_store_rigid, kf_merge_brick_store_halved,
+// kf_align_brick_store): every component in the key range, every brick named once; then the table above.  False -- the callers' KF_ERR_ARG, which this plain
+// header does not see -- leaves tkey, tslot and mask as they were.  (A std::bad_alloc reaches the caller's try.)
+static inline bool kf_source_keys_table(uint32_t count, const int32_t* keys, std::vector<unsigned long long>& tkey, std::vector<unsigned>& tslot, uint32_t& mask) {
+  std::vector<unsigned long long> packed(count);
+  for (uint32_t i = 0; i < count; ++i) {
+    const int32_t* k = keys + 3 * (size_t)i;
+    for (int j = 0; j < 3; ++j) if (!kf_brick_key_in_range(k[j])) return false;
+    packed[i] = kf_brick_key_pack(k[0], k[1], k[2]);
+  }
+  if (!kf_brick_keys_unique(packed.data(), packed.size())) return false;
+  mask = kf_rigid_source_table(count, keys, tkey, tslot);
+  return true;
 }
 
 static inline void kf_rigid_word_key(uint64_t w, int32_t out[3]) {

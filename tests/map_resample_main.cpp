@@ -1,6 +1,6 @@
 // map_resample_main.cpp -- CPU check of the host side of a map merge under a rigid transform (csrc/rigid_keys.h: kf_rigid_valid, kf_rigid_keys,
-// kf_rigid_brick_base, kf_rigid_source_table), a program of its own: tests/test_map_resample_abi_cpu.py builds it with AddressSanitizer + UBSan and runs it
-// as a child process.  usage: map_resample_main
+// kf_rigid_brick_base, kf_rigid_source_table, kf_source_keys_table), a program of its own: tests/test_map_resample_abi_cpu.py builds it with
+// AddressSanitizer + UBSan and runs it as a child process.  usage: map_resample_main
 #include "rigid_keys.h"
 #include <limits.h>
 #include <stdio.h>
@@ -135,6 +135,46 @@ int main() {
     for (uint32_t e = 0; e < n; ++e) CHECK(find(kf_brick_key_pack(many[3 * e], many[3 * e + 1], many[3 * e + 2])) == (int64_t)e);
     CHECK(find(kf_brick_key_pack(1, 1, 1)) == -1 && find(kf_brick_key_pack(-100, 0, 1)) == -1);
     CHECK(kf_rigid_source_table(0, nullptr, tkey, tslot) == 1 && tkey.size() == 2 && tkey[0] == KF_BRICK_KEY_EMPTY && tkey[1] == KF_BRICK_KEY_EMPTY);
+  }
+  // ---- the source keys of an entry point: in range, each once, then the table
+  {
+    std::vector<unsigned long long> tkey;
+    std::vector<unsigned> tslot;
+    uint32_t mask = 77;
+    CHECK(kf_source_keys_table(0, nullptr, tkey, tslot, mask) && mask == 1 && tkey.size() == 2 && tkey[0] == KF_BRICK_KEY_EMPTY && tkey[1] == KF_BRICK_KEY_EMPTY);
+    const int32_t HI = KF_BRICK_KEY_MAX - 1, LO = KF_BRICK_KEY_MIN;
+    for (int j = 0; j < 3; ++j) {                                // each component at either end of the range, and one past it
+      int32_t k[2][3] = {{5, -6, 7}, {0, 0, 0}};
+      k[0][j] = HI; k[1][j] = LO;
+      mask = 77;
+      CHECK(kf_source_keys_table(2, &k[0][0], tkey, tslot, mask) && mask == 3 && tkey.size() == 4);
+      const std::vector<unsigned long long> held = tkey;
+      k[0][j] = HI + 1; mask = 77;
+      CHECK(!kf_source_keys_table(2, &k[0][0], tkey, tslot, mask) && mask == 77 && tkey == held);   // refused: nothing written
+      k[0][j] = HI; k[1][j] = LO - 1;
+      CHECK(!kf_source_keys_table(2, &k[0][0], tkey, tslot, mask) && mask == 77 && tkey == held);
+      k[1][j] = INT_MIN; k[0][j] = INT_MAX;
+      CHECK(!kf_source_keys_table(2, &k[0][0], tkey, tslot, mask));
+    }
+    const int32_t twice[3][3] = {{1, 2, 3}, {-1, -2, -3}, {1, 2, 3}}, once[3][3] = {{1, 2, 3}, {-1, -2, -3}, {1, 2, 4}};
+    mask = 77;
+    CHECK(!kf_source_keys_table(3, &twice[0][0], tkey, tslot, mask) && mask == 77);
+    CHECK(kf_source_keys_table(3, &once[0][0], tkey, tslot, mask) && mask == 7);
+    // the invariant: mask + 1 a power of two >= 2 * count, every key found at its slot from its hash on before a free entry
+    std::vector<int32_t> many;
+    for (int z = -3; z < 4; ++z) for (int y = -2; y < 3; ++y) for (int x = 0; x < 9; ++x) { many.push_back(x * 37 - 100); many.push_back(y); many.push_back(z * 1000); }
+    const uint32_t n = (uint32_t)(many.size() / 3);
+    CHECK(kf_source_keys_table(n, many.data(), tkey, tslot, mask));
+    CHECK(((uint64_t)mask + 1) >= 2ull * n && (((uint64_t)mask + 1) & mask) == 0 && tkey.size() == (size_t)mask + 1 && tslot.size() == tkey.size());
+    for (uint32_t e = 0; e < n; ++e) {
+      const unsigned long long key = kf_brick_key_pack(many[3 * e], many[3 * e + 1], many[3 * e + 2]);
+      int64_t at = -1;
+      for (uint32_t p = 0, h = kf_brick_key_hash(key, mask); p <= mask && tkey[h] != KF_BRICK_KEY_EMPTY; ++p, h = (h + 1u) & mask)
+        if (tkey[h] == key) { at = (int64_t)tslot[h]; break; }
+      CHECK(at == (int64_t)e);
+    }
+    many[3 * (n - 1)] = many[0]; many[3 * (n - 1) + 1] = many[1]; many[3 * (n - 1) + 2] = many[2];   // the last key names the first brick again
+    CHECK(!kf_source_keys_table(n, many.data(), tkey, tslot, mask));
   }
   if (fails) { printf("%d checks FAILED\n", fails); return 1; }
   printf("map resample ok\n");

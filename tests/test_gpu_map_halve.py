@@ -18,6 +18,7 @@ import pytest
 import test_gpu_brickstore as B
 import test_gpu_map_file as M
 import test_gpu_map_merge as MM
+import test_gpu_map_resample as R
 import test_gpu_shift as G
 from hybkinectfu_amd import host_app as H
 from hybkinectfu_amd import lib as K
@@ -260,6 +261,26 @@ def test_no_colour_given_on_a_colour_context():
     ctx.merge_brick_store_halved(b[0], b[1], b[2], None)
     assert same_store(store_sorted(ctx), np_merge(ha, hb, color_given=False))
     ctx.close()
+
+
+def test_halved_onto_held_slots_with_a_pending_word():
+    """the held path with deferred-weight words not 0: the halved bricks meet the TRUE weights, and the words left behind are 0.  The fine map is session
+    B's, moved by whole fine bricks so that its coarse bricks start at the held bricks' least corner."""
+    a, before = R.pending_store()
+    b = MM.session_map(64, False, "B")
+    off = 2 * before[0].min(axis=0) - b[0].min(axis=0)
+    fine = sort_map((np.ascontiguousarray(b[0] + off.astype(np.int32)), b[1], b[2], None))
+    hb = np_halve(fine)
+    ia = {tuple(k): i for i, k in enumerate(before[0].tolist())}
+    both = sum(int(np.count_nonzero((before[2][ia[tuple(k)]] > 0) & (hb[2][i] > 0))) for i, k in enumerate(hb[0].tolist()) if tuple(k) in ia)
+    print("held", len(before[0]), "coarse incoming", len(hb[0]), "shared keys", len(keyset(before) & keyset(hb)), "voxels with two weights", both)
+    assert keyset(before) & keyset(hb) and both > 0               # held keys are hit, and voxels blend
+    a.merge_brick_store_halved(fine[0], fine[1], fine[2], None)
+    want = np_merge(before, hb)
+    first = store_sorted(a)
+    assert same_store(first, want) and a.brick_store_count() == (len(want[0]), 0, 0) and not same_store(first, before)
+    assert same_store(store_sorted(a), first)                     # a second read-out applies nothing twice
+    a.close()
 
 
 # ---- 6. order and run independence ----------------------------------------------------------------------------------------------------------------------------------

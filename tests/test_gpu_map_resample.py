@@ -198,6 +198,34 @@ def test_identity_and_whole_bricks_equal_the_plain_merge(res, color):
         m1.close(); m2.close()
 
 
+def pending_store(res=64, maxw=MM.MAXW):
+    """test_gpu_map_merge.test_held_slots_with_a_pending_word's store: fused with deferral forced on, its bricks gone by a shift with their deferred-weight
+    words.  Returns the context and its read-out (true weights)."""
+    a = K.Context(K.camera(*G.CAM), res, G.SIZES[res], maxw, levels=3)
+    a.set_defer(1)
+    a.brick_store_reserve(CAP)
+    G.fuse(a, range(6))
+    assert a.fusion_form()["defer"] == 1
+    a.shift_volume(0, -24, 16)
+    before = store_sorted(a)
+    assert len(before[0]) >= 20 and a.brick_store_count() == (len(before[0]), 0, 0)
+    return a, before
+
+
+def test_identity_onto_held_slots_with_a_pending_word():
+    """the held path with deferred-weight words not 0: the rigid merge starts from the TRUE weights and leaves words of 0, as the plain merge does"""
+    _, b = two_maps(64, False)
+    (m1, before), (m2, twin) = pending_store(), pending_store()
+    assert same_store(before, twin) and keyset(before) & keyset(b)
+    m1.merge_brick_store_rigid(b[0], b[1], b[2], None, xf_of(np.eye(3), (0, 0, 0)))
+    m2.merge_brick_store(b[0], b[1], b[2])
+    first = store_sorted(m1)
+    assert same_store(first, store_sorted(m2)) and same_store(first, np_merge(before, b)) and not same_store(first, before)
+    assert m1.brick_store_count() == m2.brick_store_count() and m1.brick_store_count()[1] == 0
+    assert same_store(store_sorted(m1), first)                    # a second read-out applies nothing twice
+    m1.close(); m2.close()
+
+
 # ---- 2. whole voxels, not whole bricks -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("res,color", [(64, False), (64, True)])
 def test_whole_voxels_are_a_verbatim_copy(res, color):

@@ -7,7 +7,9 @@ cd "$(dirname "$0")/.."
 name=$1; flags=$2; src=${3:-hybkinectfu_amd/csrc}; inc=${3:+$3/../../include}; inc=${inc:-include}
 mkdir -p ab/obj_$name
 pids=()
-for f in ctx preprocess track integrate raycast mcubes weld meshparts view shift brickstore mapmesh viewat resample align halve erase query; do
+srcs=$(make -C hybkinectfu_amd/csrc -pn 2>/dev/null | sed -n 's/^SRCS := //p' | head -1)   # this tree's list, as tools/device_listing_sha.sh takes it
+for f in $srcs; do
+  f=${f%.hip}
   [ -f $src/$f.hip ] || continue                              # (an older checkout has fewer translation units)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -fno-slp-vectorize -fPIC -std=c++17 -Wno-unused-value -I$inc $flags -c $src/$f.hip -o ab/obj_$name/$f.o &
   pids+=($!)
