@@ -126,6 +126,7 @@ extern "C" int kf_destroy(kf_ctx* c) {
   kf_world_soup_free(c);
   kf_brick_store_free(c);
   kf_erase_scratch_free(c);
+  kf_edt_scratch_free(c);
   if (c->up_stream) { hipStreamSynchronize(c->up_stream); hipStreamDestroy(c->up_stream); }
   for (int i = 0; i < KF_UP_SLOTS; ++i) {
     if (c->up_host[i]) hipHostFree(c->up_host[i]);

@@ -274,6 +274,9 @@ struct kf_ctx {
   // kf_brick_store_erase_box / kf_brick_store_erase_weak (erase.hip): a few 32-bit words per slot of the store -- keep flags and their prefix, the list of holes,
   // the scan's chunk sums, the result.  Allocated by the first erase for the store's capacity, allocated anew when that has changed, freed by kf_destroy.
   void* erase_scratch; uint32_t erase_scratch_bricks;
+  // kf_map_distance_field (edt.hip): the site bits of the widened box and the x and y passes' 16-bit outputs.  Allocated by the first call that asks for
+  // distances, grown when a later box needs more, freed by kf_destroy.  Not the extraction scratch: a map mesh may be using that.
+  void* edt_scratch; size_t edt_scratch_bytes;
 };
 
 enum { KF_STAGE_UPLOAD = 0, KF_STAGE_PREPROCESS = 1, KF_STAGE_TRACK = 2, KF_STAGE_INTEGRATE = 3, KF_STAGE_RAYCAST = 4,
@@ -723,3 +726,4 @@ int kf_brick_store_capture_enqueue(kf_ctx* ctx);   // kf_brick_store_capture pas
 int kf_brick_store_reset(kf_ctx* ctx);   // no entries, counts zero (kf_brick_store_clear, kf_reset_volume); asynchronous
 void kf_brick_store_free(kf_ctx* ctx);   // for kf_destroy and kf_brick_store_reserve: the caller has synchronised the stream
 void kf_erase_scratch_free(kf_ctx* ctx); // (erase.hip) for kf_destroy: the caller has synchronised the stream
+void kf_edt_scratch_free(kf_ctx* ctx);   // (edt.hip) for kf_destroy: the caller has synchronised the stream

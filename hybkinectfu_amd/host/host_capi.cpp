@@ -5,6 +5,7 @@
 #include "map_file.hpp"
 #include "erase_box_voxels.hpp"
 #include "map_query_voxels.hpp"
+#include "edt_box_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <string.h>
 
@@ -230,6 +231,32 @@ int hkf_map_query_voxels(const double* world_m, uint32_t count3, float cell, dou
   if (!world_m || !vox) return -1;
   hkf_query_voxels(world_m, count3, cell, vox);
   return 0;
+}
+// HybKinectfu::distanceField (the box and max_dist_m in WORLD metres): 1 done, 0 refused or failed, -1 without an application.  hkf_app_distance_field_box
+// computes nothing on the device: the voxel box and the clamped radius the field would have, so that the caller can size dist (float) and cls (a byte) --
+// capacity items each, nx * ny * nz are needed; a capacity below that is refused with nothing written.  lo_vox, dims, radius (may be NULL): as found.
+int hkf_app_distance_field_box(const float lo_m[3], const float hi_m[3], float max_dist_m, int32_t lo_vox[3], uint32_t dims[3], uint32_t* radius) {
+  if (!g_app) return -1;
+  if (!lo_m || !hi_m || !lo_vox || !dims) return 0;
+  const float cell = AppParams::instance()->_volume_params.fVolumeMeterSize / (float)AppParams::instance()->_volume_params.nResolution;
+  if (radius) *radius = hkf_edt_radius(max_dist_m, cell);
+  uint64_t count = 0;
+  return hkf_edt_box_voxels(lo_m, hi_m, cell, lo_vox, dims) && hkf_edt_voxel_count(dims, &count) ? 1 : 0;       // (0 also for a box of more than HKF_EDT_MAX_VOXELS voxels)
+}
+int hkf_app_distance_field(const float lo_m[3], const float hi_m[3], float max_dist_m, float level, uint32_t site_mask, uint64_t capacity, float* dist, uint8_t* cls,
+                           int32_t lo_vox[3], uint32_t dims[3], uint32_t* radius) {
+  if (!g_app) return -1;
+  if (!lo_m || !hi_m || !dist || !cls) return 0;
+  int32_t lo[3]; uint32_t n3[3], r = 0;
+  uint64_t count = 0;
+  if (hkf_app_distance_field_box(lo_m, hi_m, max_dist_m, lo, n3, &r) != 1 || !hkf_edt_voxel_count(n3, &count) || count > capacity) return 0;
+  std::vector<float> d; std::vector<uint8_t> c;
+  if (!g_app->distanceField(lo_m, hi_m, max_dist_m, level, site_mask, d, c, n3, &r, lo)) return 0;
+  memcpy(dist, d.data(), d.size() * sizeof(float)); memcpy(cls, c.data(), c.size());
+  if (lo_vox) memcpy(lo_vox, lo, sizeof(lo));
+  if (dims) memcpy(dims, n3, sizeof(n3));
+  if (radius) *radius = r;
+  return 1;
 }
 int hkf_app_frame_id() { if (!g_app) return -1; return (int)g_app->frameId(); }
 int hkf_map_file_info(const char* path, uint32_t* u32x4, float* f32x2, int32_t* origin3, uint32_t* frame_id, float* pose16, uint64_t* u64x2) {

@@ -5,11 +5,13 @@
 #include "map_file.hpp"
 #include "erase_box_voxels.hpp"
 #include "map_query_voxels.hpp"
+#include "edt_box_voxels.hpp"
 #include "mesh_parts.hpp"
 #include <math.h>
 #include <string.h>
 #include <stdio.h>
 #include <algorithm>
+#include <exception>
 #include <fstream>
 #include <new>
 #include <unordered_map>
@@ -760,6 +762,52 @@ bool HybKinectfu::castMapRays(const double* origin_m, const float* dir, const fl
   const float step = p->_raycast_params.fRayIncrement / cell;
   if (dm->check(kf_map_cast_rays(dm->ctx(), (uint32_t)n, vox.data(), dir, t0.data(), t1.data(), step, 1u << 24, status, t_m, normal, color, weight))) return false;
   if (t_m) for (size_t i = 0; i < n; ++i) t_m[i] = t_m[i] * cell;
+  return true;
+}
+bool HybKinectfu::distanceFieldVoxels(const int32_t lo_vox[3], const uint32_t dims[3], uint32_t radius, float level, uint32_t siteMask, uint16_t* dist2, uint8_t* cls) {
+  uint64_t count = 0;
+  if (!_inited || !lo_vox || !dims || !hkf_edt_voxel_count(dims, &count)) return false;        // (also a box of more than HKF_EDT_MAX_VOXELS voxels)
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  const uint32_t tx = hkf_edt_tile_count(dims[0]), ty = hkf_edt_tile_count(dims[1]), tz = hkf_edt_tile_count(dims[2]);
+  if (tx == 1u && ty == 1u && tz == 1u) return dm->check(kf_map_distance_field(dm->ctx(), lo_vox, dims, radius, level, siteMask, dist2, cls)) == 0;
+  std::vector<uint16_t> td;
+  std::vector<uint8_t> tc;
+  try {
+    td.resize(dist2 ? (size_t)HKF_EDT_TILE * HKF_EDT_TILE * HKF_EDT_TILE : 0);
+    tc.resize(cls ? (size_t)HKF_EDT_TILE * HKF_EDT_TILE * HKF_EDT_TILE : 0);
+  } catch (const std::exception&) { return false; }
+  for (uint32_t iz = 0; iz < tz; ++iz) for (uint32_t iy = 0; iy < ty; ++iy) for (uint32_t ix = 0; ix < tx; ++ix) {
+    uint32_t off[3], len[3];
+    hkf_edt_tile(dims[0], ix, &off[0], &len[0]); hkf_edt_tile(dims[1], iy, &off[1], &len[1]); hkf_edt_tile(dims[2], iz, &off[2], &len[2]);
+    const int64_t lo64[3] = {(int64_t)lo_vox[0] + off[0], (int64_t)lo_vox[1] + off[1], (int64_t)lo_vox[2] + off[2]};
+    if (lo64[0] > INT32_MAX || lo64[1] > INT32_MAX || lo64[2] > INT32_MAX) return false;     // (such a box lies outside the key range)
+    const int32_t lo[3] = {(int32_t)lo64[0], (int32_t)lo64[1], (int32_t)lo64[2]};
+    if (dm->check(kf_map_distance_field(dm->ctx(), lo, len, radius, level, siteMask, dist2 ? td.data() : nullptr, cls ? tc.data() : nullptr))) return false;
+    for (uint32_t z = 0; z < len[2]; ++z) for (uint32_t y = 0; y < len[1]; ++y) {
+      const size_t src = ((size_t)z * len[1] + y) * len[0], dst = (((size_t)off[2] + z) * dims[1] + off[1] + y) * dims[0] + off[0];
+      if (dist2) memcpy(dist2 + dst, td.data() + src, 2 * (size_t)len[0]);
+      if (cls) memcpy(cls + dst, tc.data() + src, len[0]);
+    }
+  }
+  return true;
+}
+bool HybKinectfu::distanceField(const float lo_m[3], const float hi_m[3], float maxDist_m, float level, uint32_t siteMask, std::vector<float>& distance_m,
+                                std::vector<uint8_t>& cls, uint32_t dims[3], uint32_t* radiusVox, int32_t* loVox) {
+  if (!_inited || !lo_m || !hi_m || !dims) return false;
+  AppParams* p = AppParams::instance();
+  const float cell = p->_volume_params.fVolumeMeterSize / (float)p->_volume_params.nResolution;
+  int32_t lo[3];
+  if (!hkf_edt_box_voxels(lo_m, hi_m, cell, lo, dims)) return false;
+  const uint32_t radius = hkf_edt_radius(maxDist_m, cell);
+  if (radiusVox) *radiusVox = radius;
+  if (loVox) memcpy(loVox, lo, sizeof(lo));
+  uint64_t count = 0;
+  if (!hkf_edt_voxel_count(dims, &count)) return false;          // too large a box: refused before anything is sized
+  const size_t n = (size_t)count;
+  std::vector<uint16_t> d2;
+  try { d2.resize(n); distance_m.resize(n); cls.resize(n); } catch (const std::exception&) { return false; }   // (bad_alloc, length_error)
+  if (!distanceFieldVoxels(lo, dims, radius, level, siteMask, d2.data(), cls.data())) return false;
+  for (size_t i = 0; i < n; ++i) distance_m[i] = d2[i] == KF_EDT_FAR ? INFINITY : sqrtf((float)d2[i]) * cell;
   return true;
 }
 bool HybKinectfu::loadMapCoarser(const std::string& path) {

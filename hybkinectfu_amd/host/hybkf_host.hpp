@@ -354,6 +354,18 @@ public:
   bool sampleMap(const double* world_m, size_t n, float* distance_m, float* weight, float* gradient, uint8_t* color);
   bool castMapRays(const double* origin_m, const float* dir, const float* t_min_m, const float* t_max_m, size_t n, uint8_t* status, float* t_m, float* normal, uint8_t* color,
                    float* weight);
+  // distanceFieldVoxels: the map's distance field over the box lo_vox / dims of world voxels (kf_map_distance_field: the squared distance in voxels to the
+  // nearest site within `radius` voxels, KF_EDT_FAR beyond; the class bytes), indexed (z * ny + y) * nx + x.  A box with an edge above 128 voxels is computed
+  // in tiles of at most 128 per axis (hkf_edt_tile, edt_box_voxels.hpp) and stitched: the same bytes, by the field's sub-box guarantee, and no box is too
+  // large for the call's cap.  dist2 / cls: nx * ny * nz items each, either may be nullptr.
+  // distanceField: the same in WORLD metres.  The box is eraseMapBox's (voxel g is in it iff lo_m <= (g + 1/2) * cell < hi_m); the radius is
+  // floor(maxDist_m / cell) clamped to 1 .. 255 and reported back in radiusVox; distance_m = sqrtf((float)d2) * cell, +infinity where no site lies within the
+  // radius.  distance_m and cls are resized to nx * ny * nz, dims receives the box's size in voxels, loVox (may be nullptr) its first voxel.
+  // Both only read: they capture nothing and move nothing.  false: not initialised, a null or empty box, a box of more than 2^31 voxels (hkf_edt_voxel_count:
+  // refused before anything is sized), no memory for the arrays, a refused call.
+  bool distanceFieldVoxels(const int32_t lo_vox[3], const uint32_t dims[3], uint32_t radius, float level, uint32_t siteMask, uint16_t* dist2, uint8_t* cls);
+  bool distanceField(const float lo_m[3], const float hi_m[3], float maxDist_m, float level, uint32_t siteMask, std::vector<float>& distance_m, std::vector<uint8_t>& cls,
+                     uint32_t dims[3], uint32_t* radiusVox, int32_t* loVox = nullptr);
   unsigned frameId() const { return _frame_id; }
 private:
   bool recentre();

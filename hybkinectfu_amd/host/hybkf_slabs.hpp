@@ -69,6 +69,8 @@ public:
   bool eraseMapWeak(float, unsigned* = nullptr) { return false; }
   bool sampleMap(const double*, size_t, float*, float*, float*, uint8_t*) { return false; }
   bool castMapRays(const double*, const float*, const float*, const float*, size_t, uint8_t*, float*, float*, uint8_t*, float*) { return false; }
+  bool distanceFieldVoxels(const int32_t*, const uint32_t*, uint32_t, float, uint32_t, uint16_t*, uint8_t*) { return false; }
+  bool distanceField(const float*, const float*, float, float, uint32_t, std::vector<float>&, std::vector<uint8_t>&, uint32_t*, uint32_t*, int32_t* = nullptr) { return false; }
   kf_group* group() const { return _group; }
   int lastError() const { return _err; }
 private:

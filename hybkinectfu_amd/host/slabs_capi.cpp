@@ -141,5 +141,7 @@ int hkf_slabs_erase_map_weak(float, uint64_t*) { return -1; }
 // querying the map reads window and brick store: always -1, nothing written
 int hkf_slabs_sample_map(const double*, uint32_t, float*, float*, float*, uint8_t*) { return -1; }
 int hkf_slabs_cast_map_rays(const double*, const float*, const float*, const float*, uint32_t, uint8_t*, float*, float*, uint8_t*, float*) { return -1; }
+// so does the distance field: always -1, nothing written
+int hkf_slabs_distance_field(const float*, const float*, float, float, uint32_t, uint64_t, float*, uint8_t*, int32_t*, uint32_t*, uint32_t*) { return -1; }
 int hkf_slabs_last_error() { return g_slabs ? g_slabs->lastError() : 0; }
 }

@@ -297,6 +297,35 @@ class App:
             raise K.KfError("hkf_app_cast_map_rays failed")
         return out
 
+    def distance_field_box(self, lo_m, hi_m, max_dist_m):
+        """the box distance_field computes for these corners, without computing it: (lo_vox (x, y, z), dims (nx, ny, nz), the radius in voxels) -- voxel g is in
+        the box iff lo_m <= (g + 1/2) * cell < hi_m, the radius is floor(max_dist_m / cell) clamped to 1 .. 255.  KfError for an empty box, a NaN corner or a
+        box of more than 2^31 voxels"""
+        l, h = (C.c_float * 3)(*[float(x) for x in lo_m]), (C.c_float * 3)(*[float(x) for x in hi_m])
+        lo, dims, radius = (C.c_int32 * 3)(), (C.c_uint32 * 3)(), C.c_uint32()
+        r = self.h.hkf_app_distance_field_box(l, h, C.c_float(max_dist_m), lo, dims, C.byref(radius))
+        if r < 0:
+            raise K.KfError("hkf_app_distance_field_box: no application")
+        if r == 0:
+            raise K.KfError("hkf_app_distance_field_box: an empty box, or one too large")
+        return tuple(int(v) for v in lo), tuple(int(v) for v in dims), int(radius.value)
+
+    def distance_field(self, lo_m, hi_m, max_dist_m, level=0.0, site_mask=1 << K.VOX_OCCUPIED):
+        """HybKinectfu::distanceField: the clearance in this session's map over the box lo_m <= voxel centre < hi_m (WORLD metres, erase_map_box's rule): the
+        distance in metres from every voxel of the box to the nearest site -- a voxel whose class (K.VOX_UNKNOWN, K.VOX_FREE: tsdf > level, K.VOX_OCCUPIED) has
+        its bit set in site_mask -- up to floor(max_dist_m / cell) voxels, clamped to 1 .. 255.  Returns (dist float32 (nz, ny, nx): sqrt(d2) * cell, inf
+        where no site lies within the radius; cls uint8 (nz, ny, nx); the radius used, voxels).  Where the box lies in voxels: distance_field_box"""
+        _, dims, _ = self.distance_field_box(lo_m, hi_m, max_dist_m)
+        l, h = (C.c_float * 3)(*[float(x) for x in lo_m]), (C.c_float * 3)(*[float(x) for x in hi_m])
+        shape = (dims[2], dims[1], dims[0])
+        dist, cls = np.zeros(shape, np.float32), np.zeros(shape, np.uint8)
+        radius = C.c_uint32()
+        r = self.h.hkf_app_distance_field(l, h, C.c_float(max_dist_m), C.c_float(level), C.c_uint32(site_mask), C.c_uint64(dist.size), K._p(dist), K._p(cls),
+                                          None, None, C.byref(radius))
+        if r <= 0:
+            raise K.KfError("hkf_app_distance_field failed")
+        return dist, cls, int(radius.value)
+
     def frame_id(self):
         """HybKinectfu::frameId: the id of the last frame processed, or the one load_map set"""
         r = self.h.hkf_app_frame_id()
@@ -461,6 +490,12 @@ class SlabsApp:
         org = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
         r = self.h.hkf_slabs_cast_map_rays(K._p(org), None, None, None, C.c_uint32(len(org)), None, None, None, None, None)
         raise K.KfError("hkf_slabs_cast_map_rays: slab groups have no map queries (%d)" % r)
+
+    def distance_field(self, lo_m, hi_m, max_dist_m, level=0.0, site_mask=1 << K.VOX_OCCUPIED):
+        """always refused (K.KfError), as sample_map"""
+        l, h = (C.c_float * 3)(*[float(x) for x in lo_m]), (C.c_float * 3)(*[float(x) for x in hi_m])
+        r = self.h.hkf_slabs_distance_field(l, h, C.c_float(max_dist_m), C.c_float(level), C.c_uint32(site_mask), C.c_uint64(0), None, None, None, None, None)
+        raise K.KfError("hkf_slabs_distance_field: slab groups have no map queries (%d)" % r)
 
     def close(self):
         self.h.hkf_slabs_shutdown()

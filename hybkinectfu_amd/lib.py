@@ -128,6 +128,7 @@ SYMBOLS = [
     "kf_merge_brick_store_halved", "kf_halved_brick_keys",
     "kf_brick_store_erase_box", "kf_brick_store_erase_weak",
     "kf_map_sample", "kf_map_sample_device", "kf_map_cast_rays", "kf_map_cast_rays_device",
+    "kf_map_distance_field", "kf_map_distance_field_device",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -192,6 +193,8 @@ def load():
             f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
         for f in (_lib.kf_map_cast_rays, _lib.kf_map_cast_rays_device):
             f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_uint32] + [C.c_void_p] * 5
+        for f in (_lib.kf_map_distance_field, _lib.kf_map_distance_field_device):
+            f.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
         _lib.kf_render_view_at.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int32), C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_map.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_uint32)]
@@ -258,6 +261,8 @@ def halved_brick_keys(keys):
 
 ERASE_INSIDE, ERASE_OUTSIDE = 0, 1                                    # kf_brick_store_erase_box: mode
 RAY_MISS, RAY_HIT, RAY_BROKEN = 0, 1, 2                               # kf_map_cast_rays: status
+VOX_UNKNOWN, VOX_FREE, VOX_OCCUPIED = 0, 1, 2                         # kf_map_distance_field: the class byte; bit c of site_mask = class c
+EDT_FAR = 0xFFFF                                                      # kf_map_distance_field: no site within the radius
 
 ALIGN_CONVERGED, ALIGN_ITER_LIMIT, ALIGN_FEW_PAIRS, ALIGN_SINGULAR = 0, 1, 2, 3   # kf_align_report.verdict
 
@@ -971,6 +976,24 @@ class Context:
         ptr = [C.c_void_p(x) if x else None for x in (dev_origin, dev_dir, dev_tmin, dev_tmax, dev_status, dev_t, dev_normal, dev_color, dev_weight)]
         _chk(self.lib.kf_map_cast_rays_device(self.h, int(n), ptr[0], ptr[1], ptr[2], ptr[3], C.c_float(step), int(max_steps), *ptr[4:]),
              "kf_map_cast_rays_device")
+
+    def map_distance_field(self, lo_vox, dims, radius, level=0.0, site_mask=1 << VOX_OCCUPIED, want=("dist2", "cls")):
+        """the map's distance field over the box of world voxels lo_vox (x, y, z), dims (nx, ny, nz): a dict of dist2 (nz, ny, nx) uint16 -- the squared
+        distance in voxels to the nearest site of the map within `radius` (1 .. 255) voxels, EDT_FAR beyond -- and cls (nz, ny, nx) uint8 (VOX_UNKNOWN,
+        VOX_FREE: tsdf > level, VOX_OCCUPIED).  The sites are the voxels whose class has its bit set in site_mask.  want: which outputs to ask for, the
+        other is passed as NULL (kf_map_distance_field)"""
+        lo, n = (C.c_int32 * 3)(*[int(x) for x in lo_vox]), (C.c_uint32 * 3)(*[int(x) for x in dims])
+        shape = (int(dims[2]), int(dims[1]), int(dims[0]))
+        out = {k: v for k, v in dict(dist2=np.zeros(shape, np.uint16), cls=np.zeros(shape, np.uint8)).items() if k in want}
+        a = [_p(out[k]) if k in out else None for k in ("dist2", "cls")]
+        _chk(self.lib.kf_map_distance_field(self.h, lo, n, int(radius), C.c_float(level), int(site_mask), *a), "kf_map_distance_field")
+        return out
+
+    def map_distance_field_device(self, lo_vox, dims, radius, level=0.0, site_mask=1 << VOX_OCCUPIED, dev_dist2=None, dev_cls=None):
+        """map_distance_field with device output pointers (integers or None), on the context's stream, non-blocking (kf_map_distance_field_device)"""
+        lo, n = (C.c_int32 * 3)(*[int(x) for x in lo_vox]), (C.c_uint32 * 3)(*[int(x) for x in dims])
+        _chk(self.lib.kf_map_distance_field_device(self.h, lo, n, int(radius), C.c_float(level), int(site_mask),
+                                                   *[C.c_void_p(x) if x else None for x in (dev_dist2, dev_cls)]), "kf_map_distance_field_device")
 
     def refill_window(self):
         """the window re-read from the store under its current origin, without capturing it first: a window brick the store does not hold reads as never

@@ -786,6 +786,44 @@ int kf_map_sample(kf_ctx* ctx, uint32_t n, const double* pos, float* tsdf, float
 int kf_map_cast_rays_device(kf_ctx* ctx, uint32_t n, const double* dev_origin, const float* dev_dir, const float* dev_tmin, const float* dev_tmax, float step, uint32_t max_steps, uint8_t* dev_status, float* dev_t, float* dev_normal, uint8_t* dev_color, float* dev_weight);
 int kf_map_cast_rays(kf_ctx* ctx, uint32_t n, const double* origin, const float* dir, const float* tmin, const float* tmax, float step, uint32_t max_steps, uint8_t* status, float* t, float* normal, uint8_t* color, float* weight);
 
+/* The distance field of the map: for every voxel of a box the exact squared Euclidean distance, in voxels, to the nearest SITE of the map, up to a radius --
+ * the clearance a planner asks for beyond the truncation band (no reference counterpart).
+ * The map as a function of a world voxel g is the one written above kf_map_sample: the window's copy where the voxel's brick is inside the window, else the
+ *   store's, else nobody holds it; weights are TRUE weights; without a store the window alone is the map.  A voxel whose brick coordinate lies outside the
+ *   key range [-2^20, 2^20) is held by nobody.
+ * The class of a voxel, one byte: KF_VOX_UNKNOWN -- the true weight is not > 0, or nobody holds the voxel; KF_VOX_FREE -- observed and tsdf > level;
+ *   KF_VOX_OCCUPIED -- observed and tsdf <= level.  level is in tsdf units: 0 means at or behind the surface, a small positive level inflates obstacles.
+ * The sites are the voxels whose class has its bit set in site_mask (bit c = class c, the mask in 1 .. 7): 1 << KF_VOX_OCCUPIED is the obstacle field; or-ing
+ *   in 1 << KF_VOX_UNKNOWN treats unknown space as an obstacle; (1 << KF_VOX_FREE) | (1 << KF_VOX_UNKNOWN) is the depth inside obstacles -- a signed field is
+ *   two calls.
+ * The field: for every voxel g of the box, d2(g) = the minimum of |s - g|^2 over ALL sites s of the map, not only those in the box.  Coordinates are integer
+ *   voxel indices, the squared distance is an integer.  The output is d2 where d2 <= radius^2, else KF_EDT_FAR.  radius is in voxels, 1 .. 255 (255^2 = 65025
+ *   fits 16 bits below the sentinel).  A site reads 0.  Two guarantees follow:
+ *   - the field of a box is the same bytes as the corresponding part of the field of any box that encloses it (so a caller may tile);
+ *   - the field does not depend on where the window stands or on which of window and store holds a brick, once captured.
+ * The box: lo_vox (world voxels, any sign, need not be brick-aligned) and dims (each >= 1); the outputs are indexed (z * ny + y) * nx + x.  The box itself must
+ *   lie inside [-2^23, 2^23) on every axis; the `radius` voxels around it that are searched may reach outside, where they read unknown.
+ * dist2: 16 bits per voxel; cls: the class byte per voxel.  Either may be NULL, independently (both NULL: nothing is done).  lo_vox and dims are host pointers
+ *   in both forms.  The _device form takes device output pointers, runs on the context's stream and does not block -- except that a call whose box needs more
+ *   scratch than any before it waits for the stream before it frees the smaller one; the other form takes host pointers: one temporary allocation, copies, and
+ *   it blocks.  The scratch (one site bit per voxel of the box widened by radius, rounded out to bricks, and 16 bits for each of nx (ny + 2 radius) (nz + 2 radius)
+ *   + nx ny (nz + 2 radius) voxels) is the context's own, allocated or grown by the first call that needs it and freed with the context; it is not the extraction
+ *   scratch.  The classes alone (dist2 NULL) need none.
+ * Nothing of the context changes: volume, store, deferred-weight words, pose, model maps, extraction scratch and every later frame are bit for bit what they
+ *   would have been.
+ * Refused with nothing written -- KF_ERR_ARG: a NULL context, lo_vox or dims; a zero dimension; a box that does not lie inside [-2^23, 2^23); radius 0 or > 255;
+ *   site_mask 0 or > 7; a NaN level; nx * (ny + 2 radius) * (nz + 2 radius) > 2^29 (the bound on the two 16-bit buffers, 2 GiB together at the most: a larger
+ *   box is tiled by the caller, which the first guarantee makes exact).  KF_ERR_STATE: a z-slab context.  KF_ERR_ALLOC: no memory for the scratch.  The cap does
+ *   NOT bound the bit volume, which is widened in x too: about (nx + 2 radius) / 8 bytes per row of (ny + 2 radius) (nz + 2 radius) -- a sixteenth of the x pass's
+ *   buffer for a box much wider than its radius, but 511 / 8 bytes per row, some 34 GB at the cap, for nx = 1 at radius 255.  KF_ERR_ALLOC is the only guard
+ *   there: keep a box's x edge at least comparable to the radius (lanes run along x in every pass, so a narrow box is slow as well). */
+#define KF_VOX_UNKNOWN 0
+#define KF_VOX_FREE 1
+#define KF_VOX_OCCUPIED 2
+#define KF_EDT_FAR 0xFFFFu
+int kf_map_distance_field_device(kf_ctx* ctx, const int32_t lo_vox[3], const uint32_t dims[3], uint32_t radius, float level, uint32_t site_mask, uint16_t* dev_dist2, uint8_t* dev_cls);
+int kf_map_distance_field(kf_ctx* ctx, const int32_t lo_vox[3], const uint32_t dims[3], uint32_t radius, float level, uint32_t site_mask, uint16_t* dist2, uint8_t* cls);
+
 /* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
  * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
  * voxels a start 10 degrees and about 5 voxels off still converges; a start much further off finds too few pairs or a wrong minimum.  Coarse-to-fine search
