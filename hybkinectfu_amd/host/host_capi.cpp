@@ -216,6 +216,23 @@ int hkf_erase_map_box_voxels(const float lo_m[3], const float hi_m[3], float cel
   hkf_erase_box_voxels(lo_m, hi_m, cell, lo_vox, hi_vox);
   return 0;
 }
+// HybKinectfu::relocalise: 1 accepted (the next frame tracks from the found pose), 0 refused or not accepted (nothing of the session changed), -1 without an
+// application.  params NULL: the defaults.  hkf_reloc_defaults_get / hkf_reloc_points / hkf_reloc_lattice / hkf_reloc_rank need no application (reloc_search.hpp).
+int hkf_app_relocalise(const uint16_t* mm, unsigned frame_id, const RelocParams* params, RelocReport* report) {
+  if (!g_app) return -1;
+  const CameraParams& c = AppParams::instance()->_depth_camera_params;
+  DepthFrameData d; d.mm = mm; d.cols = (int)c.cols; d.rows = (int)c.rows; d.frame_id = frame_id; d.on_device = false;
+  const RelocParams def = hkf_reloc_defaults();
+  return g_app->relocalise(d, params ? *params : def, report) ? 1 : 0;
+}
+void hkf_reloc_defaults_get(RelocParams* out) { if (out) *out = hkf_reloc_defaults(); }
+uint32_t hkf_reloc_points(const float* verts, uint32_t n_pix, float cell, uint32_t max_points, float* out, float* median_depth_m) {
+  return reloc_points(verts, n_pix, cell, max_points, out, median_depth_m);
+}
+int64_t hkf_reloc_lattice(const double* centre, const int32_t* n, double trans_step, double rot_step, double* out, int64_t cap) {
+  return reloc_lattice(centre, n, trans_step, rot_step, out, cap);
+}
+uint32_t hkf_reloc_rank(const kf_pose_score* scores, uint32_t n, uint32_t min_obs, uint32_t M, uint32_t* best) { return reloc_rank(scores, n, min_obs, M, best); }
 // HybKinectfu::sampleMap / castMapRays (positions, t: WORLD metres): 1 done, 0 refused or failed, -1 without an application.  Any output may be NULL.
 // hkf_map_query_voxels needs no application: count3 coordinates in metres as fp64 voxel positions
 int hkf_app_sample_map(const double* world_m, uint32_t n, float* distance_m, float* weight, float* gradient, uint8_t* color) {

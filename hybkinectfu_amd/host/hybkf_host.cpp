@@ -734,6 +734,116 @@ bool HybKinectfu::eraseMapWeak(float minWeight, unsigned* bricksRemoved) {
   if (bricksRemoved) *bricksRemoved = removed;
   return es == 0;
 }
+bool HybKinectfu::relocalise(const DepthFrameData& depth_frame, const RelocParams& rp_in, RelocReport* report) {
+  RelocReport rep;
+  memset(&rep, 0, sizeof(rep));
+  if (report) *report = rep;
+  if (!_inited || !depth_frame.mm) return false;
+  const AppParams* p = AppParams::instance();
+  CudaDeviceDataMan* dm = CudaDeviceDataMan::instance();
+  kf_ctx* ctx = dm->ctx();
+  RelocParams par = rp_in;
+  const RelocParams def = hkf_reloc_defaults();
+  const uint32_t levels = p->_icp_params.nPyramidLevels ? p->_icp_params.nPyramidLevels : 1u;
+  const uint32_t level = par.level < 0 ? levels - 1u : (uint32_t)par.level;
+  if (level >= levels) return false;
+  if (par.top == 0) par.top = def.top;
+  if (par.max_points == 0) par.max_points = def.max_points;
+  for (int k = 0; k < 6; ++k) if (par.n[k] < 0) par.n[k] = def.n[k];
+  if (par.top > 4096u || reloc_lattice_count(par.n) < 0) return false;
+  lastTracked();                                                // a frame still in flight settles first
+  copyFrameToGPU(depth_frame, ColorFrameData());
+  if (dm->check(kf_preprocess(ctx, p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc, p->_depth_prepocess_params.fSigmaPixel,
+                              p->_depth_prepocess_params.fSigmaDepth, &p->_depth_camera_params))) return false;
+  if (level > 0 && dm->check(kf_downsample_new_vertices(ctx))) return false;   // (the pyramid is the tracker's work: without it the level holds the last frame's)
+  // the points: the level's vertex map, valid vertices, voxels
+  const uint32_t cols = p->_depth_camera_params.cols >> level, rows = p->_depth_camera_params.rows >> level;
+  const float cell = volume_cell();
+  std::vector<float> verts, pts;
+  std::vector<double> poses, centres, refined;
+  std::vector<kf_pose_score> scores;
+  std::vector<uint32_t> best;
+  std::vector<kf_align_report> reps;
+  try { verts.resize((size_t)cols * rows * 4); pts.resize((size_t)par.max_points * 3); } catch (const std::bad_alloc&) { return false; }
+  if (dm->check(kf_download_map(ctx, KF_MAP_NEW_VERTICES, level, verts.data(), verts.size() * sizeof(float)))) return false;
+  float median = 0.f;
+  const uint32_t n_pts = reloc_points(verts.data(), cols * rows, cell, par.max_points, pts.data(), &median);
+  rep.points = n_pts; rep.median_depth = median;
+  if (report) *report = rep;
+  if (n_pts == 0 || !(median > 0.f)) return false;             // no measurement in the frame
+  const float trans_m = par.trans_step > 0.f ? par.trans_step : p->_integrate_params.fSdfTruncation;
+  const float rot = par.rot_step > 0.f ? par.rot_step : atanf(p->_integrate_params.fSdfTruncation / median);
+  rep.trans_step = trans_m; rep.rot_step = rot;
+  // the centre pose, world voxels, fp64
+  const Mat44 cw = par.has_guess ? [&] { Mat44 g; memcpy(g.entries, par.guess, 64); return g; }() : worldPose(_camera_pose_finder->getCameraPose());
+  double centre[12];
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) centre[4 * i + j] = (double)cw.entries[4 * i + j];
+    centre[4 * i + 3] = (double)cw.entries[4 * i + 3] / (double)cell;
+  }
+  for (int i = 0; i < 12; ++i) if (!isfinite(centre[i])) return false;
+  const int64_t K = reloc_lattice_count(par.n);
+  try {
+    poses.resize((size_t)K * 12); scores.resize((size_t)K); best.resize(par.top); centres.resize((size_t)par.top * 3); refined.resize((size_t)par.top * 12);
+    reps.resize(par.top);
+  } catch (const std::bad_alloc&) { return false; }
+  reloc_lattice(centre, par.n, (double)trans_m / (double)cell, (double)rot, poses.data(), K);
+  rep.candidates = (uint32_t)K;
+  if (report) *report = rep;
+  if (dm->check(kf_map_score_poses(ctx, n_pts, pts.data(), (uint32_t)K, poses.data(), par.band, scores.data()))) return false;
+  const uint32_t eligible = reloc_rank(scores.data(), (uint32_t)K, par.min_obs, par.top, best.data());
+  const uint32_t M = eligible < par.top ? eligible : par.top;
+  if (M == 0) return false;                                     // no candidate sees enough of the map
+  rep.best_index = best[0]; rep.best_score = scores[best[0]];
+  memcpy(rep.best_pose, &poses[(size_t)best[0] * 12], sizeof(rep.best_pose));
+  if (report) *report = rep;
+  // each candidate's centre: R * mean(points) + t
+  double mean[3] = {0.0, 0.0, 0.0};
+  for (uint32_t i = 0; i < n_pts; ++i) for (int k = 0; k < 3; ++k) mean[k] += (double)pts[3 * (size_t)i + k];
+  for (int k = 0; k < 3; ++k) mean[k] /= (double)n_pts;
+  for (uint32_t a = 0; a < M; ++a) {
+    const double* P = &poses[(size_t)best[a] * 12];
+    memcpy(&refined[(size_t)a * 12], P, 12 * sizeof(double));
+    for (int j = 0; j < 3; ++j) centres[3 * (size_t)a + j] = ((P[4 * j] * mean[0] + P[4 * j + 1] * mean[1]) + P[4 * j + 2] * mean[2]) + P[4 * j + 3];
+  }
+  kf_refine_params fp = {par.max_iter, par.min_pairs, par.eps_rot, par.eps_trans, par.gate};
+  if (dm->check(kf_map_refine_poses(ctx, n_pts, pts.data(), M, refined.data(), centres.data(), &fp, reps.data()))) return false;
+  if (dm->check(kf_map_score_poses(ctx, n_pts, pts.data(), M, refined.data(), par.band, scores.data()))) return false;
+  uint32_t win = 0;
+  if (reloc_rank(scores.data(), M, par.min_obs, 1u, &win) == 0) return false;
+  const double* F = &refined[(size_t)win * 12];
+  memcpy(rep.refined_pose, F, sizeof(rep.refined_pose));
+  rep.refined_score = scores[win]; rep.verdict = reps[win].verdict; rep.iterations = reps[win].iterations;
+  const bool accept = (double)scores[win].n_in >= (double)par.accept_inliers * (double)n_pts && scores[win].n_obs >= par.min_obs &&
+                      reps[win].verdict != KF_ALIGN_FEW_PAIRS && reps[win].verdict != KF_ALIGN_SINGULAR;
+  if (report) *report = rep;
+  if (!accept) return false;
+  // the found pose in world metres (fp32), its frame, and the pose in that frame
+  Mat44 wp = Mat44::getIdentity(), local;
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j) wp.entries[4 * i + j] = (float)F[4 * i + j];
+    wp.entries[4 * i + 3] = (float)(F[4 * i + 3] * (double)cell);
+  }
+  int32_t frame[3];
+  hkf_view_frame(wp.entries, p->_volume_params.fVolumeMeterSize, p->_volume_params.nResolution, frame, local.entries);
+  int o[3]; volumeOrigin(o);
+  const bool move = p->_volume_params.nBrickStoreBricks > 0 && (frame[0] != o[0] || frame[1] != o[1] || frame[2] != o[2]);
+  if (move) {                                                   // loadMap's tail: the window stands where the pose looks
+    if (dm->check(kf_brick_store_capture(ctx)) || dm->check(kf_place_window(ctx, frame[0], frame[1], frame[2]))) return false;   // (refused: window, origin and pose untouched)
+  } else {                                                      // the pose in the window as it stands: window metres, fp32
+    local = wp;
+    for (int i = 0; i < 3; ++i) local.entries[4 * i + 3] = (float)((F[4 * i + 3] - (double)o[i]) * (double)cell);
+  }
+  _camera_pose_finder->setCameraPose(local);                    // host copy and device-resident pose (kf_set_pose: "tracked")
+  _frame_id = depth_frame.frameId(); _last_tracked = true; _pending = false;
+  rep.accepted = 1;
+  if (report) *report = rep;
+  const bool resident = _camera_pose_finder->deviceResident();
+  const kf_mat44 kp = to_kf(local);
+  kf_raycast_params rc = {p->_raycast_params.fRayIncrement};
+  return 0 == dm->check(kf_raycast_volume(ctx, p->_switch_params.useRGBData, resident ? nullptr : &kp, &rc, &p->_depth_camera_params,
+                                          p->_depth_prepocess_params.fMinTrunc, p->_depth_prepocess_params.fMaxTrunc));
+}
 bool HybKinectfu::sampleMap(const double* world_m, size_t n, float* distance_m, float* weight, float* gradient, uint8_t* color) {
   if (!_inited || !world_m || n > 0xFFFFFFFFull) return false;
   if (n == 0) return true;

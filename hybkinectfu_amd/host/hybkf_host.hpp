@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 #include "../../include/hybkf.h"
+#include "reloc_search.hpp"
 
 // ---- src/AppParams.h:12-95,156-166 -----------------------------------------------------------------------------------
 struct IOParams { std::string meshFilename, rgbdReadFilename, rgbdWriteFilename, trajReadFilename, trajWriteFilename; };
@@ -342,6 +343,18 @@ public:
   // already streamed into the world soup (setStreamMesh) is not taken back.  bricksRemoved / voxelsCleared (may be nullptr): the call's counts.
   bool eraseMapBox(const float lo_m[3], const float hi_m[3], bool keepInside, unsigned* bricksRemoved = nullptr, uint64_t* voxelsCleared = nullptr);
   bool eraseMapWeak(float minWeight, unsigned* bricksRemoved = nullptr);
+  // relocalise: finds the camera again in this session's map from one depth frame (kf_map_score_poses, kf_map_refine_poses; reloc_search.hpp).  A frame in flight
+  // settles; the frame is uploaded and preprocessed as processNewFrame does (and its vertex pyramid built), nothing is tracked or fused; the valid vertices of pyramid level params.level
+  // (default: the coarsest), at most params.max_points (4096) of them, are the points.  The centre pose is params.guess (camera -> WORLD metres) or the current
+  // pose; around it a lattice of 2 n + 1 candidates per axis (n = 2 on all six), translation steps of params.trans_step (default fSdfTruncation) along the
+  // world's axes, rotation steps of params.rot_step (default atan(fSdfTruncation / median depth): one step moves the median point by one truncation, the
+  // Gauss-Newton basin) about the camera's own centre.  All candidates are scored, the best params.top (16) refined about R * mean(points) + t, scored once
+  // more, and the best of those is accepted when its n_in >= accept_inliers * points, its n_obs >= min_obs and its verdict is neither FEW_PAIRS nor SINGULAR.
+  // On accept: with a store reserved and the pose's frame (hkf_view_frame) different from the window's origin the window is captured and placed there; the
+  // pose is set, the model maps are raycast as loadMap does, and the next processNewFrame is TRACKED from there.  false -- refused, nothing eligible or not
+  // accepted --: pose, window, store, volume and frame id are what they were; only the frame's preprocessing buffers have changed.  The search is a lattice
+  // around a guess: its reach is the lattice's extent and nothing more.  report (may be nullptr): what was found, accepted or not.
+  bool relocalise(const DepthFrameData& depth_frame, const RelocParams& params, RelocReport* report);
   // sampleMap: the map at n points in WORLD metres (world_m: 3 n doubles, the first cube's coordinates -- those of the map mesh's vertices and of worldPose),
   // read where it lies, window and store (kf_map_sample): the position in voxels is x / (double)cell (hkf_query_voxels, map_query_voxels.hpp; cell the
   // fp32 quotient size / resolution).  distance_m: tsdf * fSdfTruncation, the signed distance in metres inside the truncation band (+-fSdfTruncation beyond

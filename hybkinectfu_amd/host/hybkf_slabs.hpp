@@ -67,6 +67,7 @@ public:
   bool alignMap(const std::string&, const Mat44&, Mat44&, kf_align_report*) { return false; }
   bool eraseMapBox(const float*, const float*, bool, unsigned* = nullptr, uint64_t* = nullptr) { return false; }
   bool eraseMapWeak(float, unsigned* = nullptr) { return false; }
+  bool relocalise(const DepthFrameData&, const RelocParams&, RelocReport*) { return false; }     // always refused: no store, part of a window each
   bool sampleMap(const double*, size_t, float*, float*, float*, uint8_t*) { return false; }
   bool castMapRays(const double*, const float*, const float*, const float*, size_t, uint8_t*, float*, float*, uint8_t*, float*) { return false; }
   bool distanceFieldVoxels(const int32_t*, const uint32_t*, uint32_t, float, uint32_t, uint16_t*, uint8_t*) { return false; }

@@ -139,6 +139,8 @@ int hkf_slabs_load_map_coarser(const char*) { return -1; }
 int hkf_slabs_erase_map_box(const float*, const float*, int, uint64_t*) { return -1; }
 int hkf_slabs_erase_map_weak(float, uint64_t*) { return -1; }
 // querying the map reads window and brick store: always -1, nothing written
+// HybKinectfuSlabs::relocalise: slab groups hold part of a window each and no store -- always refused, nothing touched
+int hkf_slabs_relocalise(const uint16_t*, unsigned, const RelocParams*, RelocReport*) { return -1; }
 int hkf_slabs_sample_map(const double*, uint32_t, float*, float*, float*, uint8_t*) { return -1; }
 int hkf_slabs_cast_map_rays(const double*, const float*, const float*, const float*, uint32_t, uint8_t*, float*, float*, uint8_t*, float*) { return -1; }
 // so does the distance field: always -1, nothing written

@@ -277,6 +277,17 @@ class App:
             raise K.KfError("hkf_app_sample_map failed")
         return out
 
+    def relocalise(self, mm, frame_id, params=None):
+        """HybKinectfu::relocalise: finds the camera again in this session's map from the depth frame mm -- a lattice of candidate poses around params.guess
+        (or the current pose) scored against the map, the best refined.  params: reloc_params(...), None for the defaults.  Returns (accepted, the report as
+        a dict); accepted: the pose is set and the next process_frame tracks from it; otherwise nothing of the session changed"""
+        mm = np.ascontiguousarray(mm, np.uint16)
+        rep = RelocReport()
+        r = self.h.hkf_app_relocalise(mm.ctypes.data_as(C.c_void_p), C.c_uint(int(frame_id)), C.byref(params) if params is not None else None, C.byref(rep))
+        if r < 0:
+            raise K.KfError("hkf_app_relocalise: no application")
+        return bool(r), _report_dict(rep)
+
     def cast_map_rays(self, origins, dirs, t_min, t_max):
         """HybKinectfu::castMapRays: the first surface crossing of rays through this session's map: origins (n, 3) in WORLD metres, dirs (n, 3) used as
         given (unit vectors: t is metres), t_min / t_max (n,) or scalars in metres; the march steps by the raycaster's increment.  A dict of numpy arrays:
@@ -353,6 +364,81 @@ def map_file_info(path):
 
 SLABS_LIB = os.path.join(K.PKG_DIR, "libhybkf_slabs.so")
 _s = None
+
+
+class RelocParams(C.Structure):
+    """host/reloc_search.hpp: RelocParams"""
+    _fields_ = [("has_guess", C.c_int32), ("guess", C.c_float * 16), ("trans_step", C.c_float), ("rot_step", C.c_float), ("n", C.c_int32 * 6),
+                ("top", C.c_uint32), ("max_points", C.c_uint32), ("level", C.c_int32), ("min_obs", C.c_uint32), ("band", C.c_float), ("gate", C.c_float),
+                ("accept_inliers", C.c_float), ("max_iter", C.c_uint32), ("min_pairs", C.c_uint32), ("eps_rot", C.c_double), ("eps_trans", C.c_double)]
+
+
+class PoseScore(C.Structure):
+    _fields_ = [("n_obs", C.c_uint32), ("n_in", C.c_uint32), ("n_behind", C.c_uint32), ("n_free", C.c_uint32), ("sum_q", C.c_uint64)]
+
+
+class RelocReport(C.Structure):
+    """host/reloc_search.hpp: RelocReport"""
+    _fields_ = [("candidates", C.c_uint32), ("points", C.c_uint32), ("best_index", C.c_uint32), ("verdict", C.c_uint32), ("iterations", C.c_uint32),
+                ("accepted", C.c_int32), ("best_score", PoseScore), ("refined_score", PoseScore), ("best_pose", C.c_double * 12), ("refined_pose", C.c_double * 12),
+                ("median_depth", C.c_float), ("trans_step", C.c_float), ("rot_step", C.c_float)]
+
+
+def reloc_params(guess=None, **kw):
+    """the defaults of HybKinectfu::relocalise (hkf_reloc_defaults_get) with the given fields replaced; guess: a 4x4 camera -> WORLD metres pose; n: six ints"""
+    par = RelocParams()
+    load().hkf_reloc_defaults_get(C.byref(par))
+    if guess is not None:
+        par.has_guess = 1
+        par.guess = (C.c_float * 16)(*np.asarray(guess, np.float32).reshape(16).tolist())
+    for k, v in kw.items():
+        if k == "n":
+            par.n = (C.c_int32 * 6)(*[int(x) for x in v])
+        else:
+            assert hasattr(par, k), k
+            setattr(par, k, v)
+    return par
+
+
+def _report_dict(rep):
+    sc = lambda s: {k: int(getattr(s, k)) for k in ("n_obs", "n_in", "n_behind", "n_free", "sum_q")}
+    return dict(candidates=rep.candidates, points=rep.points, best_index=rep.best_index, verdict=rep.verdict, iterations=rep.iterations, accepted=bool(rep.accepted),
+                best_score=sc(rep.best_score), refined_score=sc(rep.refined_score), best_pose=np.array(rep.best_pose[:]).reshape(3, 4),
+                refined_pose=np.array(rep.refined_pose[:]).reshape(3, 4), median_depth=rep.median_depth, trans_step=rep.trans_step, rot_step=rep.rot_step)
+
+
+def reloc_points(verts, cell, max_points):
+    """hkf_reloc_points: (the points (n, 3) float32 in voxels, the median depth in metres) of a float4 vertex map in metres"""
+    v = np.ascontiguousarray(verts, np.float32).reshape(-1, 4)
+    out, med = np.zeros((max(int(max_points), 1), 3), np.float32), C.c_float(0)
+    h = load()
+    h.hkf_reloc_points.restype = C.c_uint32
+    n = h.hkf_reloc_points(K._p(v), C.c_uint32(len(v)), C.c_float(cell), C.c_uint32(int(max_points)), K._p(out), C.byref(med))
+    return out[:n].copy(), med.value
+
+
+def reloc_lattice(centre, n, trans_step, rot_step):
+    """hkf_reloc_lattice: the candidate poses (K, 3, 4) around centre [R | t] (3, 4), or None when refused"""
+    c = np.ascontiguousarray(centre, np.float64).reshape(12)
+    nn = (C.c_int32 * 6)(*[int(x) for x in n])
+    h = load()
+    h.hkf_reloc_lattice.restype = C.c_int64
+    k = h.hkf_reloc_lattice(K._p(c), nn, C.c_double(trans_step), C.c_double(rot_step), None, C.c_int64(0))
+    if k < 0:
+        return None
+    out = np.zeros((k, 3, 4), np.float64)
+    h.hkf_reloc_lattice(K._p(c), nn, C.c_double(trans_step), C.c_double(rot_step), K._p(out), C.c_int64(k))
+    return out
+
+
+def reloc_rank(scores, min_obs, m):
+    """hkf_reloc_rank: (the best min(m, eligible) indices, how many poses were eligible) of a K.POSE_SCORE_DTYPE array"""
+    sc = np.ascontiguousarray(scores, K.POSE_SCORE_DTYPE)
+    best = np.zeros(max(int(m), 1), np.uint32)
+    h = load()
+    h.hkf_reloc_rank.restype = C.c_uint32
+    e = h.hkf_reloc_rank(K._p(sc), C.c_uint32(len(sc)), C.c_uint32(int(min_obs)), C.c_uint32(int(m)), K._p(best))
+    return best[:min(int(m), e)].copy(), int(e)
 
 
 def load_slabs():
@@ -484,6 +570,11 @@ class SlabsApp:
         pts = np.ascontiguousarray(points, np.float64).reshape(-1, 3)
         r = self.h.hkf_slabs_sample_map(K._p(pts), C.c_uint32(len(pts)), None, None, None, None)
         raise K.KfError("hkf_slabs_sample_map: slab groups have no map queries (%d)" % r)
+
+    def relocalise(self, mm, frame_id, params=None):
+        """always refused (K.KfError), nothing touched: relocalisation reads window and brick store, which a slab group does not have"""
+        r = self.h.hkf_slabs_relocalise(None, C.c_uint(int(frame_id)), None, None)
+        raise K.KfError("hkf_slabs_relocalise: slab groups cannot relocalise (%d)" % r)
 
     def cast_map_rays(self, origins, dirs, t_min, t_max):
         """always refused (K.KfError), as sample_map"""

@@ -129,6 +129,7 @@ SYMBOLS = [
     "kf_brick_store_erase_box", "kf_brick_store_erase_weak",
     "kf_map_sample", "kf_map_sample_device", "kf_map_cast_rays", "kf_map_cast_rays_device",
     "kf_map_distance_field", "kf_map_distance_field_device",
+    "kf_map_score_poses", "kf_map_score_poses_device", "kf_map_pose_sums", "kf_map_refine_poses",
     "kf_marching_cubes_at", "kf_marching_cubes_map", "kf_map_tile_frames",
     "kf_slab_layer_bytes", "kf_slab_shift_needs", "kf_slab_needs", "kf_slab_pack_layers", "kf_shift_slab",
 ]
@@ -193,6 +194,10 @@ def load():
             f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 5
         for f in (_lib.kf_map_cast_rays, _lib.kf_map_cast_rays_device):
             f.argtypes = [C.c_void_p, C.c_uint32] + [C.c_void_p] * 4 + [C.c_float, C.c_uint32] + [C.c_void_p] * 5
+        for f in (_lib.kf_map_score_poses, _lib.kf_map_score_poses_device):
+            f.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_float, C.c_void_p]
+        _lib.kf_map_pose_sums.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+        _lib.kf_map_refine_poses.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(RefineParams), C.c_void_p]
         for f in (_lib.kf_map_distance_field, _lib.kf_map_distance_field_device):
             f.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_uint32), C.c_uint32, C.c_float, C.c_uint32, C.c_void_p, C.c_void_p]
         _lib.kf_marching_cubes_at.argtypes = [C.c_void_p, C.c_int, C.c_float, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_int]
@@ -273,6 +278,14 @@ class AlignParams(C.Structure):
 
 class AlignReport(C.Structure):
     _fields_ = [("iterations", C.c_uint32), ("verdict", C.c_uint32), ("sums", C.c_double * 29), ("rms", C.c_double), ("step", C.c_double * 6)]
+
+
+class RefineParams(C.Structure):
+    _fields_ = [("max_iter", C.c_uint32), ("min_pairs", C.c_uint32), ("eps_rot", C.c_double), ("eps_trans", C.c_double), ("gate", C.c_float)]
+
+
+# kf_pose_score: 24 bytes per pose
+POSE_SCORE_DTYPE = np.dtype([("n_obs", "<u4"), ("n_in", "<u4"), ("n_behind", "<u4"), ("n_free", "<u4"), ("sum_q", "<u8")])
 
 
 def align_params(centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
@@ -976,6 +989,44 @@ class Context:
         ptr = [C.c_void_p(x) if x else None for x in (dev_origin, dev_dir, dev_tmin, dev_tmax, dev_status, dev_t, dev_normal, dev_color, dev_weight)]
         _chk(self.lib.kf_map_cast_rays_device(self.h, int(n), ptr[0], ptr[1], ptr[2], ptr[3], C.c_float(step), int(max_steps), *ptr[4:]),
              "kf_map_cast_rays_device")
+
+    def map_score_poses(self, points, poses, band):
+        """candidate camera poses scored against the map: points (n, 3) fp32 in the camera frame, voxel units; poses (k, 3, 4) fp64 [R | t], camera -> world
+        voxels; band in (0, 1], tsdf units.  A (k,) array of POSE_SCORE_DTYPE: points observed, in the band, behind a surface, in free space, and the sum of
+        the quantised |tsdf| (kf_map_score_poses)"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        out = np.zeros(len(poses), POSE_SCORE_DTYPE)
+        _chk(self.lib.kf_map_score_poses(self.h, len(points), _p(points), len(poses), _p(poses), C.c_float(band), _p(out)), "kf_map_score_poses")
+        return out
+
+    def map_score_poses_device(self, n_points, dev_points, n_poses, dev_poses, band, dev_scores):
+        """map_score_poses with device pointers (integers), on the context's stream, non-blocking (kf_map_score_poses_device)"""
+        _chk(self.lib.kf_map_score_poses_device(self.h, int(n_points), C.c_void_p(dev_points), int(n_poses), C.c_void_p(dev_poses), C.c_float(band),
+                                                C.c_void_p(dev_scores)), "kf_map_score_poses_device")
+
+    def map_pose_sums(self, points, poses, centres, gate):
+        """the 29 Gauss-Newton sums (kf_align_brick_store's layout) of each pose, (k, 29) fp64: points and poses as map_score_poses takes them, centres
+        (k, 3) fp64 in world voxels, gate in (0, 1] (kf_map_pose_sums)"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        poses = np.ascontiguousarray(poses, np.float64).reshape(-1, 12)
+        centres = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+        assert len(centres) == len(poses)
+        out = np.zeros((len(poses), 29), np.float64)
+        _chk(self.lib.kf_map_pose_sums(self.h, len(points), _p(points), len(poses), _p(poses), _p(centres), C.c_float(gate), _p(out)), "kf_map_pose_sums")
+        return out
+
+    def map_refine_poses(self, points, poses, centres, gate, max_iter=25, min_pairs=100, eps_rot=1e-9, eps_trans=1e-9):
+        """Gauss-Newton from each pose on the map's distance at the points, all poses in one launch per iteration: (the refined poses (k, 3, 4), a list of
+        k dicts of iterations, verdict (ALIGN_*), sums (29,), rms, step (6,)) (kf_map_refine_poses)"""
+        points = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+        poses = np.array(poses, np.float64).reshape(-1, 12)
+        centres = np.ascontiguousarray(centres, np.float64).reshape(-1, 3)
+        assert len(centres) == len(poses)
+        par = RefineParams(int(max_iter), int(min_pairs), float(eps_rot), float(eps_trans), float(gate))
+        reps = (AlignReport * len(poses))()
+        _chk(self.lib.kf_map_refine_poses(self.h, len(points), _p(points), len(poses), _p(poses), _p(centres), C.byref(par), reps), "kf_map_refine_poses")
+        return poses.reshape(-1, 3, 4), [dict(iterations=r.iterations, verdict=r.verdict, sums=np.array(r.sums[:]), rms=r.rms, step=np.array(r.step[:])) for r in reps]
 
     def map_distance_field(self, lo_vox, dims, radius, level=0.0, site_mask=1 << VOX_OCCUPIED, want=("dist2", "cls")):
         """the map's distance field over the box of world voxels lo_vox (x, y, z), dims (nx, ny, nz): a dict of dist2 (nz, ny, nx) uint16 -- the squared

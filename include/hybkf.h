@@ -786,6 +786,52 @@ int kf_map_sample(kf_ctx* ctx, uint32_t n, const double* pos, float* tsdf, float
 int kf_map_cast_rays_device(kf_ctx* ctx, uint32_t n, const double* dev_origin, const float* dev_dir, const float* dev_tmin, const float* dev_tmax, float step, uint32_t max_steps, uint8_t* dev_status, float* dev_t, float* dev_normal, uint8_t* dev_color, float* dev_weight);
 int kf_map_cast_rays(kf_ctx* ctx, uint32_t n, const double* origin, const float* dir, const float* tmin, const float* tmax, float step, uint32_t max_steps, uint8_t* status, float* t, float* normal, uint8_t* color, float* weight);
 
+/* Relocalising a frame in the map: many candidate camera poses of one point set scored against the map, and the best few refined by Gauss-Newton on the
+ * map's distance at the points (no reference counterpart: the reference blocks on a key press when the camera is lost).  The map, its weights and the sample
+ * are those written above kf_map_sample; nothing of the context changes: volume, store, deferred-weight words, pose, model maps, scratch and every later
+ * frame are bit for bit what they would have been.  Colour plays no part.
+ * Points: 3 x fp32 per point, in the CAMERA frame, in voxel units (metres / cell), used as given.  Poses: 12 x fp64 per pose, row-major [R | t], camera ->
+ *   world voxels, t at entries 3, 7 and 11 as in kf_align_step's xf.  Poses are NOT checked for being rigid.
+ * Position of point (x, y, z) under a pose, per axis j, all in fp64 with one rounding per operation:
+ *     w_j = ((R[j][0] * (double)x + R[j][1] * (double)y) + R[j][2] * (double)z) + t[j].
+ * kf_map_score_poses: per pose five integers over the points.  The value at w is kf_map_sample's tsdf -- the same bits, the same observed rule (all eight
+ *   corners with TRUE weight > 0; a w that is not finite or lies outside +-2^23 reads unobserved).  An observed point, with a = fabsf(tsdf): counts in
+ *   n_obs; a < band: n_in; otherwise tsdf < 0: n_behind (the point lies inside an object); otherwise n_free (it floats in observed free space);
+ *   sum_q += (uint32_t)(fminf(a, 1.f) * 65536.f) (the product is exact, the conversion truncates: at most 65536 per point).  n_obs = n_in + n_behind + n_free.
+ *   Integers, because integer addition commutes: the bytes do not depend on the grid, the chunking or the order in which workgroups arrive, so no fold order
+ *   has to be fixed and any pose count fills the chip.  A pose with a NaN in it scores all zeros.
+ *   The _device form takes device pointers, runs on the context's stream (it zeroes dev_scores there first) and does not block; the other takes host
+ *   pointers: one temporary allocation, copies, and it blocks.
+ *   Refused with nothing written -- KF_ERR_ARG: a NULL context, points, poses or scores; n_points 0 or > 2^24; n_poses 0 or > 2^20; band not finite, not > 0
+ *   or > 1.  KF_ERR_STATE: a z-slab context.  KF_ERR_ALLOC: the host form's temporary does not fit.
+ * kf_map_pose_sums: the 29 sums of kf_align_brick_store's layout for each of n_poses (at most 4096) poses, one launch.  Point i under pose k: w as above; phi
+ *   and g = kf_map_sample's tsdf and grad at w; the point takes part when it is observed and fabsf(phi) < gate, gate in (0, 1];
+ *   x_j = (float)(w_j - centre_k[j]), the difference in fp64;  J = (x_1 g_2 - x_2 g_1, x_2 g_0 - x_0 g_2, x_0 g_1 - x_1 g_0, g_0, g_1, g_2), every product and
+ *   difference rounded once, in fp32;  e = -phi.  Sums per pose: [0, 21) the upper triangle of sum J_a J_b row by row, [21, 27) sum J_a e, [27] sum e e,
+ *   [28] the number of points that took part, counted in integers; every product is formed in fp64 from its fp32 factors, hence exact.
+ *   kf_align_step(sums, centre, pose, step) applies to them unchanged: under a left twist xi = (omega, v) about the centre, pose <- T(c) exp(xi) T(-c) pose,
+ *   a point moves by omega x (w - c) + v, so d phi = g . (omega x x + v) = J . xi and e' = e - J . xi: the step solves (sum J J^T) xi = sum J e.
+ *   The fold is fixed, so the same inputs give the same 29 doubles bit for bit on every run and in every context: with G = min(ceil(n_points / 256), 64),
+ *   point i belongs to workgroup (i / 256) % G of its pose, lane i % 256; a lane adds its points in ascending order; the wave's lanes fold by the butterfly
+ *   xor 32 .. 1; the four waves as ((w0 + w1) + w2) + w3; the G rows are added in ascending order.  No atomic on a float anywhere.
+ * kf_map_refine_poses: kf_align_brick_store's loop, per pose: evaluate the sums; KF_ALIGN_FEW_PAIRS when fewer than max(min_pairs, 1) points took part;
+ *   KF_ALIGN_ITER_LIMIT when max_iter steps are done; a kf_align_step, KF_ALIGN_SINGULAR when it refuses; KF_ALIGN_CONVERGED when the step has |omega| <=
+ *   eps_rot and |v| <= eps_trans (the stepped pose is the result; it is not evaluated again).  An eps below KF_ALIGN_EPS_ROT_MIN / KF_ALIGN_EPS_TRANS_MIN is
+ *   raised to it: the sample's fraction is fp32 here too.  The stepped pose is not checked for being rigid (the poses that go in are not either).  All the
+ *   poses still running are evaluated in one launch per iteration, with one read-back of 29 doubles per running pose; a pose's result does not depend on
+ *   what else is in the batch.  poses is in / out.  On FEW_PAIRS and SINGULAR a pose is the last one evaluated with enough pairs (the guess, if none).
+ *   max_iter == 0 evaluates the sums, reports them (KF_ALIGN_ITER_LIMIT) and leaves the poses alone.  reports: one per pose, as kf_align_brick_store's.
+ *   centres: 3 x fp64 per pose, world voxels: the point rotations are taken about -- the middle of the points under the pose keeps sum J J^T well conditioned.
+ *   Both calls take host pointers and block.  Refused with nothing written -- as kf_map_score_poses (n_poses > 4096; gate in place of band), and KF_ERR_ARG
+ *   for a NULL centres, sums, params or reports, an eps that is negative or not finite, a centre or pose entry that is not finite. */
+typedef struct kf_pose_score { uint32_t n_obs, n_in, n_behind, n_free; uint64_t sum_q; } kf_pose_score;   /* 24 bytes */
+typedef struct kf_refine_params { uint32_t max_iter, min_pairs; double eps_rot, eps_trans; float gate; } kf_refine_params;
+struct kf_align_report;
+int kf_map_score_poses_device(kf_ctx* ctx, uint32_t n_points, const float* dev_points, uint32_t n_poses, const double* dev_poses, float band, kf_pose_score* dev_scores);
+int kf_map_score_poses(kf_ctx* ctx, uint32_t n_points, const float* points, uint32_t n_poses, const double* poses, float band, kf_pose_score* scores);
+int kf_map_pose_sums(kf_ctx* ctx, uint32_t n_points, const float* points, uint32_t n_poses, const double* poses, const double* centres, float gate, double* sums);
+int kf_map_refine_poses(kf_ctx* ctx, uint32_t n_points, const float* points, uint32_t n_poses, double* poses, const double* centres, const kf_refine_params* params, struct kf_align_report* reports);
+
 /* The distance field of the map: for every voxel of a box the exact squared Euclidean distance, in voxels, to the nearest SITE of the map, up to a radius --
  * the clearance a planner asks for beyond the truncation band (no reference counterpart).
  * The map as a function of a world voxel g is the one written above kf_map_sample: the window's copy where the voxel's brick is inside the window, else the
@@ -827,7 +873,7 @@ int kf_map_distance_field(kf_ctx* ctx, const int32_t lo_vox[3], const uint32_t d
 /* Aligning two maps: the rigid transform kf_merge_brick_store_rigid needs, found by Gauss-Newton on the SDF-to-SDF error between the store and an incoming
  * map (no reference counterpart).  A REFINEMENT, not a global search: its basin is about the truncation band -- on an analytic box with a band of four
  * voxels a start 10 degrees and about 5 voxels off still converges; a start much further off finds too few pairs or a wrong minimum.  Coarse-to-fine search
- * and global relocalisation are not offered.
+ * and global alignment of two maps are not offered (for a depth FRAME against the map, see kf_map_score_poses: a lattice of poses scored, the best refined).
  * The destination is the brick store as held (read only): a key inside the current window is shadowed by the window's copy, so call
  * kf_brick_store_capture first.  The source is an incoming map in kf_read_brick_store's layout (count entries: keys, tsdf, weight).  xf is the rigid
  * merge's [R | t]: row-major 3x4, source world -> destination world, t in voxels, VALID as defined above.  Colour plays no part.
