@@ -1,13 +1,14 @@
 // align.hip -- aligning two maps: the rigid transform a map merge needs, found by Gauss-Newton on the SDF-to-SDF error between the brick store and an
 // incoming map.  No reference counterpart.  The rule is written out above kf_align_brick_store in include/hybkf.h; one evaluation of the 29 sums is the
-// kernel below, the step from the sums to the next transform is align_step.h (host, fp64), the source keys' check and table and a brick's base corner are
+// kernel below -- how a row enters them and how a workgroup folds them is align_rows.h, shared with relocal.hip --, the step from the sums to the next
+// transform and the turn of the loop that gives the verdicts are align_step.h (host, fp64), the source keys' check and table and a brick's base corner are
 // rigid_keys.h, the source's upload, its 27 bricks around a held one and a corner's fetch are the rigid merge's (resample_shared.h).
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"
 #include "rigid_keys.h"
 #include "resample_shared.h"
-#include "align_step.h"
+#include "align_rows.h"
 #include <stdint.h>
 #include <string.h>
 #include <algorithm>
@@ -15,12 +16,10 @@
 #include <vector>
 
 #define KF_ALIGN_MAX_GROUPS 1024u      // the grid is min(held, this): a fixed function of the held count, so the fold order is too
-// the transform and the centre, by value: every index is a constant, the 15 doubles stay in scalar registers
-struct KfAlignXf { double m[12]; double c[3]; };
 
 // One held voxel in the band: td its tsdf, (ux, uy, uz) its source position relative to the brick's base corner (ibx, iby, ibz), (xx, xy, xz) its position
 // relative to the centre.  All eight corners floor(u) + {0, 1}^3 are read; one that the source does not hold, whose weight is not > 0 or whose |tsdf| is
-// not < 1 leaves the voxel out.  s_src, (b0x, b0y, b0z): source_bricks27's.  Adds the voxel's 28 exact products to acc in fp64 and 1 to n.
+// not < 1 leaves the voxel out.  s_src, (b0x, b0y, b0z): source_bricks27's.  Adds the voxel's row to acc and n (align_row_add).
 __device__ __forceinline__ void align_voxel(const KfResampleSource& src, const unsigned* s_src, float td, float ux, float uy, float uz, int ibx, int iby, int ibz,
                                             int b0x, int b0y, int b0z, float xx, float xy, float xz, float r00, float r01, float r02, float r10, float r11,
                                             float r12, float r20, float r21, float r22, double (&acc)[28], unsigned& n) {
@@ -47,15 +46,7 @@ __device__ __forceinline__ void align_voxel(const KfResampleSource& src, const u
   const float gdx = (r00 * gx + r01 * gy) + r02 * gz, gdy = (r10 * gx + r11 * gy) + r12 * gz, gdz = (r20 * gx + r21 * gy) + r22 * gz;
   const double J[6] = {(double)(xy * gdz - xz * gdy), (double)(xz * gdx - xx * gdz), (double)(xx * gdy - xy * gdx), (double)gdx, (double)gdy, (double)gdz};
   const double e = (double)(phi - td);
-  int k = 0;
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int b = a; b < 6; ++b, ++k) acc[k] += J[a] * J[b];      // (a product of two fp32 values is exact in fp64)
-#pragma unroll
-  for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * e;
-  acc[27] += e * e;
-  n += 1u;
+  align_row_add(J, e, acc, n);
 }
 
 // The sums of one evaluation for kf_align_brick_store.  One workgroup iteration per held slot, 256 lanes x 2 x-adjacent voxels (the slot's float4); the
@@ -66,13 +57,12 @@ __device__ __forceinline__ void align_voxel(const KfResampleSource& src, const u
 // goes on only with both.  The word is one of three in rotation (the one used two iterations later is cleared after this iteration's barrier, which every
 // lane has passed before it can write to it), the 27 slots one of two sets (a lane can write the other set while a slower one still reads this one, and
 // reaches this one again only past the next barrier).
-// Every lane keeps 28 fp64 sums and an integer count across its iterations; at the end the waves fold theirs by a fixed butterfly, the four waves' results
-// meet in LDS in wave order and the workgroup writes its row of 29 doubles: no atomic on a float anywhere, the same bits on every run.
+// Every lane keeps 28 fp64 sums and an integer count across its iterations (at most 2^20 iterations of 512 voxels); at the end the workgroup folds them in a
+// fixed order and writes its row of 29 doubles (align_rows_fold): no atomic on a float anywhere, the same bits on every run.
 __global__ void __launch_bounds__(256) k_store_align_sums(KfBrickStore st, KfBrickStore stab, KfResampleSource src, unsigned held, KfAlignXf xf,
                                                           const unsigned* __restrict__ order, double* __restrict__ rows) {
   __shared__ unsigned s_src[2][27];
   __shared__ unsigned s_flag[3];
-  __shared__ double s_red[4][KF_ALIGN_SUMS];
   const float r00 = (float)xf.m[0], r01 = (float)xf.m[1], r02 = (float)xf.m[2], r10 = (float)xf.m[4], r11 = (float)xf.m[5], r12 = (float)xf.m[6];
   const float r20 = (float)xf.m[8], r21 = (float)xf.m[9], r22 = (float)xf.m[10];
   const float lx = (float)((threadIdx.x & 3u) << 1), ly = (float)((threadIdx.x >> 2) & 7u), lz = (float)(threadIdx.x >> 5);
@@ -123,42 +113,19 @@ __global__ void __launch_bounds__(256) k_store_align_sums(KfBrickStore st, KfBri
                   r20, r21, r22, acc, n);
     }
   }
-  // the wave's lanes by a butterfly (every lane ends with the same sum), the four waves in order
-#pragma unroll
-  for (int k = 0; k < 28; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-    acc[k] = v;
-  }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) n += (unsigned)__shfl_xor((int)n, m);
-  if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-    for (int k = 0; k < 28; ++k) s_red[threadIdx.x >> 6][k] = acc[k];
-    s_red[threadIdx.x >> 6][28] = (double)n;                                  // (at most 2^20 iterations of 512 voxels: the integer and the double are exact)
-  }
-  __syncthreads();
-  if (threadIdx.x < KF_ALIGN_SUMS)
-    rows[(size_t)blockIdx.x * KF_ALIGN_SUMS + threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+  align_rows_fold(acc, n, rows + (size_t)blockIdx.x * KF_ALIGN_SUMS);
 }
 
 extern "C" int kf_align_step(const double sums[29], const double centre[3], double xf[12], double step[6]) {
   return kf_align_step_host(sums, centre, xf, step);
 }
 
-static bool align_params_valid(const kf_align_params* p) {
-  if (!isfinite(p->eps_rot) || !isfinite(p->eps_trans) || p->eps_rot < 0.0 || p->eps_trans < 0.0) return false;
-  for (int k = 0; k < 3; ++k) if (!isfinite(p->centre[k])) return false;
-  return true;
-}
-
 extern "C" int kf_align_brick_store(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, double xf[12],
                                     const kf_align_params* params, kf_align_report* report) {
   if (!c || !xf || !params || !report) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;       // a z-slab context has no store
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;                // a z-slab context has no store
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
-  if ((count && (!keys || !tsdf || !weight)) || !kf_rigid_valid(xf) || !align_params_valid(params)) return KF_ERR_ARG;
+  if ((count && (!keys || !tsdf || !weight)) || !kf_rigid_valid(xf) || !kf_align_stop_valid(params->eps_rot, params->eps_trans, params->centre, 1)) return KF_ERR_ARG;
   if (count > (1u << 30)) return KF_ERR_ALLOC;               // (as kf_merge_brick_store_rigid: the source table's probe counts entries in 32 bits)
   std::vector<unsigned long long> tkey;
   std::vector<unsigned> tslot;
@@ -195,16 +162,15 @@ extern "C" int kf_align_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
     const hipError_t se = hipStreamSynchronize(c->stream);   // on success and on failure alike: nothing still reads the caller's arrays
     if (e != hipSuccess || se != hipSuccess) return (int)(e != hipSuccess ? e : se);
   }
-  kf_align_report rep;
-  memset(&rep, 0, sizeof(rep));
-  double cur[12], good[12];
-  memcpy(cur, xf, sizeof(cur)); memcpy(good, xf, sizeof(good));
-  for (;;) {
-    // the sums at `cur`: one row per workgroup, folded here in index order
-    double sums[KF_ALIGN_SUMS] = {};
+  KfAlignLoop loop;
+  kf_align_loop_begin(loop, xf);
+  double sums[KF_ALIGN_SUMS];
+  do {
+    // the sums at loop.cur: one row per workgroup, folded here in index order
+    memset(sums, 0, sizeof(sums));
     if (groups) {
-      KfAlignXf kx;
-      memcpy(kx.m, cur, sizeof(kx.m)); memcpy(kx.c, params->centre, sizeof(kx.c));
+      KfAlignXf kx;                                          // by value: every index is a constant, the 15 doubles stay in scalar registers
+      memcpy(kx.m, loop.cur, sizeof(kx.m)); memcpy(kx.c, params->centre, sizeof(kx.c));
       hipLaunchKernelGGL(k_store_align_sums, dim3(groups), dim3(256), 0, c->stream, c->bstore, stab, src, (unsigned)held, kx, dorder, drows);
       e = hipGetLastError();
       if (e == hipSuccess) e = hipMemcpyAsync(rows.data(), drows, (size_t)groups * KF_ALIGN_SUMS * sizeof(double), hipMemcpyDeviceToHost, c->stream);
@@ -213,19 +179,8 @@ extern "C" int kf_align_brick_store(kf_ctx* c, uint32_t count, const int32_t* ke
       for (unsigned g = 0; g < groups; ++g)
         for (int k = 0; k < KF_ALIGN_SUMS; ++k) sums[k] += rows[(size_t)g * KF_ALIGN_SUMS + k];
     }
-    memcpy(rep.sums, sums, sizeof(sums));
-    rep.rms = sums[28] > 0.0 ? sqrt(sums[27] / sums[28]) : 0.0;
-    if (!(sums[28] > 0.0) || sums[28] < (double)params->min_pairs) { rep.verdict = KF_ALIGN_FEW_PAIRS; break; }
-    memcpy(good, cur, sizeof(good));                         // evaluated successfully
-    if (rep.iterations >= params->max_iter) { rep.verdict = KF_ALIGN_ITER_LIMIT; break; }
-    double step[6];
-    if (kf_align_step_host(sums, params->centre, cur, step) || !kf_rigid_valid(cur)) { rep.verdict = KF_ALIGN_SINGULAR; break; }
-    rep.iterations += 1u;
-    memcpy(rep.step, step, sizeof(step));
-    const double rot = sqrt(step[0] * step[0] + step[1] * step[1] + step[2] * step[2]), tr = sqrt(step[3] * step[3] + step[4] * step[4] + step[5] * step[5]);
-    if (rot <= fmax(params->eps_rot, KF_ALIGN_EPS_ROT_MIN) && tr <= fmax(params->eps_trans, KF_ALIGN_EPS_TRANS_MIN)) { rep.verdict = KF_ALIGN_CONVERGED; memcpy(good, cur, sizeof(good)); break; }
-  }
-  memcpy(xf, good, sizeof(good));
-  *report = rep;
+  } while (kf_align_loop_turn(loop, sums, params->centre, params->max_iter, params->min_pairs, params->eps_rot, params->eps_trans, true));
+  memcpy(xf, loop.good, sizeof(loop.good));
+  *report = loop.rep;
   return 0;
 }

@@ -1,11 +1,15 @@
-// align_step.h -- the host side of aligning two maps (align.hip, kf_align_brick_store; no reference counterpart): one Gauss-Newton step from the 29 sums to
-// the updated transform.  Plain host C++, fp64: the library and the stand-alone test program (tests/map_align_main.cpp) both include it.  The rule is
-// written out above kf_align_brick_store in include/hybkf.h.
+// align_step.h -- the host side of aligning two maps (align.hip, kf_align_brick_store) and of refining poses in the map (relocal.hip, kf_map_refine_poses); no
+// reference counterpart: one Gauss-Newton step from the 29 sums to the updated transform, and one turn of the loop around it -- the only place that gives
+// a verdict (kf_align_loop_turn).  Plain host C++, fp64: the library and the stand-alone test program (tests/map_align_main.cpp) both include it.  The rule
+// is written out above kf_align_brick_store in include/hybkf.h.
 //
 // sums: [0, 21) the upper triangle of A = sum J J^T, row by row ((0,0), (0,1) .. (0,5), (1,1) .. (5,5)); [21, 27) b = sum J e; [27] sum e e; [28] the pair
 // count.  J = (x cross gd, gd): the first three unknowns are the rotation vector omega (radians, about `centre`), the last three the translation v (voxels).
 #pragma once
 #include <math.h>
+#include <string.h>
+#include "../../include/hybkf.h"
+#include "rigid_keys.h"
 
 #define KF_ALIGN_SUMS 29
 
@@ -78,4 +82,41 @@ static inline int kf_align_step_host(const double* sums, const double* centre, d
   for (int i = 0; i < 12; ++i) xf[i] = out[i];
   for (int i = 0; i < 6; ++i) step[i] = xi[i];
   return 0;
+}
+
+// eps_rot and eps_trans finite and >= 0, the n centres (3 doubles each) finite: what both loops ask of their stopping rule
+static inline bool kf_align_stop_valid(double eps_rot, double eps_trans, const double* centres, size_t n) {
+  if (!isfinite(eps_rot) || !isfinite(eps_trans) || eps_rot < 0.0 || eps_trans < 0.0) return false;
+  for (size_t i = 0; i < 3 * n; ++i) if (!isfinite(centres[i])) return false;
+  return true;
+}
+
+// One pose's loop.  cur: where the next evaluation is taken.  good: the result so far -- the last pose evaluated with enough pairs (the guess, if none), and the
+// stepped pose once the verdict is CONVERGED.  rep: the steps taken, the last evaluation's sums and rms, the last step; its verdict counts once a turn said stop.
+struct KfAlignLoop { double cur[12], good[12]; kf_align_report rep; };
+
+static inline void kf_align_loop_begin(KfAlignLoop& s, const double* xf) {
+  memcpy(s.cur, xf, sizeof(s.cur)); memcpy(s.good, xf, sizeof(s.good));
+  memset(&s.rep, 0, sizeof(s.rep));
+}
+
+// One turn: `sums` are the 29 sums evaluated at s.cur.  True: s.cur is stepped and wants an evaluation; false: s.rep.verdict says why the loop ends, s.good is
+// the result.  require_rigid: a stepped transform that is no longer rigid (kf_rigid_valid) ends the loop like a refused step, iterations and step as they were.
+static inline bool kf_align_loop_turn(KfAlignLoop& s, const double* sums, const double* centre, uint32_t max_iter, uint32_t min_pairs, double eps_rot,
+                                      double eps_trans, bool require_rigid) {
+  kf_align_report& rep = s.rep;
+  memcpy(rep.sums, sums, sizeof(rep.sums));
+  rep.rms = sums[28] > 0.0 ? sqrt(sums[27] / sums[28]) : 0.0;
+  if (!(sums[28] > 0.0) || sums[28] < (double)min_pairs) { rep.verdict = KF_ALIGN_FEW_PAIRS; return false; }
+  memcpy(s.good, s.cur, sizeof(s.good));                         // evaluated successfully
+  if (rep.iterations >= max_iter) { rep.verdict = KF_ALIGN_ITER_LIMIT; return false; }
+  double step[6];
+  if (kf_align_step_host(sums, centre, s.cur, step) || (require_rigid && !kf_rigid_valid(s.cur))) { rep.verdict = KF_ALIGN_SINGULAR; return false; }
+  rep.iterations += 1u;
+  memcpy(rep.step, step, sizeof(step));
+  const double rot = sqrt(step[0] * step[0] + step[1] * step[1] + step[2] * step[2]), tr = sqrt(step[3] * step[3] + step[4] * step[4] + step[5] * step[5]);
+  if (rot <= fmax(eps_rot, KF_ALIGN_EPS_ROT_MIN) && tr <= fmax(eps_trans, KF_ALIGN_EPS_TRANS_MIN)) {
+    rep.verdict = KF_ALIGN_CONVERGED; memcpy(s.good, s.cur, sizeof(s.good)); return false;
+  }
+  return true;
 }

@@ -198,7 +198,7 @@ void kf_brick_store_free(kf_ctx* c) {
 
 extern "C" int kf_brick_store_reserve(kf_ctx* c, uint32_t max_bricks) {
   if (!c) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;       // a z-slab context cannot shift: nothing would ever use the store
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;       // a z-slab context cannot shift: nothing would ever use the store
   KF_CHECK(hipSetDevice(c->cfg.device));
   KF_CHECK(hipStreamSynchronize(c->stream));                 // whatever still reads or writes the old store
   kf_brick_store_free(c);
@@ -282,7 +282,7 @@ int kf_brick_store_capture_enqueue(kf_ctx* c) {
 }
 extern "C" int kf_brick_store_capture(kf_ctx* c) {
   if (!c) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   if (!kf_window_in_key_range(c->origin_vox, c->vol.nb)) return KF_ERR_ARG;   // (a window that shifts with a store reserved never leaves the key range; one that moved before the reserve may have)
   KF_CHECK(hipSetDevice(c->cfg.device));

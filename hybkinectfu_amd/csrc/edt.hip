@@ -131,7 +131,6 @@ __global__ void __launch_bounds__(256) k_edt_pass(const unsigned short* __restri
   }
 }
 
-static inline bool edt_whole_volume(const kf_ctx* c) { return c->vol.bz0 == 0 && c->vol.bz1 == c->vol.nb; }   // a z-slab context holds part of a window and no store
 static inline size_t edt_pad(size_t b) { return (b + 255u) & ~(size_t)255u; }
 static inline unsigned edt_grid(size_t n) { const size_t g = (n + 255u) / 256u; return (unsigned)(g > 8192u ? 8192u : g); }
 
@@ -169,12 +168,10 @@ extern "C" int kf_map_distance_field_device(kf_ctx* c, const int32_t lo_vox[3], 
                                             uint16_t* dev_dist2, uint8_t* dev_cls) {
   uint64_t n_dom = 0;
   { const int as = edt_args(c, lo_vox, dims, radius, level, site_mask, n_dom); if (as) return as; }
-  if (!edt_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (!dev_dist2 && !dev_cls) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
-  MapRef m;
-  m.vol = c->vol; m.st = c->bstore;
-  for (int k = 0; k < 3; ++k) m.ob[k] = c->origin_vox[k] >> 3;          // (a multiple of 8; the shift floors)
+  const MapRef m = query_map(c);
   EdtBox e;
   e.halo = dev_dist2 ? radius : 0u;
   size_t nbricks = 1;
@@ -205,23 +202,18 @@ extern "C" int kf_map_distance_field_device(kf_ctx* c, const int32_t lo_vox[3], 
   return (int)hipGetLastError();
 }
 
-// the host form: one temporary device allocation for the two outputs, copies on the context's stream, one wait
+// the host form: the two outputs in one temporary (KfCarveTemp), one wait
 extern "C" int kf_map_distance_field(kf_ctx* c, const int32_t lo_vox[3], const uint32_t dims[3], uint32_t radius, float level, uint32_t site_mask, uint16_t* dist2,
                                      uint8_t* cls) {
   uint64_t n_dom = 0;
   { const int as = edt_args(c, lo_vox, dims, radius, level, site_mask, n_dom); if (as) return as; }
-  if (!edt_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (!dist2 && !cls) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
-  const size_t n = (size_t)dims[0] * dims[1] * dims[2], b_d = edt_pad(2 * n);
-  char* tmp = nullptr;
-  if (hipMalloc((void**)&tmp, b_d + n) != hipSuccess) { (void)hipGetLastError(); return KF_ERR_ALLOC; }
-  uint16_t* d_d = dist2 ? (uint16_t*)tmp : nullptr;
-  uint8_t* d_c = cls ? (uint8_t*)(tmp + b_d) : nullptr;
-  int st = kf_map_distance_field_device(c, lo_vox, dims, radius, level, site_mask, d_d, d_c);
-  if (!st && d_d) st = (int)hipMemcpyAsync(dist2, d_d, 2 * n, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_c) st = (int)hipMemcpyAsync(cls, d_c, n, hipMemcpyDeviceToHost, c->stream);
-  const int ss = (int)hipStreamSynchronize(c->stream);                   // (also after a failure: the temporary is freed below)
-  hipFree(tmp);
-  return st ? st : ss;
+  const size_t n = (size_t)dims[0] * dims[1] * dims[2];
+  KfCarveTemp tmp;
+  if (!tmp.get(KfCarveTemp::pad(2 * n) + KfCarveTemp::pad(n))) return KF_ERR_ALLOC;
+  uint16_t* d_d = tmp.down(dist2, 2 * n);
+  uint8_t* d_c = tmp.down(cls, n);
+  return tmp.finish(c, kf_map_distance_field_device(c, lo_vox, dims, radius, level, site_mask, d_d, d_c));
 }

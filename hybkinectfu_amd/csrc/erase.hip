@@ -185,7 +185,7 @@ static int erase_run(kf_ctx* c, const KfEraseBox* box, int mode, float min_weigh
 
 extern "C" int kf_brick_store_erase_box(kf_ctx* c, const int32_t lo_vox[3], const int32_t hi_vox[3], int mode, uint32_t* bricks_removed, uint64_t* voxels_cleared) {
   if (!c || !lo_vox || !hi_vox || (mode != KF_ERASE_INSIDE && mode != KF_ERASE_OUTSIDE)) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;       // a z-slab context has no store
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;       // a z-slab context has no store
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   const KfEraseBox box = kf_erase_box_clamped(lo_vox, hi_vox);
   return erase_run(c, &box, mode, 0.f, bricks_removed, voxels_cleared);
@@ -193,7 +193,7 @@ extern "C" int kf_brick_store_erase_box(kf_ctx* c, const int32_t lo_vox[3], cons
 
 extern "C" int kf_brick_store_erase_weak(kf_ctx* c, float min_weight, uint32_t* bricks_removed) {
   if (!c || isnan(min_weight)) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;       // a z-slab context has no store
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;       // a z-slab context has no store
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   return erase_run(c, nullptr, 0, min_weight, bricks_removed, nullptr);
 }

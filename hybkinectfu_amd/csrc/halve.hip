@@ -120,7 +120,7 @@ extern "C" int64_t kf_halved_brick_keys(uint32_t count, const int32_t* keys, int
 
 extern "C" int kf_merge_brick_store_halved(kf_ctx* c, uint32_t count, const int32_t* keys, const float* tsdf, const float* weight, const uint8_t* color) {
   if (!c) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;       // a z-slab context has no store
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;       // a z-slab context has no store
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   if (color && !c->bstore.color) return KF_ERR_STATE;
   if (count == 0) return 0;                                  // nothing to merge: the arrays are not looked at

@@ -288,6 +288,42 @@ void kf_evt_attached_done(kf_ctx* c, int stage);
 
 #define KF_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return (int)e_; } while (0)
 
+// false: a z-slab context, which holds part of a window and no store
+static inline bool kf_whole_volume(const kf_ctx* c) { return c->vol.bz0 == 0 && c->vol.bz1 == c->vol.nb; }
+
+// What a host form (host pointers in and out, blocks) puts around its _device form: one temporary device allocation carved into the arrays (each part a
+// multiple of 16 bytes), copies on the context's stream, one wait.  get() the padded total, then up() every input and down() every output in the order
+// they are carved, call the _device form unless `st` is set, and return finish().
+struct KfCarveTemp {
+  struct Down { void* host; const void* dev; size_t bytes; };
+  char* base = nullptr; size_t used = 0;
+  int st = 0;                          // the first error of a copy up
+  Down downs[6]; int n_down = 0;
+  static size_t pad(size_t b) { return (b + 15) & ~(size_t)15; }
+  bool get(size_t bytes) { if (hipMalloc((void**)&base, bytes) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; } return true; }
+  void* take(size_t bytes) { void* p = base + used; used += pad(bytes); return p; }
+  // an input array: carved and copied up
+  template <class T> T* up(kf_ctx* c, const T* host, size_t bytes) {
+    T* d = (T*)take(bytes);
+    if (!st) st = (int)hipMemcpyAsync(d, host, bytes, hipMemcpyHostToDevice, c->stream);
+    return d;
+  }
+  // an output array the caller may not want (host NULL: nothing carved, NULL): copied down by finish()
+  template <class T> T* down(T* host, size_t bytes) {
+    if (!host) return nullptr;
+    T* d = (T*)take(bytes);
+    downs[n_down].host = host; downs[n_down].dev = d; downs[n_down].bytes = bytes; ++n_down;
+    return d;
+  }
+  // the outputs down when `status` is 0, the wait in any case (the temporary is freed after it): the first error
+  int finish(kf_ctx* c, int status) {
+    for (int k = 0; k < n_down && !status; ++k) status = (int)hipMemcpyAsync(downs[k].host, downs[k].dev, downs[k].bytes, hipMemcpyDeviceToHost, c->stream);
+    const int ss = (int)hipStreamSynchronize(c->stream);
+    return status ? status : ss;
+  }
+  ~KfCarveTemp() { if (base) hipFree(base); }
+};
+
 static inline int kf_div_up(int a, int b) { return (a + b - 1) / b; }
 // words of a packed table of n bits, padded to whole 16-byte vectors
 static inline int kf_bit_words(size_t n_bits) { return (int)((((n_bits + 31) >> 5) + 3) & ~(size_t)3); }

@@ -7,6 +7,13 @@ namespace mapq {
 
 // where the map lies: the window's planes, its origin in world bricks, the store
 struct MapRef { KfVolume vol; KfBrickStore st; int ob[3]; };
+// (host) the map of a whole-volume context (kf_whole_volume)
+static inline MapRef query_map(const kf_ctx* c) {
+  MapRef m;
+  m.vol = c->vol; m.st = c->bstore;
+  for (int k = 0; k < 3; ++k) m.ob[k] = c->origin_vox[k] >> 3;      // (a multiple of 8; the shift floors)
+  return m;
+}
 
 // the last brick a lane resolved: its key, its base pointers (tw == nullptr: nobody holds it) and its four deferred-weight words
 struct MapBrick {

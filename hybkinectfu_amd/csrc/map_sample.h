@@ -1,8 +1,8 @@
 // map_sample.h -- the map sampled at a point (device): the trilinear value with its gradient, weight and colour (query_sample) and the nearest voxel
-// (query_nearest), over the map as map_lookup.h defines it; and what every entry point that samples the map asks of its context (host: query_whole_volume,
-// query_map, QueryTemp).  Shared by query.hip (kf_map_sample, kf_map_cast_rays) and relocal.hip (kf_map_score_poses, kf_map_pose_sums).  No reference
-// counterpart: the value and gradient are align_voxel's lines (align.hip), the colour v_interp_color's (vwindow.h).  The contract is written out above
-// kf_map_sample in include/hybkf.h.  Include after kf_internal.h, brick_key.h, brick_find.h, resample_shared.h (lerp1) and map_lookup.h.
+// (query_nearest), over the map as map_lookup.h defines it (query_map: a context's).  Shared by query.hip (kf_map_sample, kf_map_cast_rays) and relocal.hip
+// (kf_map_score_poses, kf_map_pose_sums).  No reference counterpart: the value and gradient are align_voxel's lines (align.hip), the colour v_interp_color's
+// (vwindow.h).  The contract is written out above kf_map_sample in include/hybkf.h.  Include after kf_internal.h,
+// brick_key.h, brick_find.h, resample_shared.h (lerp1) and map_lookup.h.
 #pragma once
 #include <stdint.h>
 #include <math.h>
@@ -77,20 +77,3 @@ __device__ __forceinline__ float query_nearest(const MapRef& m, double px, doubl
   unsigned off;
   return map_voxel(m, (int)floor(px), (int)floor(py), (int)floor(pz), b, off).x;
 }
-
-static inline bool query_whole_volume(const kf_ctx* c) { return c->vol.bz0 == 0 && c->vol.bz1 == c->vol.nb; }   // a z-slab context holds part of a window and no store
-static inline MapRef query_map(const kf_ctx* c) {
-  MapRef m;
-  m.vol = c->vol; m.st = c->bstore;
-  for (int k = 0; k < 3; ++k) m.ob[k] = c->origin_vox[k] >> 3;      // (a multiple of 8; the shift floors)
-  return m;
-}
-
-// the host forms: one temporary device allocation carved into the arrays (each part a multiple of 16 bytes), copies on the context's stream, one wait
-struct QueryTemp {
-  char* base = nullptr; size_t used = 0, cap = 0;
-  static size_t pad(size_t b) { return (b + 15) & ~(size_t)15; }
-  bool get(size_t bytes) { cap = bytes; if (hipMalloc((void**)&base, bytes) != hipSuccess) { (void)hipGetLastError(); base = nullptr; return false; } return true; }
-  void* take(size_t bytes) { void* p = base + used; used += pad(bytes); return p; }
-  ~QueryTemp() { if (base) hipFree(base); }
-};

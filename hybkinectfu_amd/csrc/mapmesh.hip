@@ -133,7 +133,7 @@ static int enqueue_at(kf_ctx* c, int has_color, float thr, const int32_t fo[3], 
 static int check_common(kf_ctx* c, int has_color, int flags) {
   if (!c) return KF_ERR_ARG;
   if (flags & ~KF_MC_WORLD) return KF_ERR_ARG;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;                     // a z-slab context, as for kf_shift_volume
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;                     // a z-slab context, as for kf_shift_volume
   if (!c->triangles || c->max_triangles == 0) return KF_ERR_STATE;
   if (has_color && !c->vol.color) return KF_ERR_STATE;
   return 0;

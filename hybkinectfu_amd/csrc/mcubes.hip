@@ -143,7 +143,7 @@ extern "C" int kf_marching_cubes_region(kf_ctx* c, int has_color, float thr, con
   if (!c || !lo || !hi) return KF_ERR_ARG;
   if (flags & ~(KF_MC_WORLD | KF_MC_TO_WORLD_SOUP)) return KF_ERR_ARG;
   if ((flags & KF_MC_TO_WORLD_SOUP) && !(flags & KF_MC_WORLD)) return KF_ERR_ARG;       // the world soup holds world coordinates only
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;                     // a z-slab context, as for kf_shift_volume
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;                     // a z-slab context, as for kf_shift_volume
   if (has_color && !c->vol.color) return KF_ERR_STATE;
   if (flags & KF_MC_TO_WORLD_SOUP) { if (!c->soup) return KF_ERR_STATE; }
   else if (!c->triangles || c->max_triangles == 0) return KF_ERR_STATE;
@@ -232,7 +232,7 @@ extern "C" int kf_set_stream_out(kf_ctx* c, int on, int has_color, float thr) {
   if (!on) { c->stream_on = 0; return 0; }
   if (!c->soup) return KF_ERR_STATE;
   if (has_color && !c->vol.color) return KF_ERR_STATE;
-  if (c->vol.bz0 != 0 || c->vol.bz1 != c->vol.nb) return KF_ERR_ARG;
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;
   c->stream_on = 1; c->stream_color = has_color ? 1 : 0; c->stream_thr = thr;
   return 0;
 }

@@ -79,7 +79,7 @@ static inline unsigned query_grid(uint32_t n) { const unsigned g = (n + 255u) / 
 
 extern "C" int kf_map_sample_device(kf_ctx* c, uint32_t n, const double* dev_pos, float* dev_tsdf, float* dev_weight, float* dev_grad, uint8_t* dev_color) {
   if (!c || !dev_pos) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (n == 0) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
   const MapRef m = query_map(c);
@@ -93,7 +93,7 @@ static inline bool query_cast_args_ok(float step, uint32_t max_steps) { return i
 extern "C" int kf_map_cast_rays_device(kf_ctx* c, uint32_t n, const double* dev_origin, const float* dev_dir, const float* dev_tmin, const float* dev_tmax, float step,
                                        uint32_t max_steps, uint8_t* dev_status, float* dev_t, float* dev_normal, uint8_t* dev_color, float* dev_weight) {
   if (!c || !dev_origin || !dev_dir || !dev_tmin || !dev_tmax || !query_cast_args_ok(step, max_steps)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (n == 0) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
   const MapRef m = query_map(c);
@@ -108,55 +108,32 @@ extern "C" int kf_map_cast_rays_device(kf_ctx* c, uint32_t n, const double* dev_
 
 extern "C" int kf_map_sample(kf_ctx* c, uint32_t n, const double* pos, float* tsdf, float* weight, float* grad, uint8_t* color) {
   if (!c || !pos) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (n == 0) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
   const size_t N = n, b_pos = 24 * N, b_f = 4 * N, b_g = 12 * N, b_c = 4 * N;
-  QueryTemp tmp;
-  if (!tmp.get(QueryTemp::pad(b_pos) + 2 * QueryTemp::pad(b_f) + QueryTemp::pad(b_g) + QueryTemp::pad(b_c))) return KF_ERR_ALLOC;
-  double* d_pos = (double*)tmp.take(b_pos);
-  float* d_t = tsdf ? (float*)tmp.take(b_f) : nullptr;
-  float* d_w = weight ? (float*)tmp.take(b_f) : nullptr;
-  float* d_g = grad ? (float*)tmp.take(b_g) : nullptr;
-  uint8_t* d_c = color ? (uint8_t*)tmp.take(b_c) : nullptr;
-  KF_CHECK(hipMemcpyAsync(d_pos, pos, b_pos, hipMemcpyHostToDevice, c->stream));
-  int st = kf_map_sample_device(c, n, d_pos, d_t, d_w, d_g, d_c);
-  if (!st && d_t) st = (int)hipMemcpyAsync(tsdf, d_t, b_f, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_w) st = (int)hipMemcpyAsync(weight, d_w, b_f, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_g) st = (int)hipMemcpyAsync(grad, d_g, b_g, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_c) st = (int)hipMemcpyAsync(color, d_c, b_c, hipMemcpyDeviceToHost, c->stream);
-  const int ss = (int)hipStreamSynchronize(c->stream);               // (also after a failure: the temporary is freed below)
-  return st ? st : ss;
+  KfCarveTemp tmp;
+  if (!tmp.get(KfCarveTemp::pad(b_pos) + 2 * KfCarveTemp::pad(b_f) + KfCarveTemp::pad(b_g) + KfCarveTemp::pad(b_c))) return KF_ERR_ALLOC;
+  const double* d_pos = tmp.up(c, pos, b_pos);
+  float *d_t = tmp.down(tsdf, b_f), *d_w = tmp.down(weight, b_f), *d_g = tmp.down(grad, b_g);
+  uint8_t* d_c = tmp.down(color, b_c);
+  return tmp.finish(c, tmp.st ? tmp.st : kf_map_sample_device(c, n, d_pos, d_t, d_w, d_g, d_c));
 }
 
 extern "C" int kf_map_cast_rays(kf_ctx* c, uint32_t n, const double* origin, const float* dir, const float* tmin, const float* tmax, float step, uint32_t max_steps,
                                 uint8_t* status, float* t, float* normal, uint8_t* color, float* weight) {
   if (!c || !origin || !dir || !tmin || !tmax || !query_cast_args_ok(step, max_steps)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   if (n == 0) return 0;
   KF_CHECK(hipSetDevice(c->cfg.device));
   const size_t N = n, b_o = 24 * N, b_d = 12 * N, b_f = 4 * N, b_s = N, b_c = 4 * N;
-  QueryTemp tmp;
-  if (!tmp.get(QueryTemp::pad(b_o) + 2 * QueryTemp::pad(b_d) + 4 * QueryTemp::pad(b_f) + QueryTemp::pad(b_s) + QueryTemp::pad(b_c))) return KF_ERR_ALLOC;
-  double* d_o = (double*)tmp.take(b_o);
-  float* d_d = (float*)tmp.take(b_d);
-  float* d_t0 = (float*)tmp.take(b_f);
-  float* d_t1 = (float*)tmp.take(b_f);
-  uint8_t* d_s = status ? (uint8_t*)tmp.take(b_s) : nullptr;
-  float* d_t = t ? (float*)tmp.take(b_f) : nullptr;
-  float* d_n = normal ? (float*)tmp.take(b_d) : nullptr;
-  uint8_t* d_c = color ? (uint8_t*)tmp.take(b_c) : nullptr;
-  float* d_w = weight ? (float*)tmp.take(b_f) : nullptr;
-  KF_CHECK(hipMemcpyAsync(d_o, origin, b_o, hipMemcpyHostToDevice, c->stream));
-  int st = (int)hipMemcpyAsync(d_d, dir, b_d, hipMemcpyHostToDevice, c->stream);
-  if (!st) st = (int)hipMemcpyAsync(d_t0, tmin, b_f, hipMemcpyHostToDevice, c->stream);
-  if (!st) st = (int)hipMemcpyAsync(d_t1, tmax, b_f, hipMemcpyHostToDevice, c->stream);
-  if (!st) st = kf_map_cast_rays_device(c, n, d_o, d_d, d_t0, d_t1, step, max_steps, d_s, d_t, d_n, d_c, d_w);
-  if (!st && d_s) st = (int)hipMemcpyAsync(status, d_s, b_s, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_t) st = (int)hipMemcpyAsync(t, d_t, b_f, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_n) st = (int)hipMemcpyAsync(normal, d_n, b_d, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_c) st = (int)hipMemcpyAsync(color, d_c, b_c, hipMemcpyDeviceToHost, c->stream);
-  if (!st && d_w) st = (int)hipMemcpyAsync(weight, d_w, b_f, hipMemcpyDeviceToHost, c->stream);
-  const int ss = (int)hipStreamSynchronize(c->stream);
-  return st ? st : ss;
+  KfCarveTemp tmp;
+  if (!tmp.get(KfCarveTemp::pad(b_o) + 2 * KfCarveTemp::pad(b_d) + 4 * KfCarveTemp::pad(b_f) + KfCarveTemp::pad(b_s) + KfCarveTemp::pad(b_c))) return KF_ERR_ALLOC;
+  const double* d_o = tmp.up(c, origin, b_o);
+  const float *d_d = tmp.up(c, dir, b_d), *d_t0 = tmp.up(c, tmin, b_f), *d_t1 = tmp.up(c, tmax, b_f);
+  uint8_t* d_s = tmp.down(status, b_s);
+  float *d_t = tmp.down(t, b_f), *d_n = tmp.down(normal, b_d);
+  uint8_t* d_c = tmp.down(color, b_c);
+  float* d_w = tmp.down(weight, b_f);
+  return tmp.finish(c, tmp.st ? tmp.st : kf_map_cast_rays_device(c, n, d_o, d_d, d_t0, d_t1, step, max_steps, d_s, d_t, d_n, d_c, d_w));
 }

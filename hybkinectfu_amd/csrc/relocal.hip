@@ -1,15 +1,16 @@
 // relocal.hip -- relocalising a depth frame in the map: the two kernels that make a search over camera poses affordable.  kf_map_score_poses scores many
 // candidate poses of one point set against the map in integers (how many points are observed, lie in the band, behind a surface, in free space);
-// kf_map_pose_sums forms the Gauss-Newton sums of a few poses in one launch, and kf_map_refine_poses is kf_align_brick_store's loop over them, per pose.
+// kf_map_pose_sums forms the Gauss-Newton sums of a few poses in one launch, and kf_map_refine_poses drives kf_align_brick_store's loop over them, per pose.
 // No reference counterpart (the reference blocks on a key press when the camera is lost).  The map is map_lookup.h's, the sample map_sample.h's
-// (kf_map_sample's bits), the step align_step.h's.  The contract is written out above kf_map_score_poses in include/hybkf.h, the argument in DESIGN.md 4e-10.
+// (kf_map_sample's bits), a row's way into the sums and the workgroup's fold align_rows.h's, the step and the loop's turn align_step.h's.  The contract is
+// written out above kf_map_score_poses in include/hybkf.h, the argument in DESIGN.md 4e-10.
 #include "kf_internal.h"
 #include "brick_key.h"
 #include "brick_find.h"
 #include "resample_shared.h"
 #include "map_lookup.h"
 #include "map_sample.h"
-#include "align_step.h"
+#include "align_rows.h"
 #include <string.h>
 #include <new>
 #include <vector>
@@ -81,18 +82,14 @@ __global__ void __launch_bounds__(256) k_score_poses(MapRef m, unsigned n_points
   }
 }
 
-// a pose and the centre its rotations are taken about, as the sums kernel reads them: 15 doubles
-struct KfPoseCentre { double m[12]; double c[3]; };
-
 // The sums of one evaluation, for several poses at once.  Workgroup (g, k) = blockIdx.x = k * G + g takes pose k and the points i with (i / 256) % G == g, lane
 // i % 256, each lane its points in ascending order.  Row of a point: phi and the gradient g by kf_map_sample's lines at w; it takes part when observed and
-// fabsf(phi) < gate; x = (float)(w - centre), the difference in fp64; J = (x cross g, g) in fp32, e = -phi; its 28 exact products are added in fp64.  The
-// tail is k_store_align_sums': the wave's lanes by the butterfly xor 32 .. 1, the four waves ((w0 + w1) + w2) + w3, one row of 29 doubles per workgroup.
-__global__ void __launch_bounds__(256) k_pose_sums(MapRef m, unsigned n_points, const float* __restrict__ pts, unsigned groups, const KfPoseCentre* __restrict__ pc,
+// fabsf(phi) < gate; x = (float)(w - centre), the difference in fp64; J = (x cross g, g) in fp32, e = -phi; the
+// row enters the lane's sums and the workgroup folds them as in k_store_align_sums (align_rows.h); a lane sees at most 2^24 points.
+__global__ void __launch_bounds__(256) k_pose_sums(MapRef m, unsigned n_points, const float* __restrict__ pts, unsigned groups, const KfAlignXf* __restrict__ pc,
                                                    float gate, double* __restrict__ rows) {
-  __shared__ double s_red[4][KF_ALIGN_SUMS];
   const unsigned pose = blockIdx.x / groups, grp = blockIdx.x - pose * groups;
-  const KfPoseCentre* __restrict__ P = pc + pose;
+  const KfAlignXf* __restrict__ P = pc + pose;
   MapBrick b = map_brick_none();
   double acc[28];
 #pragma unroll
@@ -106,33 +103,9 @@ __global__ void __launch_bounds__(256) k_pose_sums(MapRef m, unsigned n_points, 
     const float x0 = (float)(w0 - P->c[0]), x1 = (float)(w1 - P->c[1]), x2 = (float)(w2 - P->c[2]);
     const double J[6] = {(double)(x1 * s.gz - x2 * s.gy), (double)(x2 * s.gx - x0 * s.gz), (double)(x0 * s.gy - x1 * s.gx), (double)s.gx, (double)s.gy, (double)s.gz};
     const double e = (double)(-s.tsdf);
-    int k = 0;
-#pragma unroll
-    for (int a = 0; a < 6; ++a)
-#pragma unroll
-      for (int c = a; c < 6; ++c, ++k) acc[k] += J[a] * J[c];             // (a product of two fp32 values is exact in fp64)
-#pragma unroll
-    for (int a = 0; a < 6; ++a) acc[21 + a] += J[a] * e;
-    acc[27] += e * e;
-    n += 1u;
+    align_row_add(J, e, acc, n);
   }
-#pragma unroll
-  for (int k = 0; k < 28; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) v += __shfl_xor(v, x);
-    acc[k] = v;
-  }
-#pragma unroll
-  for (int x = 32; x >= 1; x >>= 1) n += (unsigned)__shfl_xor((int)n, x);
-  if ((threadIdx.x & 63u) == 0u) {
-#pragma unroll
-    for (int k = 0; k < 28; ++k) s_red[threadIdx.x >> 6][k] = acc[k];
-    s_red[threadIdx.x >> 6][28] = (double)n;                                // (at most 2^24 points: the integer and the double are exact)
-  }
-  __syncthreads();
-  if (threadIdx.x < KF_ALIGN_SUMS)
-    rows[(size_t)blockIdx.x * KF_ALIGN_SUMS + threadIdx.x] = ((s_red[0][threadIdx.x] + s_red[1][threadIdx.x]) + s_red[2][threadIdx.x]) + s_red[3][threadIdx.x];
+  align_rows_fold(acc, n, rows + (size_t)blockIdx.x * KF_ALIGN_SUMS);
 }
 
 // the finishing launch: a pose's `groups` rows added in ascending order, one lane per entry
@@ -153,7 +126,7 @@ static inline bool score_args_ok(uint32_t n_points, uint32_t n_poses, uint32_t m
 extern "C" int kf_map_score_poses_device(kf_ctx* c, uint32_t n_points, const float* dev_points, uint32_t n_poses, const double* dev_poses, float band,
                                          kf_pose_score* dev_scores) {
   if (!c || !dev_points || !dev_poses || !dev_scores || !score_args_ok(n_points, n_poses, KF_SCORE_MAX_POSES, band)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   KF_CHECK(hipSetDevice(c->cfg.device));
   // the chunking: a small pose count is spread over the chip, a large one gets one workgroup per pose that walks all the points
   const unsigned most = (n_points + 255u) / 256u, want = (KF_SCORE_TARGET_GROUPS + n_poses - 1u) / n_poses;
@@ -165,40 +138,35 @@ extern "C" int kf_map_score_poses_device(kf_ctx* c, uint32_t n_points, const flo
 
 extern "C" int kf_map_score_poses(kf_ctx* c, uint32_t n_points, const float* points, uint32_t n_poses, const double* poses, float band, kf_pose_score* scores) {
   if (!c || !points || !poses || !scores || !score_args_ok(n_points, n_poses, KF_SCORE_MAX_POSES, band)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
   KF_CHECK(hipSetDevice(c->cfg.device));
   const size_t b_pts = 12 * (size_t)n_points, b_pose = 96 * (size_t)n_poses, b_sc = sizeof(kf_pose_score) * (size_t)n_poses;
-  QueryTemp tmp;
-  if (!tmp.get(QueryTemp::pad(b_pts) + QueryTemp::pad(b_pose) + QueryTemp::pad(b_sc))) return KF_ERR_ALLOC;
-  double* d_pose = (double*)tmp.take(b_pose);
-  float* d_pts = (float*)tmp.take(b_pts);
-  kf_pose_score* d_sc = (kf_pose_score*)tmp.take(b_sc);
-  int st = (int)hipMemcpyAsync(d_pts, points, b_pts, hipMemcpyHostToDevice, c->stream);
-  if (!st) st = (int)hipMemcpyAsync(d_pose, poses, b_pose, hipMemcpyHostToDevice, c->stream);
-  if (!st) st = kf_map_score_poses_device(c, n_points, d_pts, n_poses, d_pose, band, d_sc);
-  if (!st) st = (int)hipMemcpyAsync(scores, d_sc, b_sc, hipMemcpyDeviceToHost, c->stream);
-  const int ss = (int)hipStreamSynchronize(c->stream);               // (also after a failure: the temporary is freed below)
-  return st ? st : ss;
+  KfCarveTemp tmp;
+  if (!tmp.get(KfCarveTemp::pad(b_pts) + KfCarveTemp::pad(b_pose) + KfCarveTemp::pad(b_sc))) return KF_ERR_ALLOC;
+  const double* d_pose = tmp.up(c, poses, b_pose);
+  const float* d_pts = tmp.up(c, points, b_pts);
+  kf_pose_score* d_sc = tmp.down(scores, b_sc);
+  return tmp.finish(c, tmp.st ? tmp.st : kf_map_score_poses_device(c, n_points, d_pts, n_poses, d_pose, band, d_sc));
 }
 
 // the device side of kf_map_pose_sums and kf_map_refine_poses: the points once, then per evaluation the poses in, the folded sums out
 struct PoseSumsRun {
-  QueryTemp tmp;
-  float* d_pts = nullptr; KfPoseCentre* d_pc = nullptr; double* d_rows = nullptr; double* d_sums = nullptr;
+  KfCarveTemp tmp;
+  float* d_pts = nullptr; KfAlignXf* d_pc = nullptr; double* d_rows = nullptr; double* d_sums = nullptr;
   unsigned n_points = 0, groups = 0;
   // false: the temporary does not fit
   bool get(uint32_t points, uint32_t poses) {
     n_points = points;
     groups = (points + 255u) / 256u;
     if (groups > KF_SUMS_MAX_GROUPS) groups = KF_SUMS_MAX_GROUPS;
-    const size_t b_pts = 12 * (size_t)points, b_pc = sizeof(KfPoseCentre) * (size_t)poses, b_sums = 8 * (size_t)KF_ALIGN_SUMS * poses, b_rows = b_sums * groups;
-    if (!tmp.get(QueryTemp::pad(b_pts) + QueryTemp::pad(b_pc) + QueryTemp::pad(b_sums) + QueryTemp::pad(b_rows))) return false;
-    d_pc = (KfPoseCentre*)tmp.take(b_pc); d_rows = (double*)tmp.take(b_rows); d_sums = (double*)tmp.take(b_sums); d_pts = (float*)tmp.take(b_pts);
+    const size_t b_pts = 12 * (size_t)points, b_pc = sizeof(KfAlignXf) * (size_t)poses, b_sums = 8 * (size_t)KF_ALIGN_SUMS * poses, b_rows = b_sums * groups;
+    if (!tmp.get(KfCarveTemp::pad(b_pts) + KfCarveTemp::pad(b_pc) + KfCarveTemp::pad(b_sums) + KfCarveTemp::pad(b_rows))) return false;
+    d_pc = (KfAlignXf*)tmp.take(b_pc); d_rows = (double*)tmp.take(b_rows); d_sums = (double*)tmp.take(b_sums); d_pts = (float*)tmp.take(b_pts);
     return true;
   }
   // the sums of pc[0 .. n) into sums (29 n doubles); blocks
-  int eval(kf_ctx* c, unsigned n, const KfPoseCentre* pc, float gate, double* sums) {
-    int st = (int)hipMemcpyAsync(d_pc, pc, sizeof(KfPoseCentre) * (size_t)n, hipMemcpyHostToDevice, c->stream);
+  int eval(kf_ctx* c, unsigned n, const KfAlignXf* pc, float gate, double* sums) {
+    int st = (int)hipMemcpyAsync(d_pc, pc, sizeof(KfAlignXf) * (size_t)n, hipMemcpyHostToDevice, c->stream);
     if (!st) {
       hipLaunchKernelGGL(k_pose_sums, dim3(n * groups), dim3(256), 0, c->stream, query_map(c), n_points, d_pts, groups, d_pc, gate, d_rows);
       hipLaunchKernelGGL(k_pose_sums_fold, dim3((n * KF_ALIGN_SUMS + 255u) / 256u), dim3(256), 0, c->stream, n, groups, d_rows, d_sums);
@@ -219,8 +187,8 @@ extern "C" int kf_map_pose_sums(kf_ctx* c, uint32_t n_points, const float* point
                                 double* sums) {
   if (!c || !points || !poses || !centres || !sums || !score_args_ok(n_points, n_poses, KF_SUMS_MAX_POSES, gate)) return KF_ERR_ARG;
   if (!all_finite(poses, 12 * (size_t)n_poses) || !all_finite(centres, 3 * (size_t)n_poses)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
-  std::vector<KfPoseCentre> pc;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
+  std::vector<KfAlignXf> pc;
   std::vector<double> out;
   try { pc.resize(n_poses); out.resize((size_t)KF_ALIGN_SUMS * n_poses); } catch (const std::bad_alloc&) { return KF_ERR_ALLOC; }   // (no exception crosses the C boundary)
   for (uint32_t k = 0; k < n_poses; ++k) { memcpy(pc[k].m, poses + 12 * (size_t)k, sizeof(pc[k].m)); memcpy(pc[k].c, centres + 3 * (size_t)k, sizeof(pc[k].c)); }
@@ -238,20 +206,14 @@ extern "C" int kf_map_pose_sums(kf_ctx* c, uint32_t n_points, const float* point
 extern "C" int kf_map_refine_poses(kf_ctx* c, uint32_t n_points, const float* points, uint32_t n_poses, double* poses, const double* centres,
                                    const kf_refine_params* params, kf_align_report* reports) {
   if (!c || !points || !poses || !centres || !params || !reports || !score_args_ok(n_points, n_poses, KF_SUMS_MAX_POSES, params->gate)) return KF_ERR_ARG;
-  if (!isfinite(params->eps_rot) || !isfinite(params->eps_trans) || params->eps_rot < 0.0 || params->eps_trans < 0.0) return KF_ERR_ARG;
-  if (!all_finite(poses, 12 * (size_t)n_poses) || !all_finite(centres, 3 * (size_t)n_poses)) return KF_ERR_ARG;
-  if (!query_whole_volume(c)) return KF_ERR_STATE;
-  struct State { double cur[12], good[12]; kf_align_report rep; };
-  std::vector<State> st;
+  if (!all_finite(poses, 12 * (size_t)n_poses) || !kf_align_stop_valid(params->eps_rot, params->eps_trans, centres, n_poses)) return KF_ERR_ARG;
+  if (!kf_whole_volume(c)) return KF_ERR_STATE;
+  std::vector<KfAlignLoop> st;
   std::vector<uint32_t> live;                                        // the poses still running, ascending
-  std::vector<KfPoseCentre> pc;
+  std::vector<KfAlignXf> pc;
   std::vector<double> sums;
   try { st.resize(n_poses); live.resize(n_poses); pc.resize(n_poses); sums.resize((size_t)KF_ALIGN_SUMS * n_poses); } catch (const std::bad_alloc&) { return KF_ERR_ALLOC; }
-  for (uint32_t k = 0; k < n_poses; ++k) {
-    memcpy(st[k].cur, poses + 12 * (size_t)k, sizeof(st[k].cur)); memcpy(st[k].good, st[k].cur, sizeof(st[k].good));
-    memset(&st[k].rep, 0, sizeof(st[k].rep));
-    live[k] = k;
-  }
+  for (uint32_t k = 0; k < n_poses; ++k) { kf_align_loop_begin(st[k], poses + 12 * (size_t)k); live[k] = k; }
   KF_CHECK(hipSetDevice(c->cfg.device));
   PoseSumsRun run;
   if (!run.get(n_points, n_poses)) return KF_ERR_ALLOC;
@@ -265,27 +227,10 @@ extern "C" int kf_map_refine_poses(kf_ctx* c, uint32_t n_points, const float* po
     const int e = run.eval(c, (unsigned)live.size(), pc.data(), params->gate, sums.data());
     if (e) return e;                                                 // (nothing written)
     size_t kept = 0;
-    for (size_t a = 0; a < live.size(); ++a) {
-      // kf_align_brick_store's loop body
-      State& s = st[live[a]];
-      const double* su = sums.data() + (size_t)KF_ALIGN_SUMS * a;
-      const double* centre = centres + 3 * (size_t)live[a];
-      kf_align_report& rep = s.rep;
-      memcpy(rep.sums, su, sizeof(rep.sums));
-      rep.rms = su[28] > 0.0 ? sqrt(su[27] / su[28]) : 0.0;
-      if (!(su[28] > 0.0) || su[28] < (double)params->min_pairs) { rep.verdict = KF_ALIGN_FEW_PAIRS; continue; }
-      memcpy(s.good, s.cur, sizeof(s.good));                         // evaluated successfully
-      if (rep.iterations >= params->max_iter) { rep.verdict = KF_ALIGN_ITER_LIMIT; continue; }
-      double step[6];
-      if (kf_align_step_host(su, centre, s.cur, step)) { rep.verdict = KF_ALIGN_SINGULAR; continue; }
-      rep.iterations += 1u;
-      memcpy(rep.step, step, sizeof(step));
-      const double rot = sqrt(step[0] * step[0] + step[1] * step[1] + step[2] * step[2]), tr = sqrt(step[3] * step[3] + step[4] * step[4] + step[5] * step[5]);
-      if (rot <= fmax(params->eps_rot, KF_ALIGN_EPS_ROT_MIN) && tr <= fmax(params->eps_trans, KF_ALIGN_EPS_TRANS_MIN)) {
-        rep.verdict = KF_ALIGN_CONVERGED; memcpy(s.good, s.cur, sizeof(s.good)); continue;
-      }
-      live[kept++] = live[a];
-    }
+    for (size_t a = 0; a < live.size(); ++a)                          // (the stepped pose is not checked for being rigid: the poses that go in are not either)
+      if (kf_align_loop_turn(st[live[a]], sums.data() + (size_t)KF_ALIGN_SUMS * a, centres + 3 * (size_t)live[a], params->max_iter, params->min_pairs,
+                             params->eps_rot, params->eps_trans, false))
+        live[kept++] = live[a];
     live.resize(kept);
   }
   for (uint32_t k = 0; k < n_poses; ++k) { memcpy(poses + 12 * (size_t)k, st[k].good, sizeof(st[k].good)); reports[k] = st[k].rep; }

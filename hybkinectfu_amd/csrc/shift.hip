@@ -186,7 +186,7 @@ extern "C" int kf_shift_volume(kf_ctx* c, int32_t dx, int32_t dy, int32_t dz) {
   if ((dx % KF_BRICK) || (dy % KF_BRICK) || (dz % KF_BRICK)) return KF_ERR_ARG;
   if (dx == 0 && dy == 0 && dz == 0) return 0;
   KfVolume& v = c->vol;
-  if (v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_ARG;     // a z-slab context: a z shift needs a layer exchange between the members of a group
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;     // a z-slab context: a z shift needs a layer exchange between the members of a group
   const int32_t d[3] = {dx, dy, dz};
   int32_t org[3];
   if (!moved_origin(c, d, org)) return KF_ERR_ARG;
@@ -221,7 +221,7 @@ extern "C" int kf_place_window(kf_ctx* c, int32_t ox, int32_t oy, int32_t oz) {
   if (!c) return KF_ERR_ARG;
   if ((ox % KF_BRICK) || (oy % KF_BRICK) || (oz % KF_BRICK)) return KF_ERR_ARG;
   KfVolume& v = c->vol;
-  if (v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_ARG;
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   const int32_t org[3] = {ox, oy, oz};
   if (!kf_window_in_key_range(c->origin_vox, v.nb) || !kf_window_in_key_range(org, v.nb)) return KF_ERR_ARG;
@@ -249,7 +249,7 @@ extern "C" int kf_place_window(kf_ctx* c, int32_t ox, int32_t oy, int32_t oz) {
 extern "C" int kf_refill_window(kf_ctx* c) {
   if (!c) return KF_ERR_ARG;
   KfVolume& v = c->vol;
-  if (v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_ARG;
+  if (!kf_whole_volume(c)) return KF_ERR_ARG;
   if (!c->bstore.max_bricks) return KF_ERR_STATE;
   if (!kf_window_in_key_range(c->origin_vox, v.nb)) return KF_ERR_ARG;
   KF_CHECK(hipSetDevice(c->cfg.device));

@@ -121,7 +121,7 @@ extern "C" int kf_render_view_at(kf_ctx* c, int mode, const int32_t frame_origin
   for (int k = 0; k < 3; ++k) if (frame_origin_vox[k] % KF_BRICK) return KF_ERR_ARG;
   if (mode == KF_VIEW_COLOR && !c->vol.color) return KF_ERR_STATE;
   const KfVolume& v = c->vol;
-  if (v.own_z0 > 0 || v.own_z1 < v.res || v.bz0 != 0 || v.bz1 != v.nb) return KF_ERR_STATE;      // a z-slab context, kf_render_view's code
+  if (v.own_z0 > 0 || v.own_z1 < v.res || !kf_whole_volume(c)) return KF_ERR_STATE;      // a z-slab context, kf_render_view's code
   if (!kf_window_in_key_range(frame_origin_vox, v.nb)) return KF_ERR_ARG;
   int d[3];
   for (int k = 0; k < 3; ++k) {                                            // the shift that would bring the window there: kf_shift_volume takes 32-bit components

@@ -198,14 +198,18 @@ def np_rows(dst, src, xf, centre):
     return np.stack([q[part] for q in J], -1), e[part]
 
 
-def np_sums(dst, src, xf, centre):
-    """(the 29 sums, float64: each the correctly rounded sum of its exact terms; per sum the sum of |term|, for the comparison's bound)"""
-    J, e = np_rows(dst, src, xf, centre)
+def np_row_sums(J, e):
+    """(the 29 sums of the rows (J, e), float64: each the correctly rounded sum of its exact terms; per sum the sum of |term|, for the comparison's bound)"""
     J, e = J.astype(f64), e.astype(f64)
     terms = [J[:, a] * J[:, b] for a, b in TRI] + [J[:, a] * e for a in range(6)] + [e * e]
     sums = np.array([math.fsum(q.tolist()) for q in terms] + [float(len(e))], f64)
     mags = np.array([math.fsum(np.abs(q).tolist()) for q in terms] + [0.0], f64)
     return sums, mags
+
+
+def np_sums(dst, src, xf, centre):
+    """np_row_sums of np_rows"""
+    return np_row_sums(*np_rows(dst, src, xf, centre))
 
 
 def matrix_of(sums):
@@ -242,12 +246,13 @@ def np_step(sums, centre, xf):
     return xf_of(E @ xf[:, :3], E @ (xf[:, 3] - c) + c + u), xi
 
 
-def np_align(dst, src, xf, centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
-    """kf_align_brick_store's loop over np_sums: (xf, verdict, iterations, the last evaluation's sums, the last step)"""
-    xf = good = np.asarray(xf, f64)
-    it, step, sums = 0, np.zeros(6), None
+def np_gauss_newton(eval_sums, xf, centre, max_iter, min_pairs, eps_rot, eps_trans):
+    """the loop of kf_align_brick_store and kf_map_refine_poses over eval_sums(xf) -> the 29 sums: (xf, verdict, iterations, the last evaluation's sums, the
+    last step)"""
+    xf = good = np.asarray(xf, f64).reshape(3, 4)
+    it, step = 0, np.zeros(6)
     while True:
-        sums, _ = np_sums(dst, src, xf, centre)
+        sums = eval_sums(xf)
         if sums[28] < max(min_pairs, 1):
             return good, FEW_PAIRS, it, sums, step
         good = xf
@@ -260,6 +265,11 @@ def np_align(dst, src, xf, centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, ep
         it += 1
         if np.linalg.norm(step[:3]) <= max(eps_rot, EPS_ROT_MIN) and np.linalg.norm(step[3:]) <= max(eps_trans, EPS_TRANS_MIN):
             return xf, CONVERGED, it, sums, step
+
+
+def np_align(dst, src, xf, centre, max_iter=25, min_pairs=1000, eps_rot=1e-9, eps_trans=1e-9):
+    """kf_align_brick_store's loop over np_sums: (xf, verdict, iterations, the last evaluation's sums, the last step)"""
+    return np_gauss_newton(lambda x: np_sums(dst, src, x, centre)[0], xf, centre, max_iter, min_pairs, eps_rot, eps_trans)
 
 
 def errors(xf, truth, at):

@@ -1,5 +1,6 @@
-// map_align_main.cpp -- CPU check of the host side of a map alignment (csrc/align_step.h: kf_align_solve6, kf_align_exp, kf_align_step_host; csrc/rigid_keys.h:
-// kf_rigid_valid on the stepped transforms), a program of its own: tests/test_map_align_abi_cpu.py builds it with AddressSanitizer + UBSan and runs it as a
+// map_align_main.cpp -- CPU check of the host side of a map alignment (csrc/align_step.h: kf_align_solve6, kf_align_exp, kf_align_step_host, and the loop around
+// them, kf_align_loop_turn, with every verdict and state transition on crafted sums; csrc/rigid_keys.h: kf_rigid_valid on the stepped transforms), a program of
+// its own: tests/test_map_align_abi_cpu.py builds it with AddressSanitizer + UBSan and runs it as a
 // child process.  usage: map_align_main
 #include "align_step.h"
 #include "rigid_keys.h"
@@ -94,6 +95,128 @@ int main() {
     CHECK(memcmp(xf, I, sizeof(xf)) == 0);
     for (int a = 0; a < 6; ++a) CHECK(step[a] == 7.0);
     CHECK(kf_align_step_host(s, centre, xf, step) == 0);        // and the good sums still step
+  }
+  // ---- the loop (kf_align_loop_turn): every verdict and every state transition, on crafted sums.  X0: a rigid start that is not the identity
+  double X0[12];
+  {
+    const double xi[6] = {0.1, -0.2, 0.15, 3, -2, 1}, zero3[3] = {0, 0, 0};
+    double E[9], u[3];
+    kf_align_exp(xi, E, u);
+    for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) X0[4 * i + j] = E[3 * i + j]; X0[4 * i + 3] = u[i]; }
+    CHECK(kf_rigid_valid(X0));
+    CHECK(kf_align_stop_valid(0.0, 0.0, centre, 1) && kf_align_stop_valid(1e-3, 1e-3, zero3, 0));
+    const double bad[3] = {1, NAN, 3};
+    CHECK(!kf_align_stop_valid(-1e-9, 0, centre, 1) && !kf_align_stop_valid(0, -1e-9, centre, 1) && !kf_align_stop_valid(NAN, 0, centre, 1) &&
+          !kf_align_stop_valid(0, INFINITY, centre, 1) && !kf_align_stop_valid(0, 0, bad, 1));
+  }
+  const double zero6[6] = {0, 0, 0, 0, 0, 0};
+  // count 0: FEW_PAIRS, nothing done, rms 0 -- also with min_pairs 0
+  for (unsigned min_pairs = 0; min_pairs <= 100; min_pairs += 100) {
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS] = {0};
+    kf_align_loop_begin(L, X0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, min_pairs, 1e-9, 1e-9, true));
+    CHECK(L.rep.verdict == KF_ALIGN_FEW_PAIRS && L.rep.iterations == 0 && L.rep.rms == 0.0);
+    CHECK(memcmp(L.good, X0, sizeof(X0)) == 0 && memcmp(L.cur, X0, sizeof(X0)) == 0 && memcmp(L.rep.step, zero6, sizeof(zero6)) == 0);
+  }
+  // enough pairs, max_iter 0: ITER_LIMIT, the pose untouched, no step, the sums and their rms reported
+  {
+    const double xi[6] = {0.01, 0.02, -0.01, 0.2, 0.1, -0.3};
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS];
+    sums_of(300, xi, 0.01, s);
+    kf_align_loop_begin(L, X0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 0, 300, 1e-9, 1e-9, true));
+    CHECK(L.rep.verdict == KF_ALIGN_ITER_LIMIT && L.rep.iterations == 0 && L.rep.rms == sqrt(s[27] / 300.0) && L.rep.rms > 0.0);
+    CHECK(memcmp(L.good, X0, sizeof(X0)) == 0 && memcmp(L.cur, X0, sizeof(X0)) == 0 && memcmp(L.rep.step, zero6, sizeof(zero6)) == 0);
+    CHECK(memcmp(L.rep.sums, s, sizeof(s)) == 0);
+    kf_align_loop_begin(L, X0);                                  // one pair short: FEW_PAIRS comes first
+    CHECK(!kf_align_loop_turn(L, s, centre, 0, 301, 1e-9, 1e-9, true) && L.rep.verdict == KF_ALIGN_FEW_PAIRS && L.rep.rms == sqrt(s[27] / 300.0));
+  }
+  // a zero matrix with enough pairs: exactly SINGULAR, the pose the evaluated one
+  for (int rigid = 0; rigid < 2; ++rigid) {
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS] = {0};
+    s[27] = 2.0; s[28] = 500.0;
+    kf_align_loop_begin(L, X0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, rigid != 0));
+    CHECK(L.rep.verdict == KF_ALIGN_SINGULAR && L.rep.iterations == 0 && memcmp(L.rep.step, zero6, sizeof(zero6)) == 0);
+    CHECK(memcmp(L.good, X0, sizeof(X0)) == 0 && memcmp(L.cur, X0, sizeof(X0)) == 0);
+  }
+  // a noise-free system: go on with iterations 1, the step the solve's, the pose stepped; then a step below eps: CONVERGED, the stepped pose returned
+  {
+    const double xi[6] = {0.02, 0.01, -0.03, 0.3, 0.2, -0.1}, small[6] = {1e-10, -2e-10, 1e-10, 3e-10, 1e-10, -1e-10};
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS], want[12], solved[6], step[6];
+    sums_of(500, xi, 0.0, s);
+    memcpy(want, X0, sizeof(want));
+    CHECK(kf_align_solve6(s, solved) && kf_align_step_host(s, centre, want, step) == 0);
+    kf_align_loop_begin(L, X0);
+    CHECK(kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, true));
+    CHECK(L.rep.iterations == 1 && memcmp(L.rep.step, solved, sizeof(solved)) == 0 && memcmp(L.cur, want, sizeof(want)) == 0);
+    CHECK(memcmp(L.good, X0, sizeof(X0)) == 0 && memcmp(L.cur, X0, sizeof(X0)) != 0);
+    sums_of(500, small, 0.0, s);
+    CHECK(kf_align_step_host(s, centre, want, step) == 0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, true));
+    CHECK(L.rep.verdict == KF_ALIGN_CONVERGED && L.rep.iterations == 2 && memcmp(L.rep.step, step, sizeof(step)) == 0);
+    CHECK(memcmp(L.good, want, sizeof(want)) == 0 && memcmp(L.cur, want, sizeof(want)) == 0 && memcmp(L.rep.sums, s, sizeof(s)) == 0);
+  }
+  // the eps floor: eps 0 converges on a step between 0 and the minima, and on neither side just above them
+  {
+    const double below[6] = {0.9 * KF_ALIGN_EPS_ROT_MIN, 0, 0, 0, 0.9 * KF_ALIGN_EPS_TRANS_MIN, 0};
+    const double rot_above[6] = {1.1 * KF_ALIGN_EPS_ROT_MIN, 0, 0, 0, 0.9 * KF_ALIGN_EPS_TRANS_MIN, 0};
+    const double trans_above[6] = {0.9 * KF_ALIGN_EPS_ROT_MIN, 0, 0, 0, 1.1 * KF_ALIGN_EPS_TRANS_MIN, 0};
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS];
+    sums_of(500, below, 0.0, s);
+    kf_align_loop_begin(L, X0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 0.0, 0.0, true) && L.rep.verdict == KF_ALIGN_CONVERGED && L.rep.iterations == 1);
+    CHECK(L.rep.step[0] > 0.0 && L.rep.step[0] < KF_ALIGN_EPS_ROT_MIN && L.rep.step[4] > 0.0 && L.rep.step[4] < KF_ALIGN_EPS_TRANS_MIN);
+    sums_of(500, rot_above, 0.0, s);
+    kf_align_loop_begin(L, X0);
+    CHECK(kf_align_loop_turn(L, s, centre, 25, 100, 0.0, 0.0, true) && L.rep.iterations == 1);
+    sums_of(500, trans_above, 0.0, s);
+    kf_align_loop_begin(L, X0);
+    CHECK(kf_align_loop_turn(L, s, centre, 25, 100, 0.0, 0.0, true) && L.rep.iterations == 1);
+    sums_of(500, rot_above, 0.0, s);                             // an eps above the floor is the caller's
+    kf_align_loop_begin(L, X0);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 2.0 * KF_ALIGN_EPS_ROT_MIN, 0.0, true) && L.rep.verdict == KF_ALIGN_CONVERGED);
+  }
+  // FEW_PAIRS after one step: the pose evaluated before the step, iterations 1, that step, the second evaluation's sums
+  {
+    const double xi[6] = {0.02, 0.01, -0.03, 0.3, 0.2, -0.1};
+    KfAlignLoop L;
+    double s[KF_ALIGN_SUMS], few[KF_ALIGN_SUMS], first[6];
+    sums_of(500, xi, 0.0, s);
+    sums_of(99, xi, 0.5, few);
+    kf_align_loop_begin(L, X0);
+    CHECK(kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, true));
+    memcpy(first, L.rep.step, sizeof(first));
+    CHECK(!kf_align_loop_turn(L, few, centre, 25, 100, 1e-9, 1e-9, true));
+    CHECK(L.rep.verdict == KF_ALIGN_FEW_PAIRS && L.rep.iterations == 1 && memcmp(L.rep.step, first, sizeof(first)) == 0);
+    CHECK(memcmp(L.good, X0, sizeof(X0)) == 0 && memcmp(L.cur, X0, sizeof(X0)) != 0);
+    CHECK(memcmp(L.rep.sums, few, sizeof(few)) == 0 && L.rep.rms == sqrt(few[27] / 99.0));
+  }
+  // from a start that is not rigid: with require_rigid SINGULAR, iterations and step as they were; without it the loop goes on
+  {
+    const double xi[6] = {0.02, 0.01, -0.03, 0.3, 0.2, -0.1};
+    double S[12], s[KF_ALIGN_SUMS], first[6];
+    memcpy(S, X0, sizeof(S));
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) S[4 * i + j] *= 1.5;
+    CHECK(!kf_rigid_valid(S));
+    sums_of(500, xi, 0.0, s);
+    KfAlignLoop L;
+    kf_align_loop_begin(L, S);
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, true));
+    CHECK(L.rep.verdict == KF_ALIGN_SINGULAR && L.rep.iterations == 0 && memcmp(L.rep.step, zero6, sizeof(zero6)) == 0 && memcmp(L.good, S, sizeof(S)) == 0);
+    kf_align_loop_begin(L, S);
+    CHECK(kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, false));
+    CHECK(L.rep.iterations == 1 && memcmp(L.good, S, sizeof(S)) == 0 && !kf_rigid_valid(L.cur));
+    memcpy(first, L.rep.step, sizeof(first));
+    double at[12];
+    memcpy(at, L.cur, sizeof(at));
+    CHECK(!kf_align_loop_turn(L, s, centre, 25, 100, 1e-9, 1e-9, true));           // the same state, now asked to stay rigid
+    CHECK(L.rep.verdict == KF_ALIGN_SINGULAR && L.rep.iterations == 1 && memcmp(L.rep.step, first, sizeof(first)) == 0 && memcmp(L.good, at, sizeof(at)) == 0);
   }
   if (fails) { printf("%d checks FAILED\n", fails); return 1; }
   printf("map align ok\n");

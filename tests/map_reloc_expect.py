@@ -150,34 +150,14 @@ def np_pose_terms(m, points, pose, centre, gate):
 
 
 def np_pose_sums(m, points, pose, centre, gate):
-    """(the 29 sums, float64: each the correctly rounded sum of its exact terms; per sum the sum of |term|, for the comparison's bound)"""
-    J, e, _ = np_pose_terms(m, points, pose, centre, gate)
-    J, e = J.astype(f64), e.astype(f64)
-    terms = [J[:, a] * J[:, b] for a, b in A.TRI] + [J[:, a] * e for a in range(6)] + [e * e]
-    sums = np.array([math.fsum(q.tolist()) for q in terms] + [float(len(e))], f64)
-    mags = np.array([math.fsum(np.abs(q).tolist()) for q in terms] + [0.0], f64)
-    return sums, mags
+    """map_align_expect.np_row_sums of np_pose_terms"""
+    return A.np_row_sums(*np_pose_terms(m, points, pose, centre, gate)[:2])
 
 
 def np_refine(m, points, pose, centre, gate, max_iter=25, min_pairs=100, eps_rot=1e-9, eps_trans=1e-9):
     """kf_map_refine_poses' loop for one pose over np_pose_sums: (pose, verdict, iterations, the last evaluation's sums, the last step)"""
     m = E._index(m)
-    xf = good = np.asarray(pose, f64).reshape(3, 4)
-    it, step = 0, np.zeros(6)
-    while True:
-        sums, _ = np_pose_sums(m, points, xf, centre, gate)
-        if sums[28] < max(min_pairs, 1):
-            return good, FEW_PAIRS, it, sums, step
-        good = xf
-        if it >= max_iter:
-            return good, ITER_LIMIT, it, sums, step
-        nxt = A.np_step(sums, centre, xf)
-        if nxt is None:
-            return good, SINGULAR, it, sums, step
-        xf, step = nxt
-        it += 1
-        if np.linalg.norm(step[:3]) <= max(eps_rot, A.EPS_ROT_MIN) and np.linalg.norm(step[3:]) <= max(eps_trans, A.EPS_TRANS_MIN):
-            return xf, CONVERGED, it, sums, step
+    return A.np_gauss_newton(lambda x: np_pose_sums(m, points, x, centre, gate)[0], pose, centre, max_iter, min_pairs, eps_rot, eps_trans)
 
 
 def centre_of(points, pose):

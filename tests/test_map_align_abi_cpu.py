@@ -1,7 +1,8 @@
 """CPU-only: the ABI and the host side of aligning two maps.  kf_align_brick_store and kf_align_step are exported, bound, declared and refuse what they must
 without a device; the host shim's names and the Python methods exist and answer -1 / False without an application.  kf_align_step is compared with numpy's
-float64 solve on the sums the restatement (map_align_expect.py) gives for the three analytic cases.  The header the step lives in (csrc/align_step.h) also
-runs in a stand-alone program with a main of its own (tests/map_align_main.cpp), built with AddressSanitizer + UBSan: nothing of it is loaded into Python."""
+float64 solve on the sums the restatement (map_align_expect.py) gives for the three analytic cases.  The header the step and the loop's turn live in
+(csrc/align_step.h) also runs in a stand-alone program with a main of its own (tests/map_align_main.cpp), built with AddressSanitizer + UBSan: nothing of it
+is loaded into Python; that program pins every verdict of the loop on crafted sums, and the same sequences go through the yardstick's loop here."""
 import ctypes as C
 import os
 import re
@@ -114,6 +115,62 @@ def test_restatement_recovers_the_moves():
     err = E.errors(xf, truth, CENTRE)
     print("2deg: iterations", it, "errors", err, "pairs", sums[28])
     assert verdict == E.CONVERGED and it <= 8 and err[0] < 0.02 and err[1] < 1e-3 and sums[28] >= 10000
+
+
+def crafted_sums(n, xi, noise=0.0, seed=7):
+    """the 29 sums of n well-spread rows J, e = J . xi + noise: map_align_main.cpp's sums_of, in numpy"""
+    rng = np.random.default_rng(seed)
+    J = (rng.random((n, 6)) - 0.5) * np.array([20.0] * 3 + [1.0] * 3)
+    return E.np_row_sums(J, J @ np.asarray(xi, float) + noise * (rng.random(n) - 0.5))[0]
+
+
+def run_loop(seq, xf, max_iter=25, min_pairs=100, eps_rot=1e-9, eps_trans=1e-9):
+    """np_gauss_newton fed the sums of `seq`, one per evaluation; also the poses it asked for"""
+    asked, it = [], iter(seq)
+
+    def eval_sums(x):
+        asked.append(x)
+        return next(it)
+    return E.np_gauss_newton(eval_sums, xf, CENTRE, max_iter, min_pairs, eps_rot, eps_trans), asked
+
+
+def test_loop_verdicts_on_crafted_sums():
+    """map_align_main.cpp's sequences through the yardstick's loop: the same verdicts, iteration counts and returned poses"""
+    x0 = E.about(E.rotation(12.0, (1, -2, 1.5)), (3, -2, 1), CENTRE)
+    xi = (0.02, 0.01, -0.03, 0.3, 0.2, -0.1)
+    good, tiny = crafted_sums(500, xi), crafted_sums(500, (1e-10, -2e-10, 1e-10, 3e-10, 1e-10, -1e-10))
+    for min_pairs in (0, 100):                                    # count 0
+        (xf, verdict, it, sums, step), asked = run_loop([np.zeros(29)], x0, min_pairs=min_pairs)
+        assert verdict == E.FEW_PAIRS and it == 0 and xf is asked[0] and not step.any()
+    noisy = crafted_sums(300, xi, 0.01)                           # max_iter 0; one pair short, FEW_PAIRS comes first
+    (xf, verdict, it, sums, step), asked = run_loop([noisy], x0, max_iter=0, min_pairs=300)
+    assert verdict == E.ITER_LIMIT and it == 0 and xf is asked[0] and not step.any() and sums is noisy
+    assert run_loop([noisy], x0, max_iter=0, min_pairs=301)[0][1] == E.FEW_PAIRS
+    z = np.zeros(29)                                              # a zero matrix with enough pairs
+    z[27], z[28] = 2.0, 500.0
+    (xf, verdict, it, sums, step), asked = run_loop([z], x0)
+    assert verdict == E.SINGULAR and it == 0 and xf is asked[0] and not step.any()
+    (xf, verdict, it, sums, step), asked = run_loop([good, tiny], x0)     # one step, then a step below eps: the stepped pose, not evaluated again
+    want1, s1 = E.np_step(good, CENTRE, x0)
+    want2, s2 = E.np_step(tiny, CENTRE, want1)
+    assert verdict == E.CONVERGED and it == 2 and len(asked) == 2 and np.array_equal(asked[1], want1) and np.array_equal(xf, want2) and np.array_equal(step, s2)
+    assert np.allclose(s1, xi, rtol=0, atol=1e-12) and sums is tiny
+    below = (0.9 * E.EPS_ROT_MIN, 0, 0, 0, 0.9 * E.EPS_TRANS_MIN, 0)      # the eps floor
+    rot_above = (1.1 * E.EPS_ROT_MIN, 0, 0, 0, 0.9 * E.EPS_TRANS_MIN, 0)
+    trans_above = (0.9 * E.EPS_ROT_MIN, 0, 0, 0, 1.1 * E.EPS_TRANS_MIN, 0)
+    (xf, verdict, it, sums, step), _ = run_loop([crafted_sums(500, below)], x0, eps_rot=0.0, eps_trans=0.0)
+    assert verdict == E.CONVERGED and it == 1 and 0 < step[0] < E.EPS_ROT_MIN and 0 < step[4] < E.EPS_TRANS_MIN
+    for above in (rot_above, trans_above):                        # goes on: the second evaluation ends it
+        (xf, verdict, it, sums, step), asked = run_loop([crafted_sums(500, above), np.zeros(29)], x0, eps_rot=0.0, eps_trans=0.0)
+        assert verdict == E.FEW_PAIRS and it == 1 and len(asked) == 2
+    assert run_loop([crafted_sums(500, rot_above)], x0, eps_rot=2 * E.EPS_ROT_MIN, eps_trans=0.0)[0][1] == E.CONVERGED
+    few = crafted_sums(99, xi, 0.5)                               # FEW_PAIRS after one step: the pose evaluated before it
+    (xf, verdict, it, sums, step), asked = run_loop([good, few], x0)
+    assert verdict == E.FEW_PAIRS and it == 1 and xf is asked[0] and np.array_equal(step, s1) and sums is few and np.array_equal(asked[1], want1)
+    s = x0.copy()                                                 # a start that is not rigid: the yardstick, like kf_map_refine_poses, goes on
+    s[:, :3] *= 1.5
+    (xf, verdict, it, sums, step), asked = run_loop([good, np.zeros(29)], s)
+    assert verdict == E.FEW_PAIRS and it == 1 and len(asked) == 2
 
 
 def test_host_side_under_sanitizers(tmp_path):
